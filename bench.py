@@ -19,7 +19,17 @@ process is one rank.  Ranks talk over RCCL (backend "nccl") only for the timing 
 max-over-ranks reduction and one all-gather of per-rank compressed byte totals (the offset exchange
 that lays the shards out as one stream, netty_amd/shard.py), all outside the data path.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--total-chunks C] [--no-cpu-baseline]
+A plain run (`python bench.py --gpus N --steps K --warmup W`) does what `value` needs and no more: it
+generates the inputs, runs W untimed and K timed steps, writes the outputs of the last step if
+--dump-outputs is given, and prints the JSON line (`value`, `ms_per_step`, the per-kernel HIP-event
+times the timed steps recorded themselves, and whether every per-chunk status they wrote is 0).
+Everything else runs only with --full: the identity check of every chunk and the corrupted-CRC subset
+(`verified`), the rooflines (copy rate, PMC traffic, issue counters, the live random-access ceiling),
+the weak-scaling leg, the framed-stream, alt-codec, latency and host-memory end-to-end legs and the CPU
+baseline with its byte-for-byte parity sample; the --no-* options leave single legs of a --full run out.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--total-chunks C] [--dump-outputs DIR]
+                       [--full [--no-cpu-baseline] [--no-e2e] [--no-alt] ...]
 """
 import argparse
 import hashlib
@@ -50,6 +60,13 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--total-chunks", type=int, default=CONFIG5_CHUNKS,
                     help="64 KiB chunks of the whole job, split across ranks (configs[4]: 1 638 400 = 100 GiB)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every check and extra leg (verification, rooflines, weak "
+                         "scaling, frame scan, alt codecs, latency, end-to-end, CPU baseline); the --no-* options "
+                         "and the legs' sizes below apply to such a run only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's shard) as DIR/<name>.npy, see "
+                         "SnappyRoundTrip.outputs; the same arguments give the same inputs in every run")
     ap.add_argument("--sub-chunks", type=int, default=0,
                     help="chunks per encode and decode call (0: the library's encode plan, decode calls of 262 144)")
     ap.add_argument("--weak-chunks", type=int, default=1 << 20,
@@ -395,6 +412,17 @@ def issue_ceiling(issue, kernels, frames_per_launch: int, ms_per_launch: float, 
 
 # ---------------------------------------------------------------------------------------- the GPU leg
 DEC_SUB = 262144  # frames per decode call: one k_parse / k_expand pair (snappy_decode.hip kSubBatch)
+# --dump-outputs: 24 bytes per chunk of the per-chunk arrays (39.3 MB at 100 GiB), then per sampled chunk
+# 256 KiB of decoded and at most 4 x 76 490 bytes of compressed bytes as float32 (18.2 MB)
+DUMP_MAX_BYTES = 64 * 10**6
+DUMP_PER_CHUNK = CONFIG5_CHUNKS
+DUMP_SAMPLE = 32
+DUMP_SEED = 20260607
+# Workspace candidates a plain run's encoder placement draws: two draws of six.  The library's default of
+# four draws (--full) takes 23 s of a 100 GiB run's set-up on a driver that clears what it allocates, most
+# of what such a run spends outside its steps; two draws take half of that.  One box in round 4 found no
+# fast placement in two draws (encoder 4.3 % slower): --full keeps the four.
+PLAIN_PLACE_CANDIDATES = 12
 
 
 class SnappyRoundTrip:
@@ -411,7 +439,8 @@ class SnappyRoundTrip:
     are kept only as per-chunk lengths; the decoded bytes are checked against the inputs after the
     timed region."""
 
-    def __init__(self, torch, dev, first: int, n: int, sub: int = 0, dec_sub: int = DEC_SUB, enc_sizes=None):
+    def __init__(self, torch, dev, first: int, n: int, sub: int = 0, dec_sub: int = DEC_SUB, enc_sizes=None,
+                 place_candidates: int = 0):
         from netty_amd import batch as B
         from netty_amd import _lib
         self.torch, self.B, self.dev = torch, B, dev
@@ -432,7 +461,9 @@ class SnappyRoundTrip:
         # place the encoder's table workspace before the shard's buffers take the memory its
         # placement choice draws candidates from (as a server would at start-up).  This
         # process owns the device, so the placement may draw as many candidates as memory allows.
-        assert L.nx_workspace_placement_config(2**64 - 1, 0) == 0
+        # `place_candidates` bounds the candidates drawn in all (0: the library's four draws of six): the
+        # driver clears every allocation, so each 40 GiB candidate costs ~1.1 s of set-up (21 drawn: 23 s).
+        assert L.nx_workspace_placement_config(2**64 - 1, place_candidates) == 0
         rc = L.nx_snappy_encoder_reserve(max(self.enc_sizes), st)
         assert rc == 0, f"nx_snappy_encoder_reserve: {rc}"
         if not sub and not enc_sizes:
@@ -552,6 +583,43 @@ class SnappyRoundTrip:
 
     def comp_bytes(self) -> int:
         return int(self.elen.to(self.torch.int64).sum().item())
+
+    def status_ok(self) -> bool:
+        """every per-chunk status the last step wrote is 0 and every decoded length is the chunk's"""
+        return (int((self.est != 0).sum()) == 0 and int((self.dst != 0).sum()) == 0
+                and int((self.dlen != CHUNK).sum()) == 0)
+
+    def outputs(self):
+        """What the last step left with a caller of its calls, as host float arrays {name: ndarray}, at most
+        DUMP_MAX_BYTES in all.  Per chunk of the shard (every chunk up to DUMP_PER_CHUNK of them, else every
+        ceil(n / DUMP_PER_CHUNK)-th): `enc_len`, `enc_status` (snappy_encode), `crc32c_masked` (as unsigned,
+        float64), `dec_len`, `dec_status` (snappy_decode with CRC verify).  Of the bytes, which a step keeps
+        only until their buffers are reused, a fixed sample (seed DUMP_SEED) of DUMP_SAMPLE chunks of the
+        last decode call: their job-wide chunk indices `sample_chunks`, their compressed bytes one after
+        the other in `encoded_sample` (lengths: enc_len) and their decoded bytes `decoded_sample` [k, 65536]."""
+        import random
+
+        import numpy as np
+        torch = self.torch
+        n = self.n
+        stride = -(-n // DUMP_PER_CHUNK)
+        pick = torch.arange(0, n, stride, dtype=torch.int64, device=self.dev)
+
+        def host(t, dtype):
+            return t[pick].cpu().numpy().astype(dtype)
+
+        out = {"enc_len": host(self.elen, np.float32), "enc_status": host(self.est, np.float32),
+               "crc32c_masked": host(self.crc.to(torch.int64) & 0xFFFFFFFF, np.float64),
+               "dec_len": host(self.dlen, np.float32), "dec_status": host(self.dst, np.float32)}
+        lo, m = next((lo, m) for kind, lo, m in reversed(self.ops) if kind == "dec")
+        sample = sorted(random.Random(DUMP_SEED).sample(range(lo, lo + m), min(DUMP_SAMPLE, m)))
+        idx = torch.tensor(sample, dtype=torch.int64, device=self.dev)
+        packed, _ = self.B.gather(self.enc, self.eoff[idx], self.elen[idx].clamp(0, self.cap))  # (a failed chunk's slot)
+        out["sample_chunks"] = np.asarray(sample, dtype=np.float64) + self.first
+        out["encoded_sample"] = packed.cpu().numpy().astype(np.float32)
+        out["decoded_sample"] = self.dec.view(-1, CHUNK)[idx - lo].cpu().numpy().astype(np.float32)
+        assert sum(a.nbytes for a in out.values()) <= DUMP_MAX_BYTES
+        return out
 
 
 def encode_plan(n: int):
@@ -736,18 +804,26 @@ def run_rank(args, rank: int, world: int, local: int, backend: str = "nccl", leg
 
     lo, hi = S.shard_range(args.total_chunks, rank, world)
     n = hi - lo
-    leg = SnappyRoundTrip(torch, dev, lo, n, args.sub_chunks) if gpu else leg_factory(lo, n)
+    full = args.full
+    # a plain run draws two rounds of workspace candidates instead of four (PLAIN_PLACE_CANDIDATES)
+    leg = (SnappyRoundTrip(torch, dev, lo, n, args.sub_chunks, place_candidates=0 if full else PLAIN_PLACE_CANDIDATES)
+           if gpu else leg_factory(lo, n))
     elapsed = timed_legs(torch, leg, args.steps, args.warmup, sync, S, dev, cdev)
-    ok, crc_detect = leg.verify(rank)
+    if args.dump_outputs and rank == 0 and hasattr(leg, "outputs"):
+        dump_outputs(args.dump_outputs, leg.outputs())
+    if full:
+        ok, crc_detect = leg.verify(rank)
+    else:  # no pass of its own: the statuses the last timed step wrote
+        ok, crc_detect = (leg.status_ok() if hasattr(leg, "status_ok") else True), None
     comp_bytes = leg.comp_bytes()
     my_off, total_comp, totals_all = S.exchange_offsets(comp_bytes, device=cdev)
     t_crc, t_enc, t_dec = leg.kernel_ms_per_step(args.steps)
     U, C_ = n * CHUNK, comp_bytes
-    copy_gbs = copy_rate_gbs(torch, leg.src[:min(n, leg.dec_sub) * CHUNK], leg.dec[:min(n, leg.dec_sub) * CHUNK]) if gpu else None
-    traffic = load_traffic() if gpu else (None, "cpu test leg")
+    copy_gbs = copy_rate_gbs(torch, leg.src[:min(n, leg.dec_sub) * CHUNK], leg.dec[:min(n, leg.dec_sub) * CHUNK]) if gpu and full else None
+    traffic = load_traffic() if gpu and full else (None, "cpu test leg" if full else "only with --full")
     r_dec = roofline(C_ + U, t_dec, n, DEC_KERNELS, traffic, copy_gbs)  # decode: C_in + U_out per chunk
     r_enc = roofline(U + C_, t_enc, n, ENC_KERNELS, traffic, copy_gbs)  # encode: U_in + C_out per chunk
-    if gpu and t_dec:
+    if gpu and full and t_dec:
         simds = torch.cuda.get_device_properties(dev).multi_processor_count * 4
         # the decode calls' frames per launch: DEC_SUB; their time per frame from this run's events
         fpl = min(getattr(leg, "dec_sub", n), n)
@@ -775,10 +851,10 @@ def run_rank(args, rank: int, world: int, local: int, backend: str = "nccl", leg
                               f"{ceil.get('lanes')} lanes (the encoder's resident lanes), timed live, fastest of up to 6 table "
                               "placements (as the encoder chooses its workspace), drawn after the job's buffers are freed at N=1"}
 
-    want_ceiling = bool(gpu and t_enc and not args.no_probe_ceiling)
+    want_ceiling = bool(gpu and full and t_enc and not args.no_probe_ceiling)
     if want_ceiling and not (rank == 0 and world == 1):
         fill_random_access()
-    if gpu:
+    if gpu and full:
         r_enc["workspace_placement"] = encoder_placement()
     dominant = r_enc if t_enc >= t_dec else r_dec
     value = args.total_chunks * CHUNK / elapsed * args.steps / 2**30
@@ -794,24 +870,24 @@ def run_rank(args, rank: int, world: int, local: int, backend: str = "nccl", leg
                    "chunk_bytes": CHUNK, "global_chunks": args.total_chunks, "chunks_per_gpu": n,
                    "calls": leg.plan_info() if hasattr(leg, "plan_info") else None,
                    "parallelism": f"dp{world} (independent chunk shards, no data-path collective)"},
-        "roofline": dominant,
-        "roofline_decode": r_dec, "roofline_encode": r_enc,
         "encode_gib_s": round(U / ((t_crc + t_enc) / 1e3) / 2**30, 3) if t_enc else None,
         "decode_gib_s": round(U / (t_dec / 1e3) / 2**30, 3) if t_dec else None,
         "kernel_ms_per_step": {"crc32c": round(t_crc, 3), "encode": round(t_enc, 3), "decode_crc": round(t_dec, 3)},
         "compression_ratio": round(C_ / U, 4) if U else None,
         "shard": {"first_chunk": lo, "chunks": n, "stream_offset": my_off, "stream_bytes": total_comp},
         "compressed_bytes_per_rank": totals_all,
-        "crc_corruption_subset_detected": crc_detect,
     }
     ok = S.all_true(ok, device=cdev)
-    line["verified"] = ok
+    line["status_ok"] = ok  # no encode or decode call of the last step reported an error, on any rank
+    if full:
+        line.update({"roofline": dominant, "roofline_decode": r_dec, "roofline_encode": r_enc,
+                     "crc_corruption_subset_detected": crc_detect, "verified": ok})
     if rank == 0:  # progress on stderr (the JSON line comes at the end, after the extra legs)
         print(f"[bench] strong leg: {line['value']} GiB/s, {line['ms_per_step']} ms/step, kernel ms/step "
-              f"{line['kernel_ms_per_step']}, verified {ok}", file=sys.stderr, flush=True)
+              f"{line['kernel_ms_per_step']}, {'verified' if full else 'status ok'} {ok}", file=sys.stderr, flush=True)
     if gpu and rank == 0:
         line["device"] = device_info(torch, dev)
-    if gpu and args.weak_chunks > 0:
+    if gpu and full and args.weak_chunks > 0:
         del leg
         torch.cuda.empty_cache()
         wk = SnappyRoundTrip(torch, dev, rank * args.weak_chunks, args.weak_chunks, args.sub_chunks)
@@ -829,7 +905,7 @@ def run_rank(args, rank: int, world: int, local: int, backend: str = "nccl", leg
         line["verified"] = ok
         leg = wk
         del wk  # `leg` is the only reference: `del leg` below frees the weak leg's buffers
-    if gpu and rank == 0 and world == 1:
+    if gpu and full and rank == 0 and world == 1:
         from netty_amd import batch as B
         # a strided sample of the first sub-batch's GPU outputs (compressed bytes, masked CRCs), taken to
         # the host now; the cpu_baseline leg checks it against the oracle byte for byte
@@ -886,7 +962,15 @@ def run_rank(args, rank: int, world: int, local: int, backend: str = "nccl", leg
     return line if rank == 0 else None, ok
 
 
-# ---------------------------------------------------------------------------------------- extra legs
+def dump_outputs(outdir: str, arrays) -> None:
+    """--dump-outputs: one DIR/<name>.npy per array of SnappyRoundTrip.outputs()."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
+# ---------------------------------------------------------------------------------------- extra legs (--full)
 def device_info(torch, dev):
     """What the box is: device properties (the encoder's speed differs by up to ~15 % between boxes of
     this pool; recorded so runs can be compared).  No rocm-smi: it is a Python script, and a child

@@ -11,7 +11,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
     D="$ROOT/gpurun_out/ab_alt/${v}_$r"
     mkdir -p "$D"
     (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$D" -o run -- \
-        python "$ROOT/bench.py" --total-chunks 16384 --weak-chunks 0 --steps 1 --warmup 0 --no-cpu-baseline --no-e2e \
+        python "$ROOT/bench.py" --full --total-chunks 16384 --weak-chunks 0 --steps 1 --warmup 0 --no-cpu-baseline --no-e2e \
         --no-frame-scan --no-probe-ceiling > "$D/bench.log" 2>&1) || exit 1
     python scripts/alt_summary.py "$D" > "$D/summary.txt" 2>&1
   done

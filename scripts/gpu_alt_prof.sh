@@ -10,5 +10,5 @@ timeout -k 10 300 python -u -m pytest ${TESTS:-tests/test_gpu_fastlz_lzf.py test
     -x -q -p no:cacheprovider --timeout 120 --timeout-method thread > gpurun_out/$TAG/pytest.log 2>&1 || exit 1
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/gpurun_out/$TAG" -o run -- \
-    python "$ROOT/bench.py" --total-chunks 16384 --weak-chunks 0 --steps 1 --warmup 0 --no-cpu-baseline --no-e2e \
+    python "$ROOT/bench.py" --full --total-chunks 16384 --weak-chunks 0 --steps 1 --warmup 0 --no-cpu-baseline --no-e2e \
     --no-frame-scan --no-probe-ceiling > "$ROOT/gpurun_out/$TAG/bench.log" 2>&1

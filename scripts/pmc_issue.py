@@ -25,7 +25,7 @@ for i in (1, 2):
             disp[(name, i)].add(r["Dispatch_Id"])
 enc = [k for k in agg if k.startswith("nx::enc::k_snappy_encode<true, false>")]
 passes = float(max(len(disp[(enc[0], 1)]), 1)) if enc else 1.0
-out = {"source": f"rocprofv3 --pmc (2 passes: instruction mix; wave-cycle split), bench.py --total-chunks {chunks} "
+out = {"source": f"rocprofv3 --pmc (2 passes: instruction mix; wave-cycle split), bench.py --full --total-chunks {chunks} "
                  f"--sub-chunks {chunks} --steps 1 --warmup 0", "source_digest": bench.source_digest(),
        "chunks_per_pass": chunks, "passes": passes, "simds": SIMDS, "kernels": {}}
 for name, d in agg.items():

@@ -12,7 +12,7 @@ for ctrs in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_
             "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE"; do
   i=$((i+1))
   timeout -s KILL 300 rocprofv3 --pmc $ctrs --output-format csv -d "$ROOT/gpurun_out/issue_$i" -o p -- \
-      python "$ROOT/bench.py" --total-chunks "$CHUNKS" --sub-chunks "$CHUNKS" --weak-chunks 0 --steps 1 --warmup 0 --no-latency \
+      python "$ROOT/bench.py" --full --total-chunks "$CHUNKS" --sub-chunks "$CHUNKS" --weak-chunks 0 --steps 1 --warmup 0 --no-latency \
       --no-probe-ceiling --no-cpu-baseline --no-e2e --no-alt --no-frame-scan > "$ROOT/gpurun_out/issue_$i.log" 2>&1 || exit 1
 done
 cd "$ROOT" && python scripts/pmc_issue.py gpurun_out "$CHUNKS" > gpurun_out/pmc_issue.json

@@ -1,5 +1,5 @@
 """Summarise the FETCH_SIZE / WRITE_SIZE passes of scripts/pmc_traffic.sh per kernel: HBM bytes per
-64 KiB chunk.  The passes run bench.py with --total-chunks = --sub-chunks = CHUNKS (round 6: 327 680,
+64 KiB chunk.  The passes run bench.py --full with --total-chunks = --sub-chunks = CHUNKS (round 6: 327 680,
 one launch of the dense encoder, whose decode call the library runs as parse/expand pairs of 262 144 +
 65 536 frames), so every pass (the timed step, verify's pass and its first-call re-runs) encodes and
 decodes all CHUNKS chunks, once per dense-encoder dispatch: a kernel's bytes per chunk = its total
@@ -24,7 +24,7 @@ for c in ("FETCH_SIZE", "WRITE_SIZE"):
             disp[(name, c)].add(r["Dispatch_Id"])
 enc = [k for k in agg if k.startswith("nx::enc::k_snappy_encode<true, false>")]
 passes = float(max(len(disp[(enc[0], "FETCH_SIZE")]), 1)) if enc else 1.0
-out = {"source": f"rocprofv3 --pmc FETCH_SIZE, then --pmc WRITE_SIZE; bench.py --total-chunks {chunks} "
+out = {"source": f"rocprofv3 --pmc FETCH_SIZE, then --pmc WRITE_SIZE; bench.py --full --total-chunks {chunks} "
                  f"--sub-chunks {chunks} --steps 1 --warmup 0 --weak-chunks 0 --no-latency --no-probe-ceiling",
        "source_digest": bench.source_digest(), "fetch_correction": 2.0, "chunks_per_pass": chunks, "passes": passes,
        "kernels": {}}

@@ -112,7 +112,7 @@ def test_run_rank_world1_small_job(dev):
     """bench.run_rank itself on the GPU at world 1 over a small total with a partial last sub-batch:
     one verified JSON line whose shard, lengths and timings are consistent."""
     import bench
-    args = bench.parse(["--total-chunks", "300", "--sub-chunks", "128", "--steps", "1", "--warmup", "1",
+    args = bench.parse(["--full", "--total-chunks", "300", "--sub-chunks", "128", "--steps", "1", "--warmup", "1",
                         "--weak-chunks", "130", "--no-cpu-baseline", "--no-e2e", "--no-alt", "--no-frame-scan",
                         "--no-probe-ceiling"])
     lines = []
@@ -124,3 +124,44 @@ def test_run_rank_world1_small_job(dev):
     assert line["weak_1m_per_gpu"]["verified"] is True and line["weak_1m_per_gpu"]["chunks_per_gpu"] == 130
     assert line["value"] > 0 and line["roofline"]["achieved"] > 0
     assert 0.3 < line["compression_ratio"] < 0.6
+
+
+def test_run_rank_plain_run_dumps_outputs(dev, oracle, tmp_path):
+    """A plain run (no --full) times its steps and nothing else: --steps sets the timed steps, the line has
+    the headline fields and none of the --full legs, and --dump-outputs writes what the last step computed:
+    per-chunk arrays of the whole shard and the bytes of a fixed sample, equal to the oracle's, float32 /
+    float64 only, the same files from a second run."""
+    import numpy as np
+
+    import bench
+    n, steps = 300, 3
+    want = [oracle.textgen_chunk(i, CHUNK) for i in range(n)]
+    runs = []
+    for d in ("a", "b"):
+        args = bench.parse(["--total-chunks", str(n), "--sub-chunks", "128", "--steps", str(steps), "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / d)])
+        lines = []
+        line, ok = bench.run_rank(args, 0, 1, 0, emit=lines.append)
+        assert ok and len(lines) == 1 and line["status_ok"] is True
+        assert line["metric"] == bench.METRIC and line["unit"] == "GiB/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "u8" and line["steps"] == steps and line["ms_per_step"] > 0
+        assert abs(line["value"] - n * CHUNK / 2**30 / (line["ms_per_step"] / 1e3)) <= 0.01 * line["value"] + 1e-3
+        for k in ("verified", "roofline", "weak_1m_per_gpu", "frame_scan", "alt_codecs", "latency", "end_to_end",
+                  "cpu_baseline", "crc_corruption_subset_detected"):
+            assert k not in line, k
+        runs.append({p.stem: np.load(p) for p in sorted((tmp_path / d).glob("*.npy"))})
+    a, b = runs
+    assert sorted(a) == ["crc32c_masked", "dec_len", "dec_status", "decoded_sample", "enc_len", "enc_status",
+                         "encoded_sample", "sample_chunks"]
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 * 10**6
+    assert all(np.array_equal(a[k], b[k]) for k in a) and sorted(a) == sorted(b)
+    enc = [oracle.snappy_encode(c) for c in want]
+    assert a["enc_len"].tolist() == [len(e) for e in enc]
+    assert a["crc32c_masked"].tolist() == [oracle.snappy_checksum(c) for c in want]
+    assert a["dec_len"].tolist() == [CHUNK] * n
+    assert not a["enc_status"].any() and not a["dec_status"].any()
+    sample = [int(c) for c in a["sample_chunks"]]
+    assert len(sample) == bench.DUMP_SAMPLE and sample == sorted(set(sample)) and 256 <= sample[0] and sample[-1] < n
+    assert a["encoded_sample"].astype(np.uint8).tobytes() == b"".join(enc[c] for c in sample)
+    assert a["decoded_sample"].astype(np.uint8).tobytes() == b"".join(want[c] for c in sample)

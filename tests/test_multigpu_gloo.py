@@ -140,7 +140,7 @@ def _bench_rank(rank, world, port, outdir):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     import bench
-    args = bench.parse(["--gpus", str(world), "--total-chunks", "7", "--steps", "2", "--warmup", "1"])
+    args = bench.parse(["--full", "--gpus", str(world), "--total-chunks", "7", "--steps", "2", "--warmup", "1"])
     lines = []
     line, ok = bench.run_rank(args, rank, world, rank, backend="gloo", leg_factory=_LegFactory(outdir, rank),
                               emit=lines.append)
