@@ -21,7 +21,7 @@
 //     pieces — the batch's output is cut into PIECES: the intersection of a record with an aligned
 //              output dword.  A pass gives one piece to each lane; the piece's record comes from a
 //              piece-start bitmask (mbcnt + max-scan), its 1-4 bytes from one unaligned 4-byte read
-//              of the input stage (literal), the ring (copy <= 4 KiB back) or HBM (older output of
+//              of the input stage (literal), the ring (copy <= kRing bytes back) or HBM (older output of
 //              this frame, already flushed and drained), and it is written with one ds_mskor.
 //     rounds — a copy whose source bytes are produced in the same pass waits until the pieces
 //              producing them (found through a per-pass byte -> piece map) are done; overlapping
@@ -53,13 +53,16 @@ namespace nx {
 namespace dec {
 
 constexpr int kWaves = 12;        // waves per workgroup (2 workgroups per CU → 24 waves/CU)
-#ifndef NX_RING  // decoded-output history per wave, bytes (a power of two, >= 2048: far reads stay two flushes back)
+#ifndef NX_RING  // decoded-output history per wave, bytes (a power of two, >= 2048: far reads stay two flushes back, see flush_to)
 #define NX_RING 2048  // (round 6: 4096 -> 2048 makes room for 32 k_expand waves per CU, below)
 #endif
 constexpr int kRing = NX_RING;     // decoded-output history per wave
-static_assert((kRing & (kRing - 1)) == 0 && kRing >= 2048, "ring");
 constexpr int kStage = 1024;      // compressed-input ring per wave
 constexpr int kFB = 512;          // flush block (64 lanes x 8 B)
+constexpr int kPass = 256;        // most output bytes of one expand pass (64 pieces x one dword)
+// The ring indexes by mask, and a far copy must read behind the two newest flush blocks (flush_to has
+// the derivation): kRing >= 3 kFB + kPass + 2, which of the powers of two leaves 2048 and up.
+static_assert((kRing & (kRing - 1)) == 0 && kRing >= 3 * kFB + kPass + 2, "ring");
 constexpr int32_t kGuardTrip = -99;
 constexpr uint32_t kRecCap = 16384;      // records per frame slot (64 KiB)
 constexpr int32_t kNeedFused = -1000;    // internal status: the frame goes to k_decode_fused
@@ -73,7 +76,7 @@ constexpr int kTabWords = 4 * 256 + 4 * 256;
 constexpr int kTabBytes = kTabWords * 4;
 
 struct WaveLds {
-    uint32_t ring[kRing / 4];    // dword 0 .. 1023
+    uint32_t ring[kRing / 4];    // dwords [0, kRing / 4): expand_tags addresses the ring from the block's first dword
     // tag records {start (absolute output position), x (bit31 = copy; low 31 bits = literal source
     // position or copy offset)}; the start of record r+1 is the end of record r (sentinel after the last)
     uint32_t tagw[2 * 64 + 2];
@@ -246,9 +249,17 @@ struct FrameIO {
         const uint8_t* ring8 = reinterpret_cast<const uint8_t*>(L.ring);
         while (flushed + (uint32_t)kFB <= limit) {
             wave_sync();
-            // Far reads target q + 4 <= flushed - 1024, i.e. blocks at least two flushes older than
-            // the newest; vmcnt counts in issue order, so vmcnt(1) retires every store but (at
-            // most) the newest vector-memory op.
+            // vmcnt counts in issue order, so vmcnt(1) retires every store but (at most) the newest
+            // vector-memory op: after this flush the stores of the two newest blocks, output
+            // [flushed - 2 kFB, flushed), may still be in flight, everything older has landed.  A far
+            // copy piece loads the dword [sp, sp + 4) of the frame's own output from HBM, so it needs
+            //     sp + 4 <= flushed - 2 kFB.
+            // expand_tags takes the far path for sp < pe - kRing, i.e. sp + 4 <= pe - kRing + 3, with
+            // [ps, pe) the pass's output, pe - ps <= kPass (64 pieces of one dword).  A pass starts
+            // where the one before ended and that one flushed every whole block up to its end, so
+            // flushed >= ps - (kFB - 1) >= pe - kPass - kFB + 1.  The far path is therefore safe when
+            //     pe - kRing + 3 <= pe - kPass - kFB + 1 - 2 kFB,  i.e.  kRing >= 3 kFB + kPass + 2 = 1794:
+            // 2048 leaves a margin of 254 bytes, 4096 of 2302 (the static_assert at kRing holds it).
             asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
             const uint2 d = *reinterpret_cast<const uint2*>(&ring8[(flushed + 8u * lane) & (kRing - 1)]);
             uint8_t* o = dst + flushed + 8u * lane;
@@ -332,7 +343,7 @@ __device__ bool expand_tags(FrameIO& io, uint32_t lds_base, uint32_t O, uint32_t
                             bool staged = true) {
     WaveLds& L = io.L;
     const uint8_t* ring8 = reinterpret_cast<const uint8_t*>(L.ring);
-    const uint32_t* lds32 = L.ring;  // ring at dwords [0, 1024), stage at [kStageDw, kStageDw + 256)
+    const uint32_t* lds32 = L.ring;  // ring at dwords [0, kRing / 4), stage at [kStageDw, kStageDw + kStage / 4)
     const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(prodm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)prodm, 0u));
     if (prod) *reinterpret_cast<uint2*>(&L.tagw[2 * rank]) = make_uint2(ostart, xv);
     if (lane == 0) L.tagw[2 * (uint32_t)__popcll(prodm)] = E;  // sentinel: end of the last tag

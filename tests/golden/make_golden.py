@@ -3,9 +3,17 @@ own tests, each tagged with the file:line it comes from.  Paths are relative to
 /root/reference/codec-compression/src/test/java/io/netty/handler/codec/compression/ unless absolute.
 
 Run: python tests/golden/make_golden.py   (no reference access needed: the vectors are inline data)
+
+With pyarrow installed it also writes tests/golden/foreign_streams.json: eight text-like and mixed
+inputs of 4-48 KiB with the Snappy and LZ4 blocks that pyarrow's bundled libsnappy and liblz4 make of
+them, encoders that share nothing with this project's, for the GPU decoders to decode
+(tests/test_gpu_decode_grammar.py needs no pyarrow: inputs and streams are both stored).
 """
+import base64
 import json
 import os
+import sys
+import zlib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -118,6 +126,44 @@ def main():
     with open(os.path.join(HERE, "kat.json"), "w") as f:
         json.dump(kat, f, indent=1)
     print("wrote", os.path.join(HERE, "kat.json"))
+    foreign_streams()
+
+
+def foreign_inputs():
+    """(name, bytes): text-like chunks, and text with random runs, zero runs and a long period spliced in."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from oracle import pyoracle as O
+    out = []
+    for i, kib in enumerate((4, 6, 8, 12, 48)):
+        out.append((f"textgen_{kib}k", O.textgen_chunk(9000 + i, kib * 1024)))
+    for i, kib in enumerate((4, 8, 16)):
+        n, parts, k = kib * 1024, [], 0
+        while sum(map(len, parts)) < n:
+            parts.append(O.textgen_chunk(9100 + 16 * i + k, 700 + 130 * k))
+            parts.append((O.java_random_bytes(77 + k, 96), bytes(300), bytes(range(37)) * 9, b"ab" * 70)[k % 4])
+            k += 1
+        out.append((f"mixed_{kib}k", b"".join(parts)[:n]))
+    return out
+
+
+def foreign_streams():
+    try:
+        import pyarrow as pa
+    except ImportError:
+        print("pyarrow not installed: foreign_streams.json left as it is")
+        return
+    snappy, lz4 = pa.Codec("snappy"), pa.Codec("lz4_raw")
+    enc = lambda b: base64.b64encode(b).decode("ascii")  # noqa: E731
+    cases = []
+    for name, data in foreign_inputs():
+        cases.append({"name": name, "length": len(data), "input_zlib": enc(zlib.compress(data, 9)),
+                      "snappy": enc(snappy.compress(data).to_pybytes()), "lz4": enc(lz4.compress(data).to_pybytes())})
+    doc = {"src": f"pyarrow {pa.__version__}: Codec('snappy') / Codec('lz4_raw') of the inputs (stored zlib-compressed); base64",
+           "cases": cases}
+    path = os.path.join(HERE, "foreign_streams.json")
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1)
+    print("wrote", path, os.path.getsize(path), "bytes")
 
 
 if __name__ == "__main__":
