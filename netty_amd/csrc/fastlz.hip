@@ -495,30 +495,19 @@ extern "C" int32_t nx_fastlz_compress_batch(const uint8_t* in, const uint64_t* i
     NX_CLEAR_STALE_ERROR();
     if (n == 0) return NX_OK;
     if (!in || !in_off || !in_len || !out || !out_off || !out_len || !status) return NX_ERR_INVALID_ARG;
-    int dev = 0, cus = 256;
-    NX_HIP_CHECK(hipGetDevice(&dev));
-    NX_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     const hipStream_t st = (hipStream_t)stream;
-    const size_t per = (size_t)nx::flz::HASH_SIZE * sizeof(uint64_t);
-    nx::WsLease lease(nx::WsKind::FastLzEnc, dev, st);
-    NX_HIP_CHECK(lease.acquire(nx::ws_want(nx::WsKind::FastLzEnc, n, cus)));
-    nx::SharedWs& W = lease.ws();
-    const nx::LaneGrid g = nx::ws_grid(nx::WsKind::FastLzEnc, n, cus, W.slots);
-    uint64_t* ws = static_cast<uint64_t*>(W.p);
-    const uint32_t iters = (uint32_t)((n + g.slots - 1) / g.slots);
-    if ((uint64_t)W.stamp + iters >= 65535u) {
-        NX_HIP_CHECK(hipMemsetAsync(ws, 0, W.slots * per, st));
-        W.stamp = 0;
-    }
-    if (g.spread)
-        hipLaunchKernelGGL(nx::flz::k_compress<true>, dim3(g.grid), dim3(g.block), 0, st, in, in_off, in_len, out, out_off, out_len, level,
-                           u16_limit, status, n, ws, W.stamp);
-    else
-        hipLaunchKernelGGL(nx::flz::k_compress<false>, dim3(g.grid), dim3(g.block), 0, st, in, in_off, in_len, out, out_off, out_len,
-                           level, u16_limit, status, n, ws, W.stamp);
-    NX_HIP_CHECK(hipGetLastError());
-    W.stamp += iters;
-    return NX_OK;
+    const auto launch = [&](size_t base, uint32_t m, const nx::LaneGrid& g, void* tables, uint32_t stamp) {
+        uint64_t* ws = static_cast<uint64_t*>(tables);
+        const int32_t* lv = level ? level + base : nullptr;  // both optional: the kernel tests them for null
+        const int32_t* lim = u16_limit ? u16_limit + base : nullptr;
+        if (g.spread)
+            hipLaunchKernelGGL(nx::flz::k_compress<true>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base, in_len + base, out,
+                               out_off + base, out_len + base, lv, lim, status + base, m, ws, stamp);
+        else
+            hipLaunchKernelGGL(nx::flz::k_compress<false>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base, in_len + base, out,
+                               out_off + base, out_len + base, lv, lim, status + base, m, ws, stamp);
+    };
+    return nx::ws_lane_launch(nx::WsKind::FastLzEnc, 65535u, n, st, launch);
 }
 
 namespace {

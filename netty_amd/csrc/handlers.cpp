@@ -415,6 +415,203 @@ extern "C" int64_t nx_fastlz_frame_encoder_encode(nx_fastlz_frame_encoder* e, co
     return (int64_t)op;
 }
 
+// ======================================================================= FastLZ / LZF / LZ4 decode()
+// One body for the three decoders: the header walk on the host (alt_frames.hpp), every block's
+// arithmetic in one GPU batch, the blocks applied in stream order.  A codec's traits say what differs.
+namespace {
+using nx::af::Blk;
+
+struct FlzSync {
+    static bool skips(const nx_fastlz_frame_decoder& d) { return d.corrupted || d.st.state == 3; }  // CORRUPTED (:197-199)
+    static constexpr auto walk = nx::af::flz_walk;
+    static constexpr bool kReadsOn = true;  // decompress may read past its chunk (in_avail = readable bytes)
+    static size_t stage_end(size_t n, size_t, size_t) { return n; }
+    static int32_t decode(Gpu& g, uint32_t nz) {
+        return nx_fastlz_decompress_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.a5.as<uint32_t>(),
+                                          g.dout.as<uint8_t>(), g.a1.as<uint64_t>(), g.a3.as<uint32_t>(), g.a4.as<int32_t>(), nz, g.s);
+    }
+    static bool block_error(int32_t r, const Blk& b, uint8_t first, int32_t* code, std::string* msg) {
+        return nx::af::flz_block_error(r, b.olen, first, code, msg);
+    }
+    static bool checked(const nx_fastlz_frame_decoder& d, const Blk& b) { return b.has_cks && d.validate; }
+    static int32_t checksum(const uint8_t* base, const uint64_t* off, const uint32_t* len, uint32_t* out, uint32_t n, hipStream_t s) {
+        return nx_adler32_batch(base, off, len, out, n, s);
+    }
+    static bool checksum_error(uint32_t got, const Blk& b, int32_t* code, std::string* msg, size_t* at) {  // :171-180
+        if (got == b.cks) return false;
+        *code = NX_ERR_FASTLZ_CRC_MISMATCH;
+        *msg = nx::af::flz_checksum_error(got, b.cks);
+        *at = b.data;
+        return true;
+    }
+    static bool emits(const Blk& b) { return b.olen > 0; }
+};
+
+struct LzfSync {
+    static bool skips(const nx_lzf_decoder& d) { return d.corrupted || d.st.state == 3; }  // CORRUPTED (:229-231)
+    static constexpr auto walk = nx::af::lzf_walk;
+    static constexpr bool kReadsOn = false;
+    static size_t stage_end(size_t, size_t p, size_t) { return p; }
+    static int32_t decode(Gpu& g, uint32_t nz) {
+        return nx_lzf_decode_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.dout.as<uint8_t>(),
+                                   g.a1.as<uint64_t>(), g.a3.as<uint32_t>(), g.a4.as<int32_t>(), nz, g.s);
+    }
+    static bool block_error(int32_t st, const Blk&, uint8_t, int32_t* code, std::string* msg) {
+        if (st == NX_OK) return false;
+        *code = st;
+        *msg = nx::af::lzf_block_error();
+        return true;
+    }
+    static bool checked(const nx_lzf_decoder&, const Blk&) { return false; }  // LZF blocks carry no checksum
+    static int32_t checksum(const uint8_t*, const uint64_t*, const uint32_t*, uint32_t*, uint32_t, hipStream_t) { return NX_OK; }
+    static bool checksum_error(uint32_t, const Blk&, int32_t*, std::string*, size_t*) { return false; }
+    static bool emits(const Blk& b) { return b.comp || b.clen > 0; }
+};
+
+struct Lz4Sync {
+    static bool skips(const nx_lz4_frame_decoder& d) { return d.corrupted || d.st.state >= 2; }  // FINISHED / CORRUPTED :250-254
+    static constexpr auto walk = nx::af::lz4_walk;
+    static constexpr bool kReadsOn = false;
+    static size_t stage_end(size_t, size_t, size_t last_end) { return last_end; }
+    static int32_t decode(Gpu& g, uint32_t nz) {
+        return nx_lz4_decode_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.dout.as<uint8_t>(),
+                                   g.a1.as<uint64_t>(), g.a3.as<uint32_t>(), g.a4.as<int32_t>(), nz, g.s);
+    }
+    static bool block_error(int32_t st, const Blk&, uint8_t, int32_t* code, std::string* msg) {
+        if (st == NX_OK) return false;  // LZ4Exception → DecompressionException (:240-241)
+        *code = st;
+        *msg = nx::af::lz4_block_error();
+        return true;
+    }
+    static bool checked(const nx_lz4_frame_decoder& d, const Blk&) { return d.validate; }
+    static int32_t checksum(const uint8_t* base, const uint64_t* off, const uint32_t* len, uint32_t* out, uint32_t n, hipStream_t s) {
+        return nx_xxhash32_batch(base, off, len, nx::af::kLz4Seed, out, n, s);
+    }
+    // CompressionUtil.checkChecksum after the payload was skipped (:222-228; Lz4XXHash32.getValue masks, :101)
+    static bool checksum_error(uint32_t h, const Blk& b, int32_t* code, std::string* msg, size_t* at) {
+        const uint32_t got = h & 0x0FFFFFFFu;
+        if (got == b.cks) return false;
+        *code = NX_ERR_LZ4_CHECKSUM_MISMATCH;
+        *msg = nx::af::lz4_checksum_error(got, b.cks);
+        *at = b.end;
+        return true;
+    }
+    static bool emits(const Blk&) { return true; }
+};
+
+template <class C, class D>
+int32_t alt_decode(D* d, const uint8_t* in, size_t n, size_t* consumed, const nx_msg** msgs, size_t* n_msgs, const char** err_msg) {
+    const nx::NoGrowScope no_grow;
+    if (!d || (!in && n) || !consumed || !msgs || !n_msgs) return NX_ERR_INVALID_ARG;
+    MsgList& ml = d->ml;
+    ml.clear();
+    auto finish = [&](int32_t r, size_t rd) {
+        *consumed = rd;
+        *msgs = ml.msgs.data();
+        *n_msgs = ml.msgs.size();
+        if (err_msg) *err_msg = ml.err.empty() ? nullptr : ml.err.c_str();
+        return r;
+    };
+    auto fail = [&](int32_t code, const std::string& msg, size_t rd) {  // the decoder turns CORRUPTED
+        ml.err = msg;
+        d->st.state = 3;
+        d->corrupted = true;
+        return finish(code, rd);
+    };
+    if (C::skips(*d)) return finish(NX_OK, n);
+    // host parse (decode() as callDecode drives it) on a copy of the header state, committed at the end
+    auto ns = d->st;
+    std::vector<Blk> blks;
+    nx::af::WalkErr werr;
+    const size_t p = C::walk(in, n, ns, blks, werr);
+    const uint32_t nb = (uint32_t)blks.size();
+    // decode jobs: every compressed block, into its 16-byte aligned slot of dout
+    std::vector<uint32_t> job(nb), cjob(nb);
+    std::vector<uint64_t> ooff;
+    uint64_t ocap = 0;
+    for (uint32_t i = 0; i < nb; ++i)
+        if (blks[i].comp) {
+            job[i] = (uint32_t)ooff.size();
+            ooff.push_back(ocap);
+            ocap += ((uint64_t)blks[i].olen + 15) & ~15ull;
+        }
+    const uint32_t nz = (uint32_t)ooff.size();
+    // checksum jobs: the decoded blocks first (their bytes in dout), then the raw ones (where they lie
+    // in the staged input, din)
+    const size_t lo = nb ? blks.front().data : 0;
+    std::vector<uint64_t> coff;
+    std::vector<uint32_t> clen;
+    uint32_t ncz = 0;
+    for (int raw = 0; raw < 2; ++raw) {
+        for (uint32_t i = 0; i < nb; ++i) {
+            const Blk& b = blks[i];
+            if (b.comp == (raw != 0) || !C::checked(*d, b)) continue;
+            cjob[i] = (uint32_t)coff.size();
+            coff.push_back(b.comp ? ooff[job[i]] : b.data - lo);
+            clen.push_back(b.comp ? b.olen : b.clen);
+        }
+        if (!raw) ncz = (uint32_t)coff.size();
+    }
+    const uint32_t nck = (uint32_t)coff.size(), ncr = nck - ncz;
+    std::vector<int32_t> res(nz);
+    std::vector<uint32_t> cval(nck);
+    std::vector<uint8_t> hout(ocap);
+    Gpu& g = d->g;
+    if (nz || nck) {  // everything is uploaded before the first launch; one sync at the end
+        const size_t span = C::stage_end(n, p, blks.back().end) - lo;
+        std::vector<uint64_t> ioff(nz);
+        std::vector<uint32_t> ilen(nz), olen(nz), iav(C::kReadsOn ? nz : 0);
+        for (uint32_t i = 0; i < nb; ++i) {
+            const Blk& b = blks[i];
+            if (!b.comp) continue;
+            ioff[job[i]] = b.data - lo;
+            ilen[job[i]] = b.clen;
+            olen[job[i]] = b.olen;
+            if (C::kReadsOn) iav[job[i]] = (uint32_t)(n - b.data);
+        }
+        if (!g.din.ensure(span + 1) || !g.dout.ensure(ocap + 16) || !g.a0.ensure(8ull * nz + 8) || !g.a1.ensure(8ull * nz + 8) ||
+            !g.a2.ensure(4ull * nz + 4) || !g.a3.ensure(4ull * nz + 4) || !g.a4.ensure(4ull * nz + 4) ||
+            !g.a5.ensure(4ull * iav.size()) || !g.a6.ensure(16ull * nck))
+            return finish(NX_ERR_HIP, 0);
+        uint64_t* d_coff = g.a6.as<uint64_t>();
+        uint32_t* d_clen = reinterpret_cast<uint32_t*>(d_coff + nck);
+        uint32_t* d_cval = d_clen + nck;
+        bool ok = g.h2d(g.din.p, in + lo, span) && g.h2d(g.a0.p, ioff.data(), 8ull * nz) && g.h2d(g.a1.p, ooff.data(), 8ull * nz) &&
+                  g.h2d(g.a2.p, ilen.data(), 4ull * nz) && g.h2d(g.a3.p, olen.data(), 4ull * nz) &&
+                  g.h2d(g.a5.p, iav.data(), 4ull * iav.size()) && g.h2d(d_coff, coff.data(), 8ull * nck) &&
+                  g.h2d(d_clen, clen.data(), 4ull * nck);
+        if (!ok) return finish(NX_ERR_HIP, 0);
+        int32_t r = nz ? C::decode(g, nz) : NX_OK;
+        if (r == NX_OK && ncz) r = C::checksum(g.dout.as<uint8_t>(), d_coff, d_clen, d_cval, ncz, g.s);
+        if (r == NX_OK && ncr) r = C::checksum(g.din.as<uint8_t>(), d_coff + ncz, d_clen + ncz, d_cval + ncz, ncr, g.s);
+        if (r != NX_OK) return finish(r, 0);
+        ok = g.d2h(res.data(), g.a4.p, 4ull * nz) && g.d2h(hout.data(), g.dout.p, ocap) && g.d2h(cval.data(), d_cval, 4ull * nck) &&
+             g.sync();
+        if (!ok) return finish(NX_ERR_HIP, 0);
+    }
+    // apply in stream order: a block's failure, then its checksum, then its message
+    for (uint32_t i = 0; i < nb; ++i) {
+        const Blk& b = blks[i];
+        int32_t code = NX_OK;
+        std::string emsg;
+        size_t at = 0;
+        if (b.comp && C::block_error(res[job[i]], b, b.data < n ? in[b.data] : 0, &code, &emsg)) return fail(code, emsg, b.data);
+        if (C::checked(*d, b) && C::checksum_error(cval[cjob[i]], b, &code, &emsg, &at)) return fail(code, emsg, at);
+        if (!C::emits(b)) continue;
+        if (b.comp) {  // decoded bytes are owned by the message list; a raw block is a view of `in`
+            const uint8_t* data = hout.data() + ooff[job[i]];
+            ml.owned.emplace_back(data, data + b.olen);
+            ml.msgs.push_back({ml.owned.back().data(), b.olen});
+        } else {
+            ml.msgs.push_back({in + b.data, b.clen});
+        }
+    }
+    if (werr.set) return fail(werr.code, werr.msg, werr.at);
+    d->st = ns;
+    return finish(NX_OK, p);
+}
+}  // namespace
+
 // ======================================================================= FastLZ frame decoder
 extern "C" nx_fastlz_frame_decoder* nx_fastlz_frame_decoder_new(int32_t validate) {
     auto* d = new nx_fastlz_frame_decoder();
@@ -429,167 +626,7 @@ extern "C" void nx_fastlz_frame_decoder_free(nx_fastlz_frame_decoder* d) { nx_al
 
 extern "C" int32_t nx_fastlz_frame_decoder_decode(nx_fastlz_frame_decoder* d, const uint8_t* in, size_t n, size_t* consumed,
                                                   const nx_msg** msgs, size_t* n_msgs, const char** err_msg) {
-    const nx::NoGrowScope no_grow;
-    if (!d || (!in && n)) return NX_ERR_INVALID_ARG;
-    MsgList& ml = d->ml;
-    ml.clear();
-    size_t rd = 0;
-    auto finish = [&](int32_t r) {
-        *consumed = rd;
-        *msgs = ml.msgs.data();
-        *n_msgs = ml.msgs.size();
-        if (err_msg) *err_msg = ml.err.empty() ? nullptr : ml.err.c_str();
-        return r;
-    };
-    if (d->corrupted || d->st.state == 3) {  // CORRUPTED (:197-199)
-        rd = n;
-        return finish(NX_OK);
-    }
-    struct Blk : nx::af::Blk {
-        int job = -1;
-    };
-    // host parse (FastLzFrameDecoder.decode as driven by callDecode); persistent header state
-    nx::af::FlzState ns = d->st;
-    std::vector<nx::af::Blk> walked;
-    nx::af::WalkErr werr;
-    const size_t p = nx::af::flz_walk(in, n, ns, walked, werr);
-    std::vector<Blk> blks(walked.size());
-    for (size_t i = 0; i < walked.size(); ++i) static_cast<nx::af::Blk&>(blks[i]) = walked[i];
-    // GPU: decompress every compressed block; Adler32 over every produced block if verifying
-    // (decompressed blocks in dout, raw blocks straight from the staged cumulation in din)
-    uint32_t nz = 0;
-    for (auto& b : blks)
-        if (b.comp) b.job = (int)nz++;
-    const uint32_t nb = (uint32_t)blks.size();
-    const bool want_cks = d->validate;
-    std::vector<int32_t> res(nz);
-    std::vector<uint32_t> adl(nb);
-    std::vector<uint64_t> ooff(nz);
-    uint64_t ocap = 0;
-    for (auto& b : blks)
-        if (b.comp) {
-            ooff[b.job] = ocap;
-            ocap += ((uint64_t)b.olen + 15) & ~15ull;
-        }
-    std::vector<uint8_t> hout(ocap);
-    Gpu& g = d->g;
-    uint32_t ncks = 0;
-    for (auto& b : blks) ncks += (b.has_cks && want_cks) ? 1u : 0u;
-    if (nz || ncks) {
-        const size_t lo = blks.front().data;
-        const size_t span = n - lo;  // decompress may read past its chunk (in_avail = readable bytes)
-        std::vector<uint64_t> ioff(nz);
-        std::vector<uint32_t> ilen(nz), iav(nz), olim(nz);
-        for (auto& b : blks)
-            if (b.comp) {
-                ioff[b.job] = b.data - lo;
-                ilen[b.job] = b.clen;
-                iav[b.job] = (uint32_t)(n - b.data);
-                olim[b.job] = b.olen;
-            }
-        // checksum jobs: compressed → (dout, ooff, olen); raw → (din, data-lo, clen)
-        std::vector<uint64_t> czoff, croff;
-        std::vector<uint32_t> czlen, crlen;
-        std::vector<uint32_t> cz_blk, cr_blk;
-        for (uint32_t i = 0; i < nb; ++i) {
-            const Blk& b = blks[i];
-            if (!(b.has_cks && want_cks)) continue;
-            if (b.comp) {
-                czoff.push_back(ooff[b.job]);
-                czlen.push_back(b.olen);
-                cz_blk.push_back(i);
-            } else {
-                croff.push_back(b.data - lo);
-                crlen.push_back(b.clen);
-                cr_blk.push_back(i);
-            }
-        }
-        const uint32_t ncz = (uint32_t)czoff.size(), ncr = (uint32_t)croff.size();
-        if (!g.din.ensure(span + 1) || !g.dout.ensure(ocap + 16) || !g.a0.ensure(8ull * nz + 8) || !g.a1.ensure(8ull * nz + 8) ||
-            !g.a2.ensure(4ull * nz + 4) || !g.a3.ensure(4ull * nz + 4) || !g.a4.ensure(4ull * nz + 4) || !g.a5.ensure(4ull * nz + 4) ||
-            !g.a6.ensure(16ull * (ncz + ncr) + 16))
-            return finish(NX_ERR_HIP);
-        uint64_t* d_coff = g.a6.as<uint64_t>();
-        uint32_t* d_clen = reinterpret_cast<uint32_t*>(d_coff + ncz + ncr);
-        uint32_t* d_cval = d_clen + ncz + ncr;
-        std::vector<uint64_t> coff(czoff);
-        coff.insert(coff.end(), croff.begin(), croff.end());
-        std::vector<uint32_t> clen(czlen);
-        clen.insert(clen.end(), crlen.begin(), crlen.end());
-        bool ok = g.h2d(g.din.p, in + lo, span) && g.h2d(g.a0.p, ioff.data(), 8ull * nz) && g.h2d(g.a1.p, ooff.data(), 8ull * nz) &&
-                  g.h2d(g.a2.p, ilen.data(), 4ull * nz) && g.h2d(g.a3.p, iav.data(), 4ull * nz) && g.h2d(g.a4.p, olim.data(), 4ull * nz) &&
-                  g.h2d(d_coff, coff.data(), 8ull * (ncz + ncr)) && g.h2d(d_clen, clen.data(), 4ull * (ncz + ncr));
-        if (!ok) return finish(NX_ERR_HIP);
-        if (nz) {
-            int32_t r = nx_fastlz_decompress_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.a3.as<uint32_t>(),
-                                                   g.dout.as<uint8_t>(), g.a1.as<uint64_t>(), g.a4.as<uint32_t>(), g.a5.as<int32_t>(),
-                                                   nz, g.s);
-            if (r != NX_OK) return finish(r);
-        }
-        if (ncz) {
-            int32_t r = nx_adler32_batch(g.dout.as<uint8_t>(), d_coff, d_clen, d_cval, ncz, g.s);
-            if (r != NX_OK) return finish(r);
-        }
-        if (ncr) {
-            int32_t r = nx_adler32_batch(g.din.as<uint8_t>(), d_coff + ncz, d_clen + ncz, d_cval + ncz, ncr, g.s);
-            if (r != NX_OK) return finish(r);
-        }
-        std::vector<uint32_t> cval(ncz + ncr);
-        ok = g.d2h(res.data(), g.a5.p, 4ull * nz) && g.d2h(hout.data(), g.dout.p, ocap) && g.d2h(cval.data(), d_cval, 4ull * (ncz + ncr)) &&
-             g.sync();
-        if (!ok) return finish(NX_ERR_HIP);
-        for (uint32_t k = 0; k < ncz; ++k) adl[cz_blk[k]] = cval[k];
-        for (uint32_t k = 0; k < ncr; ++k) adl[cr_blk[k]] = cval[ncz + k];
-    }
-    // apply in order
-    for (uint32_t i = 0; i < nb; ++i) {
-        Blk& b = blks[i];
-        const uint8_t* data;
-        uint32_t len;
-        if (b.comp) {
-            const int32_t r = res[b.job];
-            int32_t code;
-            std::string emsg;
-            if (nx::af::flz_block_error(r, b.olen, b.data < n ? in[b.data] : 0, &code, &emsg)) {
-                ml.err = emsg;
-                d->st.state = 3;
-                d->corrupted = true;
-                rd = b.data;
-                return finish(code);
-            }
-            data = hout.data() + ooff[b.job];
-            len = b.olen;
-        } else {
-            data = in + b.data;
-            len = b.clen;
-        }
-        if (b.has_cks && want_cks && adl[i] != b.cks) {  // FastLzFrameDecoder.java:171-180
-            ml.err = nx::af::flz_checksum_error(adl[i], b.cks);
-            d->st.state = 3;
-            d->corrupted = true;
-            rd = b.data;
-            return finish(NX_ERR_FASTLZ_CRC_MISMATCH);
-        }
-        if (len > 0) {
-            if (b.comp) {
-                ml.owned.emplace_back(data, data + len);
-                ml.msgs.push_back({ml.owned.back().data(), len});
-            } else {
-                ml.msgs.push_back({data, len});
-            }
-        }
-        rd = b.end;
-    }
-    if (werr.set) {
-        ml.err = werr.msg;
-        d->st.state = 3;
-        d->corrupted = true;
-        rd = werr.at;
-        return finish(werr.code);
-    }
-    rd = p;
-    d->st = ns;
-    return finish(NX_OK);
+    return alt_decode<FlzSync>(d, in, n, consumed, msgs, n_msgs, err_msg);
 }
 
 // ======================================================================= LZF encoder / decoder
@@ -680,92 +717,7 @@ extern "C" void nx_lzf_decoder_free(nx_lzf_decoder* d) { nx_alt_decoder_unref(d)
 
 extern "C" int32_t nx_lzf_decoder_decode(nx_lzf_decoder* d, const uint8_t* in, size_t n, size_t* consumed, const nx_msg** msgs,
                                          size_t* n_msgs, const char** err_msg) {
-    const nx::NoGrowScope no_grow;
-    if (!d || (!in && n)) return NX_ERR_INVALID_ARG;
-    MsgList& ml = d->ml;
-    ml.clear();
-    size_t rd = 0;
-    auto finish = [&](int32_t r) {
-        *consumed = rd;
-        *msgs = ml.msgs.data();
-        *n_msgs = ml.msgs.size();
-        if (err_msg) *err_msg = ml.err.empty() ? nullptr : ml.err.c_str();
-        return r;
-    };
-    if (d->corrupted || d->st.state == 3) {  // CORRUPTED (:229-231)
-        rd = n;
-        return finish(NX_OK);
-    }
-    struct Blk : nx::af::Blk {
-        int job = -1;
-    };
-    nx::af::LzfState ns = d->st;
-    std::vector<nx::af::Blk> walked;
-    nx::af::WalkErr werr;
-    const size_t p = nx::af::lzf_walk(in, n, ns, walked, werr);
-    std::vector<Blk> blks(walked.size());
-    for (size_t i = 0; i < walked.size(); ++i) static_cast<nx::af::Blk&>(blks[i]) = walked[i];
-    uint32_t nz = 0;
-    uint64_t ocap = 0;
-    std::vector<uint64_t> ooff;
-    for (auto& b : blks)
-        if (b.comp) {
-            b.job = (int)nz++;
-            ooff.push_back(ocap);
-            ocap += ((uint64_t)b.olen + 15) & ~15ull;
-        }
-    std::vector<int32_t> st(nz);
-    std::vector<uint8_t> hout(ocap);
-    Gpu& g = d->g;
-    if (nz) {
-        const size_t lo = blks.front().data;
-        const size_t span = p - lo;
-        std::vector<uint64_t> ioff(nz);
-        std::vector<uint32_t> ilen(nz), olen(nz);
-        for (auto& b : blks)
-            if (b.comp) {
-                ioff[b.job] = b.data - lo;
-                ilen[b.job] = b.clen;
-                olen[b.job] = b.olen;
-            }
-        if (!g.din.ensure(span + 1) || !g.dout.ensure(ocap + 16) || !g.a0.ensure(8ull * nz) || !g.a1.ensure(8ull * nz) ||
-            !g.a2.ensure(4ull * nz) || !g.a3.ensure(4ull * nz) || !g.a4.ensure(4ull * nz))
-            return finish(NX_ERR_HIP);
-        bool ok = g.h2d(g.din.p, in + lo, span) && g.h2d(g.a0.p, ioff.data(), 8ull * nz) && g.h2d(g.a1.p, ooff.data(), 8ull * nz) &&
-                  g.h2d(g.a2.p, ilen.data(), 4ull * nz) && g.h2d(g.a3.p, olen.data(), 4ull * nz);
-        if (!ok) return finish(NX_ERR_HIP);
-        int32_t r = nx_lzf_decode_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.dout.as<uint8_t>(),
-                                        g.a1.as<uint64_t>(), g.a3.as<uint32_t>(), g.a4.as<int32_t>(), nz, g.s);
-        if (r != NX_OK) return finish(r);
-        ok = g.d2h(st.data(), g.a4.p, 4ull * nz) && g.d2h(hout.data(), g.dout.p, ocap) && g.sync();
-        if (!ok) return finish(NX_ERR_HIP);
-    }
-    for (auto& b : blks) {
-        if (b.comp) {
-            if (st[b.job] != NX_OK) {
-                ml.err = nx::af::lzf_block_error();
-                d->st.state = 3;
-                d->corrupted = true;
-                rd = b.data;
-                return finish(st[b.job]);
-            }
-            ml.owned.emplace_back(hout.begin() + ooff[b.job], hout.begin() + ooff[b.job] + b.olen);
-            ml.msgs.push_back({ml.owned.back().data(), b.olen});
-        } else if (b.clen > 0) {
-            ml.msgs.push_back({in + b.data, b.clen});
-        }
-        rd = b.end;
-    }
-    if (werr.set) {
-        ml.err = werr.msg;
-        d->st.state = 3;
-        d->corrupted = true;
-        rd = werr.at;
-        return finish(werr.code);
-    }
-    rd = p;
-    d->st = ns;
-    return finish(NX_OK);
+    return alt_decode<LzfSync>(d, in, n, consumed, msgs, n_msgs, err_msg);
 }
 
 // ======================================================================= LZ4 frame encoder / decoder
@@ -775,8 +727,6 @@ extern "C" int32_t nx_lzf_decoder_decode(nx_lzf_decoder* d, const uint8_t* in, s
 // one batch: nx_lz4_frame_encode_batch / nx_lz4_decode_batch + nx_xxhash32_batch.
 using nx::af::kLz4Header;
 using nx::af::kLz4Magic;
-using nx::af::kLz4Seed;
-
 
 extern "C" nx_lz4_frame_encoder* nx_lz4_frame_encoder_new_ex(int32_t block_size, int32_t high_compressor, int32_t max_encode_size) {
     // compressionLevel(blockSize) :158-166; the device block encoder takes blocks below 32 MiB
@@ -967,134 +917,5 @@ extern "C" void nx_lz4_frame_decoder_free(nx_lz4_frame_decoder* d) { nx_alt_deco
 
 extern "C" int32_t nx_lz4_frame_decoder_decode(nx_lz4_frame_decoder* d, const uint8_t* in, size_t n, size_t* consumed,
                                                const nx_msg** msgs, size_t* n_msgs, const char** err_msg) {
-    const nx::NoGrowScope no_grow;
-    if (!d || (!in && n) || !consumed || !msgs || !n_msgs) return NX_ERR_INVALID_ARG;
-    MsgList& ml = d->ml;
-    ml.clear();
-    size_t rd = 0;
-    auto finish = [&](int32_t r) {
-        *consumed = rd;
-        *msgs = ml.msgs.data();
-        *n_msgs = ml.msgs.size();
-        if (err_msg) *err_msg = ml.err.empty() ? nullptr : ml.err.c_str();
-        return r;
-    };
-    if (d->corrupted || d->st.state >= 2) {  // FINISHED / CORRUPTED :250-254
-        rd = n;
-        return finish(NX_OK);
-    }
-    struct Blk : nx::af::Blk {
-        int job = -1;
-    };
-    nx::af::Lz4State ns = d->st;
-    std::vector<nx::af::Blk> walked;
-    nx::af::WalkErr werr;
-    const size_t p = nx::af::lz4_walk(in, n, ns, walked, werr);
-    std::vector<Blk> blks(walked.size());
-    for (size_t i = 0; i < walked.size(); ++i) static_cast<nx::af::Blk&>(blks[i]) = walked[i];
-    // GPU: decode the compressed blocks; hash every block's bytes when validating
-    uint32_t nz = 0;
-    uint64_t ocap = 0;
-    std::vector<uint64_t> ooff;
-    for (auto& b : blks)
-        if (b.type == 0x20u) {
-            b.job = (int)nz++;
-            ooff.push_back(ocap);
-            ocap += ((uint64_t)b.olen + 15) & ~15ull;
-        }
-    const uint32_t nb = (uint32_t)blks.size();
-    std::vector<int32_t> st(nz);
-    std::vector<uint32_t> hz(nz), hr(nb);
-    std::vector<uint8_t> hout(ocap);
-    Gpu& g = d->g;
-    if (nb) {
-        const size_t lo = blks.front().data, span = blks.back().end - lo;
-        std::vector<uint64_t> ioff(nz), roff(nb);
-        std::vector<uint32_t> ilen(nz), olen(nz), rlen(nb);
-        for (uint32_t k = 0; k < nb; ++k) {
-            const Blk& b = blks[k];
-            roff[k] = b.data - lo;
-            rlen[k] = b.type == 0x10u ? b.clen : 0u;
-            if (b.job >= 0) {
-                ioff[b.job] = b.data - lo;
-                ilen[b.job] = b.clen;
-                olen[b.job] = b.olen;
-            }
-        }
-        if (!g.din.ensure(span + 1) || !g.dout.ensure(ocap + 16) || !g.a0.ensure(8ull * nb) || !g.a1.ensure(8ull * nb) ||
-            !g.a2.ensure(4ull * nb) || !g.a3.ensure(4ull * nb) || !g.a4.ensure(4ull * nb) || !g.a5.ensure(4ull * nb) ||
-            !g.a6.ensure(4ull * nb))
-            return finish(NX_ERR_HIP);
-        bool ok = g.h2d(g.din.p, in + lo, span);
-        if (nz)
-            ok = ok && g.h2d(g.a0.p, ioff.data(), 8ull * nz) && g.h2d(g.a1.p, ooff.data(), 8ull * nz) &&
-                 g.h2d(g.a2.p, ilen.data(), 4ull * nz) && g.h2d(g.a3.p, olen.data(), 4ull * nz);
-        if (!ok) return finish(NX_ERR_HIP);
-        if (nz) {
-            int32_t r = nx_lz4_decode_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.dout.as<uint8_t>(),
-                                            g.a1.as<uint64_t>(), g.a3.as<uint32_t>(), g.a4.as<int32_t>(), nz, g.s);
-            if (r != NX_OK) return finish(r);
-            if (d->validate) {
-                r = nx_xxhash32_batch(g.dout.as<uint8_t>(), g.a1.as<uint64_t>(), g.a3.as<uint32_t>(), kLz4Seed, g.a5.as<uint32_t>(),
-                                      nz, g.s);
-                if (r != NX_OK) return finish(r);
-                ok = g.d2h(hz.data(), g.a5.p, 4ull * nz);
-            }
-            ok = ok && g.d2h(st.data(), g.a4.p, 4ull * nz) && g.d2h(hout.data(), g.dout.p, ocap);
-        }
-        if (ok && d->validate) {  // non-compressed blocks are hashed where they lie (retainedSlice :197-199)
-            ok = g.sync() && g.h2d(g.a0.p, roff.data(), 8ull * nb) && g.h2d(g.a2.p, rlen.data(), 4ull * nb);
-            if (ok) {
-                int32_t r = nx_xxhash32_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), kLz4Seed,
-                                              g.a6.as<uint32_t>(), nb, g.s);
-                if (r != NX_OK) return finish(r);
-                ok = g.d2h(hr.data(), g.a6.p, 4ull * nb);
-            }
-        }
-        ok = ok && g.sync();
-        if (!ok) return finish(NX_ERR_HIP);
-    }
-    for (uint32_t k = 0; k < nb; ++k) {
-        const Blk& b = blks[k];
-        const uint8_t* data;
-        if (b.job >= 0) {
-            if (st[b.job] != NX_OK) {  // LZ4Exception → DecompressionException (:240-241)
-                ml.err = nx::af::lz4_block_error();
-                d->st.state = 3;
-                d->corrupted = true;
-                rd = b.data;
-                return finish(st[b.job]);
-            }
-            data = hout.data() + ooff[b.job];
-        } else {
-            data = in + b.data;
-        }
-        if (d->validate) {  // CompressionUtil.checkChecksum (:226-228; Lz4XXHash32.getValue masks, :101)
-            const uint32_t got = (b.job >= 0 ? hz[b.job] : hr[k]) & 0x0FFFFFFFu;
-            if (got != b.cks) {
-                ml.err = nx::af::lz4_checksum_error(got, b.cks);
-                d->st.state = 3;
-                d->corrupted = true;
-                rd = b.end;
-                return finish(NX_ERR_LZ4_CHECKSUM_MISMATCH);
-            }
-        }
-        if (b.job >= 0) {
-            ml.owned.emplace_back(data, data + b.olen);
-            ml.msgs.push_back({ml.owned.back().data(), b.olen});
-        } else {
-            ml.msgs.push_back({in + b.data, b.olen});
-        }
-        rd = b.end;
-    }
-    if (werr.set) {
-        ml.err = werr.msg;
-        d->st.state = 3;
-        d->corrupted = true;
-        rd = werr.at;
-        return finish(werr.code);
-    }
-    rd = p;
-    d->st = ns;
-    return finish(NX_OK);
+    return alt_decode<Lz4Sync>(d, in, n, consumed, msgs, n_msgs, err_msg);
 }

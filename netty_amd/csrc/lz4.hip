@@ -16,7 +16,6 @@
 // (a stamp mismatch reads as the zeroed table), so the table is never cleared between blocks;
 // a large block zeroes its 4096 slots before and after itself, so none of its raw indices can pass
 // a later small block's stamp check.
-#include <algorithm>
 #include "nx_common.hpp"
 #include "workspace.hpp"
 
@@ -581,34 +580,17 @@ extern "C" int32_t nx_lz4hc_encode_batch(const uint8_t* in, const uint64_t* in_o
     NX_CLEAR_STALE_ERROR();
     if (n == 0) return NX_OK;
     if (!in || !in_off || !in_len || !out || !out_off || !out_len || !status) return NX_ERR_INVALID_ARG;
-    int dev = 0, cus = 256;
-    NX_HIP_CHECK(hipGetDevice(&dev));
-    NX_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     const hipStream_t st = (hipStream_t)stream;
-    const size_t per = nx::lz4::kHcTableWords * sizeof(uint32_t);
-    nx::WsLease lease(nx::WsKind::Lz4HcEnc, dev, st);
-    NX_HIP_CHECK(lease.acquire(nx::ws_want(nx::WsKind::Lz4HcEnc, n, cus)));
-    nx::SharedWs& W = lease.ws();
-    const nx::LaneGrid g = nx::ws_grid(nx::WsKind::Lz4HcEnc, n, cus, W.slots);
-    uint32_t* ws = static_cast<uint32_t*>(W.p);
-    const size_t per_launch = g.slots * (kHcMaxStamp - 1);
-    for (size_t base = 0; base < n; base += per_launch) {
-        const uint32_t m = (uint32_t)std::min<size_t>(per_launch, n - base);
-        const uint32_t iters = (uint32_t)((m + g.slots - 1) / g.slots);
-        if (W.stamp + iters >= kHcMaxStamp) {
-            NX_HIP_CHECK(hipMemsetAsync(ws, 0, W.slots * per, st));
-            W.stamp = 0;
-        }
+    const auto launch = [&](size_t base, uint32_t m, const nx::LaneGrid& g, void* tables, uint32_t stamp) {
+        uint32_t* ws = static_cast<uint32_t*>(tables);
         if (g.spread)
             hipLaunchKernelGGL(nx::lz4::k_lz4hc_encode<true>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base, in_len + base, out,
-                               out_off + base, out_len + base, status + base, m, ws, W.stamp);
+                               out_off + base, out_len + base, status + base, m, ws, stamp);
         else
             hipLaunchKernelGGL(nx::lz4::k_lz4hc_encode<false>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base, in_len + base,
-                               out, out_off + base, out_len + base, status + base, m, ws, W.stamp);
-        NX_HIP_CHECK(hipGetLastError());
-        W.stamp += iters;
-    }
-    return NX_OK;
+                               out, out_off + base, out_len + base, status + base, m, ws, stamp);
+    };
+    return nx::ws_lane_launch(nx::WsKind::Lz4HcEnc, kHcMaxStamp, n, st, launch);
 }
 
 // Replaces LZ4Compressor.compress as Lz4FrameEncoder.flushBufferedData calls it for one block
@@ -618,28 +600,15 @@ extern "C" int32_t nx_lz4_encode_batch(const uint8_t* in, const uint64_t* in_off
     NX_CLEAR_STALE_ERROR();
     if (n == 0) return NX_OK;
     if (!in || !in_off || !in_len || !out || !out_off || !out_len || !status) return NX_ERR_INVALID_ARG;
-    int dev = 0, cus = 256;
-    NX_HIP_CHECK(hipGetDevice(&dev));
-    NX_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     const hipStream_t st = (hipStream_t)stream;
-    const size_t per = nx::lz4::kTableSlots * sizeof(uint64_t);
-    nx::WsLease lease(nx::WsKind::Lz4Enc, dev, st);
-    NX_HIP_CHECK(lease.acquire(nx::ws_want(nx::WsKind::Lz4Enc, n, cus)));
-    nx::SharedWs& W = lease.ws();
-    const nx::LaneGrid g = nx::ws_grid(nx::WsKind::Lz4Enc, n, cus, W.slots);  // 16 waves per CU, as the Snappy encoder
-    uint64_t* ws = static_cast<uint64_t*>(W.p);
-    const uint32_t iters = (uint32_t)((n + g.slots - 1) / g.slots);
-    if (W.stamp + iters >= kMaxStamp) {
-        NX_HIP_CHECK(hipMemsetAsync(ws, 0, W.slots * per, st));
-        W.stamp = 0;
-    }
-    if (g.spread)
-        hipLaunchKernelGGL(nx::lz4::k_lz4_encode<true>, dim3(g.grid), dim3(g.block), 0, st, in, in_off, in_len, out, out_off, out_len,
-                           status, n, ws, W.stamp);
-    else
-        hipLaunchKernelGGL(nx::lz4::k_lz4_encode<false>, dim3(g.grid), dim3(g.block), 0, st, in, in_off, in_len, out, out_off, out_len,
-                           status, n, ws, W.stamp);
-    NX_HIP_CHECK(hipGetLastError());
-    W.stamp += iters;
-    return NX_OK;
+    const auto launch = [&](size_t base, uint32_t m, const nx::LaneGrid& g, void* tables, uint32_t stamp) {
+        uint64_t* ws = static_cast<uint64_t*>(tables);
+        if (g.spread)
+            hipLaunchKernelGGL(nx::lz4::k_lz4_encode<true>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base, in_len + base, out,
+                               out_off + base, out_len + base, status + base, m, ws, stamp);
+        else
+            hipLaunchKernelGGL(nx::lz4::k_lz4_encode<false>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base, in_len + base, out,
+                               out_off + base, out_len + base, status + base, m, ws, stamp);
+    };
+    return nx::ws_lane_launch(nx::WsKind::Lz4Enc, kMaxStamp, n, st, launch);
 }

@@ -110,6 +110,36 @@ class WsLease {
     size_t a_ = 0, b_ = 0;
 };
 
+// One batch of a lane-per-chunk encoder over kind k's tables.  A lane stamps its table entries with
+// stamp_base + its iteration, and stamps stay below max_stamp between two zeroings of the tables:
+// the batch runs in launches of at most slots * (max_stamp - 1) chunks, and the tables are zeroed
+// before a launch whose stamps would reach max_stamp.  launch(base, m, grid, tables, stamp_base)
+// enqueues the kernel for chunks [base, base + m).
+template <class Launch>
+int32_t ws_lane_launch(WsKind k, uint32_t max_stamp, uint32_t n, hipStream_t st, Launch&& launch) {
+    int dev = 0, cus = 256;
+    NX_HIP_CHECK(hipGetDevice(&dev));
+    NX_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    WsLease lease(k, dev, st);
+    NX_HIP_CHECK(lease.acquire(ws_want(k, n, cus)));
+    SharedWs& W = lease.ws();
+    const LaneGrid g = ws_grid(k, n, cus, W.slots);
+    const size_t table_bytes = (size_t)kWsSpec[(int)k].entry_bytes << kWsSpec[(int)k].lg;
+    const size_t per_launch = g.slots * (max_stamp - 1);
+    for (size_t base = 0; base < n; base += per_launch) {
+        const uint32_t m = (uint32_t)(n - base < per_launch ? n - base : per_launch);
+        const uint32_t iters = (uint32_t)((m + g.slots - 1) / g.slots);
+        if (W.stamp + iters >= max_stamp) {
+            NX_HIP_CHECK(hipMemsetAsync(W.p, 0, W.slots * table_bytes, st));
+            W.stamp = 0;
+        }
+        launch(base, m, g, W.p, W.stamp);
+        NX_HIP_CHECK(hipGetLastError());
+        W.stamp += iters;
+    }
+    return NX_OK;
+}
+
 // Owners: hold at creation (grows to `units` now), unhold at destruction (the last one frees).
 int32_t ws_hold(WsKind k, int dev, uint32_t units, hipStream_t st);
 void ws_unhold(WsKind k, int dev);
