@@ -74,6 +74,7 @@ int32_t nx_snappy_encode_batch(const uint8_t* in, const uint64_t* in_off, const 
 #define NX_WS_LZF_ENC 3
 #define NX_WS_DEC_RECORDS 4
 #define NX_WS_LZ4HC_ENC 5
+#define NX_WS_DEFLATE_ENC 6
 int32_t nx_snappy_encoder_reserve(uint32_t max_chunks, void* stream);
 /* The same with a bound (round 6): max_bytes caps the Snappy table workspace for good (0: no cap; 128
  * KiB per lane, whole blocks of 256 lanes above 16 384): batches of any size then run on those lanes
@@ -203,6 +204,32 @@ int32_t nx_fastlz_decompress_batch(const uint8_t* in, const uint64_t* in_off, co
 /* java.util.zip.Adler32 over each chunk (FastLzFrameEncoder.java:142-146 / Decoder :171-180). */
 int32_t nx_adler32_batch(const uint8_t* in, const uint64_t* off, const uint32_t* len,
                          uint32_t* out, uint32_t n, void* stream);
+
+/* java.util.zip.CRC32 over each chunk (JdkZlibEncoder.java:58,262-264: the gzip trailer's checksum;
+ * IEEE 802.3, reflected 0xEDB88320): the CRC32C kernel over a second table set. */
+int32_t nx_crc32_batch(const uint8_t* in, const uint64_t* off, const uint32_t* len,
+                       uint32_t* out, uint32_t n, void* stream);
+/* The checksum of A || B from the checksums of A and B and the length of B (host arithmetic, no
+ * device): how a handle folds its slices' checksums into the running value of JdkZlibEncoder's CRC32
+ * (:262-264) or of the Deflater's Adler32. */
+uint32_t nx_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+uint32_t nx_adler32_combine(uint32_t adler_a, uint32_t adler_b, uint64_t len_b);
+
+/* Replaces Deflater.deflate(..., SYNC_FLUSH) as JdkZlibEncoder.deflate calls it (JdkZlibEncoder.java:
+ * 256-276,342-357) for n independent chunks, in_len[i] <= 65536, into slots of
+ * nx_deflate_max_compressed_length(in_len[i]) bytes.  Chunk i's output is a byte-aligned run of
+ * RFC 1951 blocks with BFINAL = 0 that ends in the empty stored block (last bytes 00 00 FF FF), so
+ * the outputs of consecutive chunks concatenate into one stream; an empty chunk writes nothing.  A
+ * block takes the smallest of stored, fixed Huffman and dynamic Huffman by exact bit count.  level
+ * as java.util.zip.Deflater: 0 stored blocks only, 1..9 and -1 (default) the one matcher (greedy,
+ * one probe, within 32 KiB; sizes near zlib level 1), anything else NX_ERR_INVALID_ARG.  The bytes
+ * differ from the JDK's zlib and inflate to the same data.  status[i] = NX_OK, or
+ * NX_ERR_INVALID_ARG for a chunk over 65536 bytes.  128 KiB of NX_WS_DEFLATE_ENC workspace per chunk
+ * of a launch; larger batches run in sub-batches. */
+size_t nx_deflate_max_compressed_length(size_t n);
+int32_t nx_deflate_encode_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                                const uint64_t* out_off, uint32_t* out_len, int32_t* status, uint32_t n, int32_t level,
+                                void* stream);
 
 /* Replaces ChunkEncoder.appendEncodedChunk(...) as LZFEncoder.appendEncoded calls it per 65535-byte
  * chunk (LzfEncoder.java:218-221; compress-lzf 1.0.3 ChunkEncoder.tryCompress): writes a complete
@@ -396,6 +423,24 @@ size_t nx_lz4_frame_max_encoded_length(size_t n, int32_t block_size);
 int64_t nx_lz4_frame_encoder_encode(nx_lz4_frame_encoder* e, const uint8_t* in, size_t n, uint8_t* out, size_t out_cap);
 int64_t nx_lz4_frame_encoder_flush(nx_lz4_frame_encoder* e, uint8_t* out, size_t out_cap);
 int64_t nx_lz4_frame_encoder_close(nx_lz4_frame_encoder* e, uint8_t* out, size_t out_cap);
+
+/* JdkZlibEncoder(wrapper, compressionLevel)  JdkZlibEncoder.java:123-137,214-276,308-340.  wrapper is
+ * ZlibWrapper's ordinal (0 ZLIB, 1 GZIP, 2 NONE); NULL for 3 (ZLIB_OR_NONE, :128-132) and for a level
+ * outside -1..9 (:124-125).  The preset-dictionary constructors are not offered.
+ * _encode: an empty message writes nothing (:220-223); otherwise the header once (GZIP: the ten bytes
+ * of :59; ZLIB: the two bytes Deflater writes for the level; NONE: none), then the message deflated in
+ * 64 KiB slices of one batch, each closed by a sync flush, so the bytes written so far always
+ * inflate to the input so far.  out_cap >= nx_zlib_max_encoded_length(n).
+ * _close (finishEncode): the header if nothing was written, the final empty block 03 00, then the
+ * trailer (ZLIB: Adler32 big-endian; GZIP: CRC32 and total-in, little-endian; NONE: nothing);
+ * out_cap >= 20.  After it _encode copies its input through (:215-218, out_cap >= n) and a second
+ * _close returns 0.  Returns bytes written or a negative NX_ERR_*. */
+typedef struct nx_zlib_encoder nx_zlib_encoder;
+nx_zlib_encoder* nx_zlib_encoder_new(int32_t wrapper, int32_t level);
+void nx_zlib_encoder_free(nx_zlib_encoder* e);
+size_t nx_zlib_max_encoded_length(size_t n);
+int64_t nx_zlib_encoder_encode(nx_zlib_encoder* e, const uint8_t* in, size_t n, uint8_t* out, size_t out_cap);
+int64_t nx_zlib_encoder_close(nx_zlib_encoder* e, uint8_t* out, size_t out_cap);
 
 /* Lz4FrameDecoder(validateChecksums)  Lz4FrameDecoder.java:95-261.  Returns NX_OK or the
  * NX_ERR_LZ4_* code of the first failure (err_msg = the reference's message; the decoder is then

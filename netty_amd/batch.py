@@ -25,7 +25,7 @@ def _chk(rc, what):
 
 
 # Shared device workspaces (include/netty_amd.h NX_WS_*; csrc/workspace.hpp)
-WS_SNAPPY_ENC, WS_LZ4_ENC, WS_FASTLZ_ENC, WS_LZF_ENC, WS_DEC_RECORDS, WS_LZ4HC_ENC = range(6)
+WS_SNAPPY_ENC, WS_LZ4_ENC, WS_FASTLZ_ENC, WS_LZF_ENC, WS_DEC_RECORDS, WS_LZ4HC_ENC, WS_DEFLATE_ENC = range(7)
 
 
 def workspace_info(kind: int) -> tuple[int, int]:
@@ -181,6 +181,30 @@ def adler32(inp, off, length):
     out = torch.empty(n, dtype=torch.int32, device=inp.device)
     _chk(_lib.load().nx_adler32_batch(_ptr(inp), _ptr(off), _ptr(length), _ptr(out), n, _stream()), "nx_adler32_batch")
     return out
+
+
+def crc32(inp, off, length, out=None):
+    """java.util.zip.CRC32 per chunk (nx_crc32_batch)."""
+    n = length.numel()
+    out = torch.empty(n, dtype=torch.int32, device=inp.device) if out is None else out
+    _chk(_lib.load().nx_crc32_batch(_ptr(inp), _ptr(off), _ptr(length), _ptr(out), n, _stream()), "nx_crc32_batch")
+    return out
+
+
+def deflate_max_compressed_length(n: int) -> int:
+    return _lib.load().nx_deflate_max_compressed_length(n)
+
+
+def deflate_encode(inp, in_off, in_len, out, out_off, level: int = 6):
+    """Raw deflate with a sync flush per chunk of at most 65536 bytes (nx_deflate_encode_batch): slots
+    of deflate_max_compressed_length bytes; level as java.util.zip.Deflater.  Returns (out_len, status)."""
+    n = in_len.numel()
+    dev = inp.device
+    out_len = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    _chk(_lib.load().nx_deflate_encode_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_len),
+                                             _ptr(status), n, int(level), _stream()), "nx_deflate_encode_batch")
+    return out_len, status
 
 
 def lzf_encode(inp, in_off, in_len, out, out_off):

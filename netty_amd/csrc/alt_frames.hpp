@@ -335,6 +335,17 @@ struct nx_lz4_frame_encoder {
     std::vector<uint8_t> buf;  // the block buffer (Lz4FrameEncoder.java:221-226)
 };
 
+struct nx_zlib_encoder {
+    nx::h::Gpu g;
+    int32_t wrapper = 0;        // ZlibWrapper ordinal: 0 ZLIB, 1 GZIP, 2 NONE
+    int32_t level = 6;
+    bool write_header = true;   // writeHeader (JdkZlibEncoder.java:60)
+    bool finished = false;
+    uint32_t crc = 0;           // GZIP: CRC32 of everything encoded (:58,262-264)
+    uint32_t adler = 1;         // ZLIB: the Deflater's Adler32
+    uint64_t total_in = 0;      // deflater.getTotalIn() (:332)
+};
+
 // allocateBuffer's maxEncodeSize check (handlers.cpp; the batcher's submit runs it too)
 int32_t nx_lz4_frame_encoder_check_size(nx_lz4_frame_encoder* e, uint64_t remaining, int32_t* target_out = nullptr);
 int32_t nx_lz4_frame_encoder_check_finished(nx_lz4_frame_encoder* e, size_t n, int32_t target);

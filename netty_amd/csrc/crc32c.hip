@@ -1,4 +1,5 @@
-// crc32c.hip — CRC32C tables + the batched masked-CRC kernel.
+// crc32c.hip — CRC tables + the batched CRC kernel: masked CRC32C (Snappy) and plain CRC32 (gzip), the
+// same kernel over a table set per polynomial.
 //
 // Replaces Crc32c.update/getValue (Crc32c.java:97-124) + Snappy.maskChecksum (Snappy.java:720-722)
 // as called by Snappy.calculateChecksum (Snappy.java:668-676), one wave per chunk.
@@ -25,15 +26,15 @@
 namespace nx {
 
 static std::mutex g_crc_mu;
-static CrcTables* g_crc_dev[64] = {nullptr};
+static CrcTables* g_crc_dev[2][64] = {{nullptr}};  // [0] Castagnoli, [1] IEEE
 static uint32_t h_T0[256];
 
-static void build_tables(CrcTables* t) {
+static void build_tables(CrcTables* t, uint32_t poly = kCrcPoly) {
     for (uint32_t i = 0; i < 256; ++i) {
         uint32_t c = i;
-        for (int k = 0; k < 8; ++k) c = (c & 1) ? (c >> 1) ^ kCrcPoly : (c >> 1);
+        for (int k = 0; k < 8; ++k) c = (c & 1) ? (c >> 1) ^ poly : (c >> 1);
         t->T8[0][i] = c;
-        h_T0[i] = c;
+        if (poly == kCrcPoly) h_T0[i] = c;
     }
     for (int k = 1; k < 8; ++k)
         for (uint32_t i = 0; i < 256; ++i) {
@@ -41,20 +42,20 @@ static void build_tables(CrcTables* t) {
             t->T8[k][i] = (c >> 8) ^ t->T8[0][c & 0xFF];
         }
     for (int j = 0; j < 10; ++j) {
-        uint32_t K = gf_x8n(16ull << j);
+        uint32_t K = gf_x8n(16ull << j, poly);
         for (int k = 0; k < 4; ++k)
-            for (uint32_t b = 0; b < 256; ++b) t->SH[j][k][b] = gf_multmodp(K, b << (8 * k));
+            for (uint32_t b = 0; b < 256; ++b) t->SH[j][k][b] = gf_multmodp(K, b << (8 * k), poly);
     }
     for (int j = 0; j < 7; ++j) {
-        uint32_t K = gf_x8n(8ull << j);
+        uint32_t K = gf_x8n(8ull << j, poly);
         for (int k = 0; k < 8; ++k)
-            for (uint32_t v = 0; v < 16; ++v) t->NS[j][k][v] = gf_multmodp(K, v << (4 * k));
+            for (uint32_t v = 0; v < 16; ++v) t->NS[j][k][v] = gf_multmodp(K, v << (4 * k), poly);
     }
     // x^-8: solve gf_multmodp(x^8, y) = x^0 (GF(2) Gaussian elimination on the 32 columns)
     {
-        const uint32_t a = gf_x8n(1), one = 0x80000000u;
+        const uint32_t a = gf_x8n(1, poly), one = 0x80000000u;
         uint32_t col[32];
-        for (int i = 0; i < 32; ++i) col[i] = gf_multmodp(a, 1u << i);
+        for (int i = 0; i < 32; ++i) col[i] = gf_multmodp(a, 1u << i, poly);
         // rows r: bit r of each column; augment with bit r of `one`
         uint64_t row[32];
         for (int r = 0; r < 32; ++r) {
@@ -77,33 +78,38 @@ static void build_tables(CrcTables* t) {
             for (int c = 0; c < 32; ++c)
                 if ((row[r] >> c) & 1u) { inv |= (uint32_t)((row[r] >> 32) & 1u) << c; break; }
         t->XI[0] = one;
-        for (int k = 1; k < 16; ++k) t->XI[k] = gf_multmodp(t->XI[k - 1], inv);
+        for (int k = 1; k < 16; ++k) t->XI[k] = gf_multmodp(t->XI[k - 1], inv, poly);
     }
 }
 
-int crc_tables_init() {
+static int tables_init(int which) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return NX_ERR_HIP;
     std::lock_guard<std::mutex> lk(g_crc_mu);
-    if (g_crc_dev[dev]) return NX_OK;
+    if (g_crc_dev[which][dev]) return NX_OK;
     std::vector<CrcTables> t(1);
-    build_tables(t.data());
+    build_tables(t.data(), which ? kCrc32Poly : kCrcPoly);
     CrcTables* d = nullptr;
     if (hipMalloc(&d, sizeof(CrcTables)) != hipSuccess) return NX_ERR_HIP;
     if (hipMemcpy(d, t.data(), sizeof(CrcTables), hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipFree(d);
         return NX_ERR_HIP;
     }
-    g_crc_dev[dev] = d;
+    g_crc_dev[which][dev] = d;
     return NX_OK;
 }
 
-const CrcTables* crc_tables_dev() {
+static const CrcTables* tables_dev(int which) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
     std::lock_guard<std::mutex> lk(g_crc_mu);
-    return g_crc_dev[dev];
+    return g_crc_dev[which][dev];
 }
+
+int crc_tables_init() { return tables_init(0); }
+const CrcTables* crc_tables_dev() { return tables_dev(0); }
+int crc32_tables_init() { return tables_init(1); }
+const CrcTables* crc32_tables_dev() { return tables_dev(1); }
 
 uint32_t host_crc32c(const uint8_t* p, size_t n) {
     static std::once_flag once;
@@ -179,10 +185,10 @@ __device__ __forceinline__ uint32_t raw128(const uint32_t* __restrict__ T, const
     return c;
 }
 
-// Masked CRC32C of chunk p[0..L) by one wave (result valid in every lane).  T = T8 (8 KiB), SH =
-// SH[3..9] (shift by 128 B .. 8 KiB), both in LDS; XI from global memory.
+// CRC of chunk p[0..L) by one wave under the polynomial the tables were built for (result valid in
+// every lane).  T = T8 (8 KiB), SH = SH[3..9] (shift by 128 B .. 8 KiB), both in LDS; XI from global memory.
 __device__ uint32_t wave_crc32c(const uint32_t* __restrict__ T, const uint32_t* __restrict__ SH, const uint32_t* __restrict__ XI,
-                                const uint8_t* __restrict__ p, uint32_t L, int lane) {
+                                const uint8_t* __restrict__ p, uint32_t L, int lane, uint32_t poly) {
     if (L < 4) {  // the init fold needs four bytes: byte-serial (every lane computes the same)
         uint32_t c = 0xFFFFFFFFu;
         for (uint32_t i = 0; i < L; ++i) c = (c >> 8) ^ T[(c ^ p[i]) & 0xFF];
@@ -212,12 +218,13 @@ __device__ uint32_t wave_crc32c(const uint32_t* __restrict__ T, const uint32_t* 
         acc = shift_tab(SH + j * 1024, is_lo ? acc : other) ^ (is_lo ? other : acc);
     }
     // raw(V) = raw(M') * x^(8k);  crc = ~raw(M')
-    return ~(k ? gf_multmodp(XI[k], acc) : acc);
+    return ~(k ? gf_multmodp(XI[k], acc, poly) : acc);
 }
 
+// poly: the polynomial of `tabs`; masked: Snappy's maskChecksum over the CRC32C, else the plain value
 __global__ void __launch_bounds__(256) k_crc32c_masked(const uint8_t* __restrict__ in, const uint64_t* __restrict__ off,
                                                        const uint32_t* __restrict__ len, uint32_t* __restrict__ out,
-                                                       uint32_t n, const CrcTables* __restrict__ tabs) {
+                                                       uint32_t n, const CrcTables* __restrict__ tabs, uint32_t poly, uint32_t masked) {
     __shared__ uint32_t sT[8 * 256];
     __shared__ uint32_t sSH[7 * 1024];
     for (int i = threadIdx.x; i < 8 * 256; i += blockDim.x) sT[i] = (&tabs->T8[0][0])[i];
@@ -226,8 +233,8 @@ __global__ void __launch_bounds__(256) k_crc32c_masked(const uint8_t* __restrict
     const int lane = threadIdx.x & 63;
     const uint32_t waves_per_block = blockDim.x / 64;
     for (uint32_t c = blockIdx.x * waves_per_block + (threadIdx.x >> 6); c < n; c += gridDim.x * waves_per_block) {
-        const uint32_t crc = wave_crc32c(sT, sSH, tabs->XI, in + off[c], len[c], lane);
-        if (lane == 0) out[c] = mask_checksum(crc);
+        const uint32_t crc = wave_crc32c(sT, sSH, tabs->XI, in + off[c], len[c], lane, poly);
+        if (lane == 0) out[c] = masked ? mask_checksum(crc) : crc;
     }
 }
 
@@ -244,7 +251,39 @@ extern "C" int32_t nx_crc32c_masked_batch(const uint8_t* in, const uint64_t* off
     unsigned grid = n / 4 + 1;
     if (grid > 2048) grid = 2048;
     hipLaunchKernelGGL(k_crc32c_masked, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, off, len, masked_out, n,
-                       crc_tables_dev());
+                       crc_tables_dev(), kCrcPoly, 1u);
     NX_HIP_CHECK(hipGetLastError());
     return NX_OK;
+}
+
+// java.util.zip.CRC32 over each chunk (JdkZlibEncoder.java:262-264, the gzip trailer's checksum): the
+// kernel above over the IEEE table set.
+extern "C" int32_t nx_crc32_batch(const uint8_t* in, const uint64_t* off, const uint32_t* len, uint32_t* out, uint32_t n,
+                                  void* stream) {
+    NX_CLEAR_STALE_ERROR();
+    if (n == 0) return NX_OK;
+    if (!in || !off || !len || !out) return NX_ERR_INVALID_ARG;
+    if (crc32_tables_init() != NX_OK) return NX_ERR_HIP;
+    unsigned grid = n / 4 + 1;
+    if (grid > 2048) grid = 2048;
+    hipLaunchKernelGGL(k_crc32c_masked, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, off, len, out, n, crc32_tables_dev(),
+                       kCrc32Poly, 0u);
+    NX_HIP_CHECK(hipGetLastError());
+    return NX_OK;
+}
+
+// CRC32 of A || B from crc32(A), crc32(B) and |B|: crc(A) advanced over |B| zero bytes, i.e. times
+// x^(8|B|) modulo the polynomial (the initial and final inversions cancel).  Host arithmetic only.
+extern "C" uint32_t nx_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
+    return gf_multmodp(gf_x8n(len_b, kCrc32Poly), crc_a, kCrc32Poly) ^ crc_b;
+}
+
+// Adler32 of A || B from adler32(A), adler32(B) and |B|: with s1 = 1 + sum of bytes and s2 = sum of
+// the running s1 (both mod 65521), s1' = s1a + s1b - 1 and s2' = s2a + s2b + |B| (s1a - 1).
+extern "C" uint32_t nx_adler32_combine(uint32_t adler_a, uint32_t adler_b, uint64_t len_b) {
+    constexpr uint64_t M = 65521;
+    const uint64_t a1 = adler_a & 0xFFFFu, a2 = adler_a >> 16, b1 = adler_b & 0xFFFFu, b2 = adler_b >> 16;
+    const uint64_t s1 = (a1 + b1 + M - 1) % M;
+    const uint64_t s2 = (a2 + b2 + (len_b % M) * ((a1 + M - 1) % M)) % M;
+    return (uint32_t)((s2 << 16) | s1);
 }

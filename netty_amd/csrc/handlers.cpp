@@ -919,3 +919,130 @@ extern "C" int32_t nx_lz4_frame_decoder_decode(nx_lz4_frame_decoder* d, const ui
                                                const nx_msg** msgs, size_t* n_msgs, const char** err_msg) {
     return alt_decode<Lz4Sync>(d, in, n, consumed, msgs, n_msgs, err_msg);
 }
+
+// ======================================================================= JdkZlibEncoder
+// JdkZlibEncoder.java:123-137 (constructor), :214-276 (encode), :308-340 (finishEncode).  Every
+// encode() ends in a sync flush, so a message is cut into 64 KiB slices that are deflated as
+// independent chunks of one launch pair (deflate.hip) and concatenated; the slices' checksums come
+// from the same launch sequence and are folded into the running value on the host.
+
+namespace {
+constexpr size_t kZlibSlice = 65536;
+constexpr uint8_t kGzipHeader[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0};  // gzipHeader (:59)
+
+// the two bytes java.util.zip.Deflater (zlib's deflateInit) writes for a level: CMF 0x78, FLG with
+// the level class in its top two bits and the check bits that make the pair a multiple of 31
+size_t zlib_write_header(const nx_zlib_encoder* e, uint8_t* out) {
+    if (e->wrapper == 1) {
+        memcpy(out, kGzipHeader, 10);
+        return 10;
+    }
+    if (e->wrapper == 0) {
+        const int32_t l = e->level;
+        out[0] = 0x78;
+        out[1] = l == 0 || l == 1 ? 0x01 : l >= 2 && l <= 5 ? 0x5E : l == 6 || l == -1 ? 0x9C : 0xDA;
+        return 2;
+    }
+    return 0;
+}
+}  // namespace
+
+extern "C" nx_zlib_encoder* nx_zlib_encoder_new(int32_t wrapper, int32_t level) {
+    if (level < -1 || level > 9) return nullptr;     // checkInRange (:124-125)
+    if (wrapper < 0 || wrapper > 2) return nullptr;  // ZLIB_OR_NONE is not allowed for compression (:128-132)
+    auto* e = new nx_zlib_encoder();
+    if (!e->g.hold(nx::WsKind::DeflateEnc)) {
+        delete e;
+        return nullptr;
+    }
+    e->wrapper = wrapper;
+    e->level = level;
+    return e;
+}
+extern "C" void nx_zlib_encoder_free(nx_zlib_encoder* e) { delete e; }
+extern "C" size_t nx_zlib_max_encoded_length(size_t n) { return 20 + n + (n / kZlibSlice + 1) * 15; }
+
+extern "C" int64_t nx_zlib_encoder_encode(nx_zlib_encoder* e, const uint8_t* in, size_t n, uint8_t* out, size_t out_cap) {
+    const nx::NoGrowScope no_grow;
+    if (!e || (n && (!in || !out))) return NX_ERR_INVALID_ARG;
+    if (e->finished) {  // out.writeBytes(uncompressed) (:215-218)
+        if (out_cap < n) return NX_ERR_INVALID_ARG;
+        nx::copy_bytes(out, in, n);
+        return (int64_t)n;
+    }
+    if (n == 0) return 0;  // :220-223
+    if (out_cap < nx_zlib_max_encoded_length(n)) return NX_ERR_INVALID_ARG;
+    const uint32_t ns = (uint32_t)((n + kZlibSlice - 1) / kZlibSlice);
+    std::vector<uint64_t> ioff(ns), ooff(ns);
+    std::vector<uint32_t> ilen(ns);
+    uint64_t oc = 0;
+    for (uint32_t i = 0; i < ns; ++i) {
+        ioff[i] = (uint64_t)i * kZlibSlice;
+        ilen[i] = (uint32_t)(n - ioff[i] < kZlibSlice ? n - ioff[i] : kZlibSlice);
+        ooff[i] = oc;
+        oc += (nx_deflate_max_compressed_length(ilen[i]) + 127) & ~(size_t)127;
+    }
+    Gpu& g = e->g;
+    if (!g.din.ensure(n) || !g.dout.ensure(oc) || !g.a0.ensure(8ull * ns) || !g.a1.ensure(8ull * ns) || !g.a2.ensure(4ull * ns) ||
+        !g.a3.ensure(4ull * ns) || !g.a4.ensure(4ull * ns) || !g.a5.ensure(4ull * ns))
+        return NX_ERR_HIP;
+    bool ok = g.h2d(g.din.p, in, n) && g.h2d(g.a0.p, ioff.data(), 8ull * ns) && g.h2d(g.a1.p, ooff.data(), 8ull * ns) &&
+              g.h2d(g.a2.p, ilen.data(), 4ull * ns);
+    if (!ok) return NX_ERR_HIP;
+    int32_t r = NX_OK;
+    if (e->wrapper == 1)
+        r = nx_crc32_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.a5.as<uint32_t>(), ns, g.s);
+    else if (e->wrapper == 0)
+        r = nx_adler32_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.a5.as<uint32_t>(), ns, g.s);
+    if (r != NX_OK) return r;
+    r = nx_deflate_encode_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.dout.as<uint8_t>(),
+                                g.a1.as<uint64_t>(), g.a3.as<uint32_t>(), g.a4.as<int32_t>(), ns, e->level, g.s);
+    if (r != NX_OK) return r;
+    std::vector<uint32_t> olen(ns), sum(ns, 0u);
+    std::vector<int32_t> st(ns);
+    ok = g.d2h(olen.data(), g.a3.p, 4ull * ns) && g.d2h(st.data(), g.a4.p, 4ull * ns) &&
+         (e->wrapper == 2 || g.d2h(sum.data(), g.a5.p, 4ull * ns)) && g.sync();
+    if (!ok) return NX_ERR_HIP;
+    for (uint32_t i = 0; i < ns; ++i)
+        if (st[i] != NX_OK) return st[i];
+    size_t op = 0;
+    if (e->write_header) {
+        e->write_header = false;
+        op = zlib_write_header(e, out);
+    }
+    for (uint32_t i = 0; i < ns && ok; ++i) {  // each slice's bytes only, concatenated in place
+        ok = g.d2h(out + op, g.dout.as<uint8_t>() + ooff[i], olen[i]);
+        op += olen[i];
+    }
+    if (!g.sync() || !ok) return NX_ERR_HIP;
+    for (uint32_t i = 0; i < ns; ++i) {
+        if (e->wrapper == 1) e->crc = nx_crc32_combine(e->crc, sum[i], ilen[i]);
+        else if (e->wrapper == 0) e->adler = nx_adler32_combine(e->adler, sum[i], ilen[i]);
+    }
+    e->total_in += n;
+    return (int64_t)op;
+}
+
+// finishEncode (:308-340): the header if nothing was written, the final block (an empty fixed-Huffman
+// block, what deflater.finish() adds after a sync flush), then the wrapper's trailer.
+extern "C" int64_t nx_zlib_encoder_close(nx_zlib_encoder* e, uint8_t* out, size_t out_cap) {
+    if (!e) return NX_ERR_INVALID_ARG;
+    if (e->finished) return 0;  // :309-312
+    if (!out || out_cap < 20) return NX_ERR_INVALID_ARG;
+    e->finished = true;
+    size_t op = 0;
+    if (e->write_header) {
+        e->write_header = false;
+        op = zlib_write_header(e, out);
+    }
+    out[op++] = 0x03;
+    out[op++] = 0x00;
+    if (e->wrapper == 0) {  // the zlib trailer: Adler32, most significant byte first
+        for (int k = 3; k >= 0; --k) out[op++] = (uint8_t)(e->adler >> (8 * k));
+    } else if (e->wrapper == 1) {  // writeIntLE(crc), writeIntLE(totalIn) (:331-335)
+        const uint32_t isize = (uint32_t)e->total_in;
+        for (int k = 0; k < 4; ++k) out[op++] = (uint8_t)(e->crc >> (8 * k));
+        for (int k = 0; k < 4; ++k) out[op++] = (uint8_t)(isize >> (8 * k));
+    }
+    return (int64_t)op;
+}

@@ -30,6 +30,8 @@ namespace nx {
 
 // CRC32C (Castagnoli, reflected poly 0x82F63B78) — Crc32c.java:27-124.
 constexpr uint32_t kCrcPoly = 0x82F63B78u;
+// CRC32 (IEEE 802.3, reflected poly 0xEDB88320) — java.util.zip.CRC32, the gzip trailer.
+constexpr uint32_t kCrc32Poly = 0xEDB88320u;
 
 // Device-side CRC tables (filled once by crc_tables_init() on the host):
 //   T8[k][b]   : slicing-by-8 tables, T8[0] = byte table of Crc32c.java:27-92
@@ -46,6 +48,9 @@ struct CrcTables {
 // pointer as an argument: no cross-TU device symbols, so no -fgpu-rdc).
 int crc_tables_init();                 // host: build + upload (idempotent). Returns NX_OK / NX_ERR_HIP.
 const CrcTables* crc_tables_dev();     // device pointer for the current device
+// The same table set for the IEEE polynomial (nx_crc32_batch), built on its first use.
+int crc32_tables_init();
+const CrcTables* crc32_tables_dev();
 // host helpers (also used by the host handler layer)
 uint32_t host_crc32c(const uint8_t* p, size_t n);
 uint32_t host_mask(uint32_t c);
@@ -53,23 +58,23 @@ uint32_t host_mask(uint32_t c);
 __host__ __device__ inline uint32_t mask_checksum(uint32_t c) { return ((c >> 15) | (c << 17)) + 0xa282ead8u; }
 
 // GF(2) multiply modulo P in CRC (reflected) representation (zlib multmodp).
-__host__ __device__ inline uint32_t gf_multmodp(uint32_t a, uint32_t b) {
+__host__ __device__ inline uint32_t gf_multmodp(uint32_t a, uint32_t b, uint32_t poly = kCrcPoly) {
     uint32_t p = 0;
     for (int i = 0; i < 32; ++i) {
         p ^= (a & 0x80000000u) ? b : 0u;
         a <<= 1;
-        b = (b & 1u) ? ((b >> 1) ^ kCrcPoly) : (b >> 1);
+        b = (b & 1u) ? ((b >> 1) ^ poly) : (b >> 1);
     }
     return p;
 }
 
 // x^(8n) mod P (reflected), by square-and-multiply.
-__host__ __device__ inline uint32_t gf_x8n(uint64_t n) {
+__host__ __device__ inline uint32_t gf_x8n(uint64_t n, uint32_t poly = kCrcPoly) {
     uint32_t result = 0x80000000u;  // x^0
     uint32_t sq = 0x00800000u;      // x^8
     while (n) {
-        if (n & 1) result = gf_multmodp(sq, result);
-        sq = gf_multmodp(sq, sq);
+        if (n & 1) result = gf_multmodp(sq, result, poly);
+        sq = gf_multmodp(sq, sq, poly);
         n >>= 1;
     }
     return result;

@@ -21,6 +21,7 @@ native host layer exactly as the Java decode() does.
 from __future__ import annotations
 
 import ctypes as C
+import enum
 
 from . import _lib
 
@@ -291,6 +292,52 @@ class Lz4FrameEncoder(_Encoder):
     def finish_encode(self) -> bytes:
         out, cap = self._out(self.block_size)
         return self._ret(_lib.load().nx_lz4_frame_encoder_close(self._h, out, cap), out)
+
+
+class ZlibWrapper(enum.IntEnum):
+    """ZlibWrapper.java:21-40 (the ordinals the C-ABI takes)"""
+    ZLIB = 0
+    GZIP = 1
+    NONE = 2
+    ZLIB_OR_NONE = 3
+
+
+class JdkZlibEncoder(_Encoder):
+    """JdkZlibEncoder.java:123-137,214-276,308-340 over the GPU deflate encoder.  encode() writes the
+    header once and the message as sync-flushed deflate blocks (64 KiB slices of one batch), so the
+    bytes written so far always inflate to the input so far; finish_encode() writes the final block
+    and the wrapper's trailer, after which encode() passes its input through (:215-218).  Levels 1-9
+    and -1 run one matcher (sizes near zlib level 1), level 0 writes stored blocks; the bytes differ
+    from the JDK's and inflate to the same data.  ZLIB_OR_NONE and levels outside -1..9 are refused
+    as the reference's constructor refuses them (:124-132)."""
+
+    _free = "nx_zlib_encoder_free"
+
+    def __init__(self, wrapper: ZlibWrapper = ZlibWrapper.ZLIB, compression_level: int = 6):
+        wrapper = ZlibWrapper(wrapper)
+        if not -1 <= compression_level <= 9:
+            raise ValueError(f"compressionLevel: {compression_level} (expected: -1-9)")
+        if wrapper == ZlibWrapper.ZLIB_OR_NONE:
+            raise ValueError(f"wrapper '{wrapper.name}' is not allowed for compression.")
+        self.wrapper = wrapper
+        self.compression_level = int(compression_level)
+        self._h = _new(_lib.load().nx_zlib_encoder_new(int(wrapper), self.compression_level), "JdkZlibEncoder")
+
+    @staticmethod
+    def _ret(r, out) -> bytes:
+        if r < 0:
+            raise CompressionException(_lib.status_string(r))
+        return bytes(out[:r])
+
+    def encode(self, data: bytes) -> bytes:
+        L = _lib.load()
+        cap = L.nx_zlib_max_encoded_length(len(data))
+        out = (C.c_uint8 * cap)()
+        return self._ret(L.nx_zlib_encoder_encode(self._h, data, len(data), out, cap), out)
+
+    def finish_encode(self) -> bytes:
+        out = (C.c_uint8 * 32)()
+        return self._ret(_lib.load().nx_zlib_encoder_close(self._h, out, 32), out)
 
 
 class Lz4FrameDecoder(_Decoder):
