@@ -42,6 +42,7 @@
 #include <algorithm>
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -106,8 +107,8 @@ struct DecRes {  // per action, written by k_dec_finish
 #define NX_PCIE_BLOCKS 64
 #endif
 constexpr uint32_t kPcieBlocks = NX_PCIE_BLOCKS;
-constexpr uint64_t kDmaOutMin = 64ull << 20;  // launch_inner: result arenas at least this large may go by DMA
-constexpr uint64_t kGatherStageMax = 8ull << 20;  // launch_inner: staging arenas up to this size move by k_gather_host
+constexpr uint64_t kDmaOutMin = 64ull << 20;  // place(): result arenas at least this large may go by DMA
+constexpr uint64_t kGatherStageMax = 8ull << 20;  // transfer_in(): staging arenas up to this size move by k_gather_host
 constexpr uint64_t kGatherPiece = 64ull << 10;    // ... in ops of this many bytes
 inline dim3 pcie_grid(uint32_t jobs) { return dim3(std::min((jobs + 3u) / 4u, kPcieBlocks)); }
 __device__ void wave_copy(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, uint32_t n, int lane) {
@@ -289,9 +290,11 @@ struct AltPiece {
     uint32_t olen;  // decoder: decoded bytes
     uint32_t kind;
     uint32_t res;   // index into the codec's result arrays
-    uint32_t aux;   // AK_FLZ_ENC: bit 0 = with Adler32; AK_LZ4_END: compression level
-    uint32_t pad;
+    uint32_t aux;   // AK_FLZ_ENC: bit 0 = with Adler32; AK_LZ4_END: compression level; decoder pieces with a
+                    // checksum: 1 + its index in AltArrays::dcks (assigned at flush)
+    uint32_t cks;   // decoder pieces, host only: the checksum to compute (CK_NONE / CK_ADLER32 / CK_XXH32)
 };
+enum : uint32_t { CK_NONE = 0, CK_ADLER32 = 1, CK_XXH32 = 2 };
 struct AltJobD {
     uint64_t out_off;  // in the mapped output arena
     uint32_t p0, np;   // pieces
@@ -481,10 +484,15 @@ struct Pinned {  // hipHostMalloc'd, mapped into the device address space; grows
     }
 };
 
+inline uint64_t align16(uint64_t x) { return (x + 15) & ~15ull; }
+
+enum class JobKind { SnappyEnc, SnappyDec, AltEnc, AltDec };
+enum class Codec { FastLz, Lzf, Lz4 };  // of an alt-codec job
+
 struct Job {
     uint64_t ticket = 0;
-    int kind = 0;  // 0 Snappy encode, 1 Snappy decode, 2 alt-codec encode, 3 alt-codec decode
-    nx_snappy_frame_decoder* dec = nullptr;
+    JobKind kind = JobKind::SnappyEnc;
+    nx_snappy_frame_decoder* dec = nullptr;  // Snappy decoder jobs hold a reference (handles.hpp)
     uint32_t index = 0;  // EncJob / DecJob index in its batch
     std::vector<SnappyAction> acts;  // decode: the parsed actions (host copy, stream order)
     std::string parse_err;           // decode: the header-level error after them, if any
@@ -500,7 +508,7 @@ struct Job {
     std::vector<std::vector<uint8_t>> owned;  // messages delivered before a re-walk moved the job (a moved
                                               // vector keeps its buffer; a deque would allocate per Job)
     // alt-codec jobs (FastLZ / LZF / LZ4)
-    int codec = -1;                     // 0 FastLZ, 1 LZF, 2 LZ4
+    Codec codec = Codec::FastLz;
     nx_alt_decoder_base* adec = nullptr;  // decoder jobs hold a reference (alt_frames.hpp)
     bool validate = false;
     std::vector<nx::af::Blk> ablk;      // decoder: the walked blocks, in order
@@ -509,11 +517,29 @@ struct Job {
     Job() = default;
     Job(const Job&) = delete;
     Job& operator=(const Job&) = delete;
-    ~Job() {  // a decoder job holds a reference to its handle (handles.hpp)
+    // A decoder job takes its reference as it learns its handle (the submitting caller's own reference
+    // keeps the handle alive meanwhile) and drops it with the job, queued or not.
+    void bind(nx_snappy_frame_decoder* d) {
+        dec = d;
+        d->refs.fetch_add(1);
+    }
+    void bind(nx_alt_decoder_base* d) {
+        adec = d;
+        d->refs.fetch_add(1);
+    }
+    ~Job() {
         nx_decoder_unref(dec);
         nx_alt_decoder_unref(adec);
     }
 };
+using JobPtr = std::unique_ptr<Job>;  // a job not yet handed to its batch (register_job)
+
+struct AltEntry {  // one block for a codec kernel; the flush lays each list out as the kernel's arrays
+    uint64_t off, slot;
+    uint32_t len, aux;  // aux: FastLZ encode level / decode in_avail; LZ4 encode level | highCompressor << 8; decode olen
+    int32_t lim;        // FastLZ encode: readU16 limit; decode: originalLength
+};
+enum AltIx { FLZ_E, LZF_E, LZ4_E, FLZ_D, LZF_D, LZ4_D, kAltLists };  // encode / decode x codec, in Codec's order
 
 struct Batch {
     Pinned staging;  // chunk payloads, then the device arrays (one H2D copy at flush)
@@ -533,40 +559,24 @@ struct Batch {
     std::vector<DecAct> dact;
     std::vector<uint8_t> dact_direct;  // payload lies in the direct region (registered cumulation)
     std::vector<DecJob> djob;
-    std::vector<uint64_t> dc_off;  // compressed chunks: payload offsets / lengths / expected CRC
-    std::vector<uint32_t> dc_len, dc_crc;
-    bool dc_validate = false;
-    std::vector<uint8_t> dc_direct;
-    std::vector<uint64_t> du_off;  // uncompressed chunks (CRC32C)
-    std::vector<uint32_t> du_len;
-    std::vector<uint8_t> du_direct;
+    uint32_t ndc = 0, ndu = 0;  // compressed / uncompressed chunks among dact (DecAct::chunk counts them);
+                                // their launch lists are derived from dact at flush
+    bool dc_validate = false;   // some compressed chunk's decoder validates: the decode launch verifies CRCs
     // alt-codec jobs: their pieces and the launch lists of the codec kernels (inputs all staged)
     std::vector<nx::bt::AltPiece> apc;
     std::vector<nx::bt::AltJobD> ajob;
     uint64_t aslots = 0;  // alt slot bytes
-    struct AltList {
-        std::vector<uint64_t> off, slot;
-        std::vector<uint32_t> len, aux;  // aux: FastLZ encode level / decode in_avail; LZ4 encode level; decode olen
-        std::vector<int32_t> lim;        // FastLZ encode: readU16 limit
-        void clear() {
-            off.clear();
-            slot.clear();
-            len.clear();
-            aux.clear();
-            lim.clear();
-        }
-        size_t size() const { return off.size(); }
-    };
-    AltList flz_e, lzf_e, lz4_e, flz_d, lzf_d, lz4_d;
+    std::vector<AltEntry> alt[kAltLists];
     Pinned out;  // mapped result arena: job outputs, then the result records
     uint64_t out_used = 0, res_enc = 0, res_dec = 0, res_alt = 0;
     // Bytes the finish kernels are known to write into `out`: decoded messages (lengths from the
     // chunks' preambles).  Encoder outputs are not counted (they fill ~half of their bound-sized
     // reservation).  When the known bytes fill most of a large arena the finish kernels write a device
-    // mirror instead and one DMA copy moves it (launch_inner).
+    // mirror instead and one DMA copy moves it (place()).
     uint64_t est_out = 0;
     uint64_t res_spill = 0;  // the flush's spill area (decoded messages longer than their preamble said)
-    std::vector<uint64_t> dslot_off;  // decode slot of each compressed chunk (device, from slots + eslots)
+    std::vector<uint64_t> dslot_off;  // decode slot of each compressed chunk (device, from slots + eslots): set at
+                                      // flush, kept for apply()'s spills beyond the spill area
     std::vector<Job*> jobs;
     nx::h::DevBuf din, slots;
     Pinned gops;  // k_gather_host's op list, read by the kernel from pinned memory
@@ -585,26 +595,15 @@ struct Batch {
         dact.clear();
         dact_direct.clear();
         djob.clear();
-        dc_off.clear();
-        dc_len.clear();
-        dc_crc.clear();
-        dc_direct.clear();
+        ndc = ndu = 0;
         dc_validate = false;
-        du_off.clear();
-        du_len.clear();
-        du_direct.clear();
         out_used = res_enc = res_dec = res_alt = res_spill = 0;
         est_out = 0;
         dslot_off.clear();
         apc.clear();
         ajob.clear();
         aslots = 0;
-        flz_e.clear();
-        lzf_e.clear();
-        lz4_e.clear();
-        flz_d.clear();
-        lzf_d.clear();
-        lz4_d.clear();
+        for (std::vector<AltEntry>& L : alt) L.clear();
         for (Job* j : jobs) delete j;
         jobs.clear();
         inflight = done = false;
@@ -676,13 +675,7 @@ namespace {
 
 bool advance(nx_batcher* b, uint64_t upto, bool block);
 
-Batch* reuse_or_new_batch(nx_batcher* b) {
-    for (Batch* x : b->all) {
-        if (!x->inflight && x->live == 0 && x != b->cur) {
-            x->reset();
-            return x;
-        }
-    }
+Batch* new_batch(nx_batcher* b) {  // a batch object with its event, its pinned arenas counted in b->arena
     Batch* x = new Batch();
     if (hipEventCreateWithFlags(&x->ev, hipEventDisableTiming) != hipSuccess) {
         delete x;
@@ -693,14 +686,20 @@ Batch* reuse_or_new_batch(nx_batcher* b) {
     return x;
 }
 
-Batch* fresh_batch(nx_batcher* b) {
-    advance(b, ~0ull, false);  // apply every completed batch (in flush order), even if its jobs were released unpolled
-    return reuse_or_new_batch(b);
+Batch* reuse_or_new_batch(nx_batcher* b) {
+    for (Batch* x : b->all) {
+        if (!x->inflight && x->live == 0 && x != b->cur) {
+            x->reset();
+            return x;
+        }
+    }
+    return new_batch(b);
 }
 
 Batch* collecting(nx_batcher* b) {
     if (!b->cur) {
-        Batch* x = fresh_batch(b);
+        advance(b, ~0ull, false);  // apply every completed batch (in flush order), even if its jobs were released unpolled
+        Batch* x = reuse_or_new_batch(b);
         if (!b->cur) b->cur = x;  // advance() may have opened one for re-walked jobs
     }
     return b->cur;
@@ -725,7 +724,8 @@ void unwalk(Job* j) {  // the job no longer needs its walked bytes kept
 
 // Queue decoder job j's walked actions into batch bt.  Payloads are copied from S (host bytes the
 // walk ran over), or, with dS (the device address of S in registered memory), gathered from there at
-// flush.  On failure the batch's arrays go back to their sizes at entry (its other jobs stay valid).
+// flush.  The caller adds j to the batch's jobs.  On failure the batch's arrays go back to their sizes at
+// entry (its other jobs stay valid).
 // Snappy.decode's preamble (readPreamble, Snappy.java:404-420): the declared length, for sizing
 // estimates only (65 536, the frame decoder's cap, when it is malformed or absent)
 inline uint32_t snappy_declared_len(const uint8_t* p, size_t n) {
@@ -738,19 +738,15 @@ inline uint32_t snappy_declared_len(const uint8_t* p, size_t n) {
 }
 
 int32_t enqueue_dec(Batch* bt, Job* j, const uint8_t* S, size_t walked, const uint8_t* dS, int64_t staged = -1) {
-    const size_t n_act = bt->dact.size(), n_dc = bt->dc_off.size(), n_du = bt->du_off.size(), n_dir = bt->direct.size();
+    const size_t n_act = bt->dact.size(), n_dir = bt->direct.size();
+    const uint32_t n_dc = bt->ndc, n_du = bt->ndu;
     const uint64_t dir_used = bt->direct_used, est0 = bt->est_out;
     auto fail = [&](int32_t code) -> int32_t {
         bt->est_out = est0;
         bt->dact.resize(n_act);
         bt->dact_direct.resize(n_act);
-        bt->dc_off.resize(n_dc);
-        bt->dc_len.resize(n_dc);
-        bt->dc_crc.resize(n_dc);
-        bt->dc_direct.resize(n_dc);
-        bt->du_off.resize(n_du);
-        bt->du_len.resize(n_du);
-        bt->du_direct.resize(n_du);
+        bt->ndc = n_dc;
+        bt->ndu = n_du;
         bt->direct.resize(n_dir);
         bt->direct_used = dir_used;
         return code;
@@ -777,16 +773,11 @@ int32_t enqueue_dec(Batch* bt, Job* j, const uint8_t* S, size_t walked, const ui
             if (!st) return fail(NX_ERR_HIP);
             nx::copy_bytes(st, S + a.data, a.dlen);
         }
-        const uint8_t dir = dS ? 1 : 0;
-        bt->dact_direct.push_back(dir);
+        bt->dact_direct.push_back(dS ? 1 : 0);
         DecAct A{off, a.dlen, 0, 0, a.crc, a.dlen, 0};
         if (a.kind == SAct::Comp) {
             A.kind = 2;
-            A.chunk = (uint32_t)bt->dc_off.size();
-            bt->dc_off.push_back(off);
-            bt->dc_len.push_back(a.dlen);
-            bt->dc_crc.push_back(a.crc);
-            bt->dc_direct.push_back(dir);
+            A.chunk = bt->ndc++;
             if (j->dec->validate) bt->dc_validate = true;
             // the message's room: the preamble's length (never more than the bound); a chunk that
             // decodes longer (malformed, yet Java keeps it) spills (k_dec_finish, apply)
@@ -795,10 +786,7 @@ int32_t enqueue_dec(Batch* bt, Job* j, const uint8_t* S, size_t walked, const ui
             bt->est_out += A.cap;
         } else {
             A.kind = 1;
-            A.chunk = (uint32_t)bt->du_off.size();
-            bt->du_off.push_back(off);
-            bt->du_len.push_back(a.dlen);
-            bt->du_direct.push_back(dir);
+            A.chunk = bt->ndu++;
             out_need += a.dlen;
             bt->est_out += a.dlen;
         }
@@ -808,7 +796,6 @@ int32_t enqueue_dec(Batch* bt, Job* j, const uint8_t* S, size_t walked, const ui
     if (!bt->reserve_out(out_need + 16, &J.out_off)) return fail(NX_ERR_HIP);
     j->index = (uint32_t)bt->djob.size();
     bt->djob.push_back(J);
-    bt->jobs.push_back(j);
     return NX_OK;
 }
 
@@ -877,157 +864,215 @@ bool rewalk(nx_batcher* b, Batch* bt, Job* j, uint64_t q) {
     return true;
 }
 
-// Launch everything `bt` collected (batcher lock held).
-int32_t launch_inner(nx_batcher* b, Batch* bt) {
-    NX_CLEAR_STALE_ERROR();
-    const hipStream_t s = b->s[b->flushes % kStreams];
-    const nx::NoGrowScope no_grow;  // the workspaces reserved at nx_batcher_new: a flush never allocates them
-    const uint32_t nes = (uint32_t)bt->esl.size(), nej = (uint32_t)bt->ejob.size(), nda = (uint32_t)bt->dact.size();
-    const uint32_t ndj = (uint32_t)bt->djob.size(), ndc = (uint32_t)bt->dc_off.size(), ndu = (uint32_t)bt->du_off.size();
-    struct Lay {
-        uint64_t at = 0;
-        uint64_t put(uint64_t n) {
-            const uint64_t r = (at + 15) & ~15ull;
-            at = r + n;
-            return r;
-        }
-    } Lh, Ld;
-    // arrays the host fills (uploaded inside the staging arena)
-    const uint64_t o_esl = Lh.put(sizeof(EncSlice) * nes), o_ein = Lh.put(8ull * nes), o_eslot = Lh.put(8ull * nes),
-                   o_elen = Lh.put(4ull * nes), o_ejob = Lh.put(sizeof(EncJob) * nej), o_dact = Lh.put(sizeof(DecAct) * nda),
-                   o_djob = Lh.put(sizeof(DecJob) * ndj), o_dcoff = Lh.put(8ull * ndc), o_dclen = Lh.put(4ull * ndc),
-                   o_dccrc = Lh.put(4ull * ndc), o_dslot = Lh.put(8ull * ndc), o_duoff = Lh.put(8ull * ndu), o_dulen = Lh.put(4ull * ndu);
-    // arrays the kernels fill (device only)
-    const uint64_t o_eclen = Ld.put(4ull * nes), o_est = Ld.put(4ull * nes), o_ecrc = Ld.put(4ull * nes), o_dlen = Ld.put(4ull * ndc),
-                   o_dcons = Ld.put(4ull * ndc), o_dst = Ld.put(4ull * ndc), o_dcrc = Ld.put(4ull * ndc), o_ducrc = Ld.put(4ull * ndu);
-    // ---- FastLZ / LZF / LZ4 jobs: codec lists, decoder checksum lists, pieces
-    const uint32_t nap = (uint32_t)bt->apc.size(), naj = (uint32_t)bt->ajob.size();
-    Batch::AltList* AL[6] = {&bt->flz_e, &bt->lzf_e, &bt->lz4_e, &bt->flz_d, &bt->lzf_d, &bt->lz4_d};
-    // LZ4 frame encode takes one compression level per launch: order its entries by level
-    std::vector<uint32_t> lz4_perm(bt->lz4_e.size());
-    for (uint32_t i = 0; i < lz4_perm.size(); ++i) lz4_perm[i] = i;
-    std::stable_sort(lz4_perm.begin(), lz4_perm.end(), [&](uint32_t a, uint32_t c) { return bt->lz4_e.aux[a] < bt->lz4_e.aux[c]; });
-    {
-        Batch::AltList& Z = bt->lz4_e;
-        Batch::AltList P;
-        std::vector<uint32_t> pos(Z.size());
-        for (uint32_t k = 0; k < lz4_perm.size(); ++k) {
-            const uint32_t i = lz4_perm[k];
-            pos[i] = k;
-            P.off.push_back(Z.off[i]);
-            P.slot.push_back(Z.slot[i]);
-            P.len.push_back(Z.len[i]);
-            P.aux.push_back(Z.aux[i]);
-            P.lim.push_back(Z.lim[i]);
-        }
-        Z = std::move(P);
-        for (nx::bt::AltPiece& q : bt->apc)
-            if (q.kind == nx::bt::AK_LZ4_ENC) q.res = pos[q.res];
-    }
-    Batch::AltList ck[4];  // decoder checksums: Adler32 over slot / input, XXH32 over slot / input
-    for (nx::bt::AltPiece& q : bt->apc) {
-        if (q.kind < nx::bt::AK_DEC_FLZ || !q.pad) continue;
-        const bool raw = q.kind == nx::bt::AK_DEC_RAW;
-        const int li = (q.pad == 2 ? 2 : 0) + (raw ? 1 : 0);
-        ck[li].off.push_back(raw ? q.src : q.slot);
-        ck[li].len.push_back(raw ? q.len : q.olen);
-        q.aux = (uint32_t)ck[li].off.size();  // 1-based within its list; made global below
-    }
-    const uint32_t nck[4] = {(uint32_t)ck[0].off.size(), (uint32_t)ck[1].off.size(), (uint32_t)ck[2].off.size(), (uint32_t)ck[3].off.size()};
-    const uint32_t ck0[4] = {0, nck[0], nck[0] + nck[1], nck[0] + nck[1] + nck[2]};
-    for (nx::bt::AltPiece& q : bt->apc) {
-        if (q.kind < nx::bt::AK_DEC_FLZ || !q.pad) continue;
-        const int li = (q.pad == 2 ? 2 : 0) + (q.kind == nx::bt::AK_DEC_RAW ? 1 : 0);
-        q.aux += ck0[li];
-    }
-    const uint32_t ncks = ck0[3] + nck[3];
-    uint64_t o_al[6][5], o_ck[4][2];
-    for (int c = 0; c < 6; ++c) {
-        const uint64_t m = AL[c]->size();
-        o_al[c][0] = Lh.put(8 * m);
-        o_al[c][1] = Lh.put(4 * m);
-        o_al[c][2] = Lh.put(8 * m);
-        o_al[c][3] = Lh.put(4 * m);
-        o_al[c][4] = Lh.put(4 * m);
-    }
-    for (int c = 0; c < 4; ++c) {
-        o_ck[c][0] = Lh.put(8ull * nck[c]);
-        o_ck[c][1] = Lh.put(4ull * nck[c]);
-    }
-    const uint64_t o_apc = Lh.put(sizeof(nx::bt::AltPiece) * nap), o_ajob = Lh.put(sizeof(nx::bt::AltJobD) * naj);
-    const uint32_t nfe = (uint32_t)bt->flz_e.size(), nle = (uint32_t)bt->lzf_e.size(), nze = (uint32_t)bt->lz4_e.size();
-    const uint32_t nfd = (uint32_t)bt->flz_d.size(), nld = (uint32_t)bt->lzf_d.size(), nzd = (uint32_t)bt->lz4_d.size();
-    const uint64_t o_fclen = Ld.put(4ull * nfe), o_fst = Ld.put(4ull * nfe), o_fadl = Ld.put(4ull * nfe), o_lolen = Ld.put(4ull * nle),
-                   o_lst = Ld.put(4ull * nle), o_zolen = Ld.put(4ull * nze), o_zst = Ld.put(4ull * nze), o_dfr = Ld.put(4ull * nfd),
-                   o_dlst = Ld.put(4ull * nld), o_dzst = Ld.put(4ull * nzd), o_dcks = Ld.put(4ull * ncks);
-    uint64_t st_arr = 0;
-    uint8_t* h = bt->stage(Lh.at + 16, &st_arr);
-    if (!h) return NX_ERR_HIP;
-    // device input arena: [staging bytes][direct region]
-    const uint64_t d0 = (bt->st_used + 15) & ~15ull;
-    for (uint32_t i = 0; i < nes; ++i)
-        if (bt->esl_direct[i]) bt->esl[i].in_off += d0;
-    for (uint32_t i = 0; i < nda; ++i)
-        if (bt->dact_direct[i]) bt->dact[i].in_off += d0;
-    for (uint32_t i = 0; i < ndc; ++i)
-        if (bt->dc_direct[i]) bt->dc_off[i] += d0;
-    for (uint32_t i = 0; i < ndu; ++i)
-        if (bt->du_direct[i]) bt->du_off[i] += d0;
-    std::vector<uint64_t> ein(nes), eslot(nes), dslot(ndc);
-    std::vector<uint32_t> elen(nes);
-    for (uint32_t i = 0; i < nes; ++i) {
-        ein[i] = bt->esl[i].in_off;
-        eslot[i] = bt->esl[i].slot_off;
-        elen[i] = bt->esl[i].len;
-    }
-    uint64_t dslot_bytes = 0;
-    for (uint32_t i = 0; i < ndc; ++i) {
-        dslot[i] = dslot_bytes;
-        dslot_bytes += nx::bt::dec_slot_bytes(bt->dc_len[i]);
-    }
-    bt->dslot_off = dslot;
-    auto cp = [&](uint64_t off, const void* src, size_t n) {
-        if (n) memcpy(h + off, src, n);
-    };
-    cp(o_esl, bt->esl.data(), sizeof(EncSlice) * nes);
-    cp(o_ein, ein.data(), 8ull * nes);
-    cp(o_eslot, eslot.data(), 8ull * nes);
-    cp(o_elen, elen.data(), 4ull * nes);
-    cp(o_ejob, bt->ejob.data(), sizeof(EncJob) * nej);
-    cp(o_dact, bt->dact.data(), sizeof(DecAct) * nda);
-    cp(o_djob, bt->djob.data(), sizeof(DecJob) * ndj);
-    cp(o_dcoff, bt->dc_off.data(), 8ull * ndc);
-    cp(o_dclen, bt->dc_len.data(), 4ull * ndc);
-    cp(o_dccrc, bt->dc_crc.data(), 4ull * ndc);
-    cp(o_dslot, dslot.data(), 8ull * ndc);
-    cp(o_duoff, bt->du_off.data(), 8ull * ndu);
-    cp(o_dulen, bt->du_len.data(), 4ull * ndu);
-    // result records in the mapped arena, after the job outputs
-    if (naj) {
-        for (int c = 0; c < 6; ++c) {
-            const Batch::AltList& L = *AL[c];
-            const size_t m = L.size();
-            cp(o_al[c][0], L.off.data(), 8 * m);
-            cp(o_al[c][1], L.len.data(), 4 * m);
-            cp(o_al[c][2], L.slot.data(), 8 * m);
-            cp(o_al[c][3], L.aux.data(), 4 * m);
-            cp(o_al[c][4], L.lim.data(), 4 * m);
-        }
+// ---------------------------------------------------------------- one flush
+// The arrays of a flush.  Each is reserved once, by element type and count, 16-byte aligned (struct
+// Flush).  Its handle is an offset: the staging arena may move when the arrays' room is staged, and the
+// kernels' arrays sit behind the slots.  Flush::operator() makes it a pointer once the bases are known.
+template <class T>
+struct In {  // filled by the host inside the staging arena, uploaded with it
+    uint64_t off;
+};
+template <class T>
+struct Dev {  // filled by the kernels: device only, after the alt slots in `slots`
+    uint64_t off;
+};
+
+// Decoder checksums run as four launches: Adler32 over decoded slots / over raw blocks' input bytes, XXH32
+// over the same two.  The list of a piece that wants one, or -1:
+inline int ck_list(const nx::bt::AltPiece& q) {
+    if (q.kind < nx::bt::AK_DEC_FLZ || !q.cks) return -1;
+    return (q.cks == nx::bt::CK_XXH32 ? 2 : 0) + (q.kind == nx::bt::AK_DEC_RAW ? 1 : 0);
+}
+struct CkCount {
+    uint32_t n[4] = {}, first[4] = {}, total = 0;  // first: the list's first result in AltArrays::dcks
+    explicit CkCount(const std::vector<nx::bt::AltPiece>& apc) {
+        for (const nx::bt::AltPiece& q : apc)
+            if (const int c = ck_list(q); c >= 0) n[c] += 1;
         for (int c = 0; c < 4; ++c) {
-            cp(o_ck[c][0], ck[c].off.data(), 8ull * nck[c]);
-            cp(o_ck[c][1], ck[c].len.data(), 4ull * nck[c]);
+            first[c] = total;
+            total += n[c];
         }
-        cp(o_apc, bt->apc.data(), sizeof(nx::bt::AltPiece) * nap);
-        cp(o_ajob, bt->ajob.data(), sizeof(nx::bt::AltJobD) * naj);
-        if (!bt->reserve_out(sizeof(nx::bt::AltRes) * nap + 8, &bt->res_alt)) return NX_ERR_HIP;
     }
-    if (!bt->reserve_out(8ull * nej + 8, &bt->res_enc) || !bt->reserve_out(sizeof(DecRes) * nda + 8, &bt->res_dec)) return NX_ERR_HIP;
+};
+
+// LZ4 frame encode takes one (level, compressor) per launch: the list is uploaded ordered by AltEntry::aux,
+// submit order kept within each value.  Returns every entry's position in that order.
+std::vector<uint32_t> order_by_aux(const std::vector<AltEntry>& L) {
+    std::vector<uint32_t> perm(L.size()), pos(L.size());
+    for (uint32_t i = 0; i < perm.size(); ++i) perm[i] = i;
+    std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t c) { return L[a].aux < L[c].aux; });
+    for (uint32_t k = 0; k < perm.size(); ++k) pos[perm[k]] = k;
+    return pos;
+}
+
+// What the stages of one flush share.  Constructing it lays the flush out: every array is declared with
+// its reservation, in the order of the declarations.
+struct Flush {
+    nx_batcher* const b;
+    Batch* const bt;
+    const hipStream_t s;
+    uint8_t* H = nullptr;        // the uploaded arrays in the staging arena ...
+    const uint8_t* A = nullptr;  // ... and in the device input arena
+    uint8_t* din = nullptr;      // device input arena: [staging bytes][direct region, from d0]
+    uint64_t d0 = 0;
+    uint8_t *eslots = nullptr, *dslots = nullptr, *aslots = nullptr;  // Snappy encode / decode slots, alt slots
+    uint8_t* D = nullptr;        // the kernels' arrays, after them
+    uint8_t* ob = nullptr;       // where the finish kernels write: the mapped result arena, or its device mirror
+    bool dma_out = false;        // ... the mirror, moved by one DMA copy
+    template <class T>
+    const T* operator()(In<T> a) const { return reinterpret_cast<const T*>(A + a.off); }
+    template <class T>
+    T* operator()(Dev<T> a) const { return reinterpret_cast<T*>(D + a.off); }
+    template <class T>
+    T* host(In<T> a) const { return reinterpret_cast<T*>(H + a.off); }
+
+    uint64_t up_used = 0, up_off = 0, kern_used = 0;  // the host-filled arrays' room (uploaded from up_off in
+                                                      // the staging arena), the kernel-filled arrays' room
+    static uint64_t take(uint64_t& used, uint64_t bytes) {
+        const uint64_t at = align16(used);
+        used = at + bytes;
+        return at;
+    }
+    struct Copy {
+        uint64_t off;
+        const void* src;
+        size_t bytes;
+    };
+    std::vector<Copy> copies;  // carried out by fill_upload(), once the room is staged
+    template <class T>
+    In<T> room(size_t n) { return {take(up_used, sizeof(T) * n)}; }  // filled in place by fill_upload()
+    template <class T>
+    In<T> put(const std::vector<T>& v) {  // sent as it stands
+        const In<T> a = room<T>(v.size());
+        if (!v.empty()) copies.push_back({a.off, v.data(), sizeof(T) * v.size()});
+        return a;
+    }
+    template <class T>
+    Dev<T> out(size_t n) { return {take(kern_used, sizeof(T) * n)}; }
+
+    // Snappy encoder: slices and jobs as submitted, the encode launch's lists (from the slices), the results
+    const uint32_t nes = (uint32_t)bt->esl.size(), nej = (uint32_t)bt->ejob.size();
+    const In<EncSlice> esl = put(bt->esl);
+    const In<EncJob> ejob = put(bt->ejob);
+    const In<uint64_t> ein = room<uint64_t>(nes), eslot = room<uint64_t>(nes);
+    const In<uint32_t> elen = room<uint32_t>(nes);
+    const Dev<uint32_t> eclen = out<uint32_t>(nes), ecrc = out<uint32_t>(nes);
+    const Dev<int32_t> est = out<int32_t>(nes);
+    // Snappy decoder: chunks and jobs as submitted, the compressed (dc) and uncompressed (du) chunks'
+    // launch lists (from the chunks), the results, the spill area's cursor
+    const uint32_t nda = (uint32_t)bt->dact.size(), ndj = (uint32_t)bt->djob.size(), ndc = bt->ndc, ndu = bt->ndu;
+    const In<DecAct> dact = put(bt->dact);
+    const In<DecJob> djob = put(bt->djob);
+    const In<uint64_t> dcoff = room<uint64_t>(ndc), dslot = room<uint64_t>(ndc), duoff = room<uint64_t>(ndu);
+    const In<uint32_t> dclen = room<uint32_t>(ndc), dccrc = room<uint32_t>(ndc), dulen = room<uint32_t>(ndu);
+    const Dev<uint32_t> dlen = out<uint32_t>(ndc), dcons = out<uint32_t>(ndc), dcrc = out<uint32_t>(ndc), ducrc = out<uint32_t>(ndu);
+    const Dev<int32_t> dst = out<int32_t>(ndc);
+    const Dev<uint32_t> spill_cur = out<uint32_t>(1);
+    uint64_t dslot_bytes = 0;  // the decode slots (fill_upload)
+    uint32_t spill_cap = 0;
+    // FastLZ / LZF / LZ4: the codec lists, the decoder checksum lists, pieces and jobs, the codecs' results
+    const uint32_t nap = (uint32_t)bt->apc.size(), naj = (uint32_t)bt->ajob.size();
+    struct AltIn {
+        In<uint64_t> off, slot;
+        In<uint32_t> len, aux;
+        In<int32_t> lim;
+        uint32_t n;
+    };
+    AltIn alt_room(AltIx c) {
+        const uint32_t n = (uint32_t)bt->alt[c].size();
+        return {room<uint64_t>(n), room<uint64_t>(n), room<uint32_t>(n), room<uint32_t>(n), room<int32_t>(n), n};
+    }
+    const AltIn al[kAltLists] = {alt_room(FLZ_E), alt_room(LZF_E), alt_room(LZ4_E), alt_room(FLZ_D), alt_room(LZF_D), alt_room(LZ4_D)};
+    const CkCount cks{bt->apc};
+    const In<uint64_t> ck_off[4] = {room<uint64_t>(cks.n[0]), room<uint64_t>(cks.n[1]), room<uint64_t>(cks.n[2]), room<uint64_t>(cks.n[3])};
+    const In<uint32_t> ck_len[4] = {room<uint32_t>(cks.n[0]), room<uint32_t>(cks.n[1]), room<uint32_t>(cks.n[2]), room<uint32_t>(cks.n[3])};
+    const In<nx::bt::AltPiece> apc = put(bt->apc);
+    const In<nx::bt::AltJobD> ajob = put(bt->ajob);
+    const Dev<uint32_t> fclen = out<uint32_t>(al[FLZ_E].n), fadl = out<uint32_t>(al[FLZ_E].n);
+    const Dev<int32_t> fst = out<int32_t>(al[FLZ_E].n);
+    const Dev<uint32_t> lolen = out<uint32_t>(al[LZF_E].n), zolen = out<uint32_t>(al[LZ4_E].n);
+    const Dev<int32_t> lst = out<int32_t>(al[LZF_E].n), zst = out<int32_t>(al[LZ4_E].n);
+    const Dev<int32_t> dfr = out<int32_t>(al[FLZ_D].n), dlst = out<int32_t>(al[LZF_D].n), dzst = out<int32_t>(al[LZ4_D].n);
+    const Dev<uint32_t> dcks = out<uint32_t>(cks.total);
+
+    Flush(nx_batcher* b_, Batch* bt_) : b(b_), bt(bt_), s(b_->s[b_->flushes % kStreams]) {}
+};
+
+// Stage the arrays' room and fill it: the copies, then one pass over each record array that moves the
+// records of registered inputs into the direct region (d0 is known only now) and derives the kernels'
+// launch lists, written where they are uploaded from.
+int32_t fill_upload(Flush& F) {
+    Batch* bt = F.bt;
+    F.H = bt->stage(F.up_used + 16, &F.up_off);
+    if (!F.H) return NX_ERR_HIP;
+    for (const Flush::Copy& c : F.copies) memcpy(F.H + c.off, c.src, c.bytes);
+    F.d0 = align16(bt->st_used);
+    EncSlice* esl = F.host(F.esl);
+    for (uint32_t i = 0; i < F.nes; ++i) {
+        if (bt->esl_direct[i]) esl[i].in_off += F.d0;
+        F.host(F.ein)[i] = esl[i].in_off;
+        F.host(F.eslot)[i] = esl[i].slot_off;
+        F.host(F.elen)[i] = esl[i].len;
+    }
+    DecAct* dact = F.host(F.dact);
+    bt->dslot_off.resize(F.ndc);
+    for (uint32_t i = 0; i < F.nda; ++i) {
+        DecAct& a = dact[i];
+        if (bt->dact_direct[i]) a.in_off += F.d0;
+        if (a.kind == 2) {
+            F.host(F.dcoff)[a.chunk] = a.in_off;
+            F.host(F.dclen)[a.chunk] = a.len;
+            F.host(F.dccrc)[a.chunk] = a.crc;
+            F.host(F.dslot)[a.chunk] = bt->dslot_off[a.chunk] = F.dslot_bytes;
+            F.dslot_bytes += nx::bt::dec_slot_bytes(a.len);
+        } else {
+            F.host(F.duoff)[a.chunk] = a.in_off;
+            F.host(F.dulen)[a.chunk] = a.len;
+        }
+    }
+    const std::vector<uint32_t> lz4_pos = order_by_aux(bt->alt[LZ4_E]);
+    for (int c = 0; c < kAltLists; ++c) {
+        const Flush::AltIn& L = F.al[c];
+        for (uint32_t i = 0; i < L.n; ++i) {
+            const AltEntry& e = bt->alt[c][i];
+            const uint32_t k = c == LZ4_E ? lz4_pos[i] : i;
+            F.host(L.off)[k] = e.off;
+            F.host(L.slot)[k] = e.slot;
+            F.host(L.len)[k] = e.len;
+            F.host(L.aux)[k] = e.aux;
+            F.host(L.lim)[k] = e.lim;
+        }
+    }
+    // the uploaded pieces: an LZ4 block's results are at its place in the launch order; a decoder piece with
+    // a checksum joins its list and learns its result's index (aux, 1-based)
+    nx::bt::AltPiece* apc = F.host(F.apc);
+    uint32_t nck[4] = {};
+    for (uint32_t p = 0; p < F.nap; ++p) {
+        nx::bt::AltPiece& q = apc[p];
+        if (q.kind == nx::bt::AK_LZ4_ENC) q.res = lz4_pos[q.res];
+        const int c = ck_list(q);
+        if (c < 0) continue;
+        const bool raw = q.kind == nx::bt::AK_DEC_RAW;
+        const uint32_t i = nck[c]++;
+        F.host(F.ck_off[c])[i] = raw ? q.src : q.slot;
+        F.host(F.ck_len[c])[i] = raw ? q.len : q.olen;
+        q.aux = F.cks.first[c] + i + 1;
+    }
+    return NX_OK;
+}
+
+// Result records and spill area (in the mapped arena, after the job outputs), the result path, the device
+// arenas and their bases.
+int32_t place(Flush& F) {
+    nx_batcher* b = F.b;
+    Batch* bt = F.bt;
+    if (F.naj && !bt->reserve_out(sizeof(nx::bt::AltRes) * F.nap + 8, &bt->res_alt)) return NX_ERR_HIP;
+    if (!bt->reserve_out(8ull * F.nej + 8, &bt->res_enc) || !bt->reserve_out(sizeof(DecRes) * F.nda + 8, &bt->res_dec)) return NX_ERR_HIP;
     // spill area: a chunk that decodes longer than its preamble said (Java grows its buffer up to
     // 65 536, SnappyFrameDecoder.java:203) has no room in its message reservation; k_dec_finish moves
     // it here, so apply() need not copy it from the device (only spills beyond this area do)
-    const uint32_t spill_cap = (uint32_t)std::min<uint64_t>(nx::bt::kSpillBytes, 65536ull * ndc);
-    if (ndc && !bt->reserve_out(spill_cap, &bt->res_spill)) return NX_ERR_HIP;
-    const uint64_t o_spc = Ld.put(4);
+    F.spill_cap = (uint32_t)std::min<uint64_t>(nx::bt::kSpillBytes, 65536ull * F.ndc);
+    if (F.ndc && !bt->reserve_out(F.spill_cap, &bt->res_spill)) return NX_ERR_HIP;
     // Where the finish kernels write: straight into the mapped arena (their stores cross PCIe), or,
     // when the expected bytes fill most of a large arena (decoded messages: lengths known from the
     // preambles), into a device mirror that one DMA copy then moves.  The copy engine does not hold
@@ -1035,30 +1080,35 @@ int32_t launch_inner(nx_batcher* b, Batch* bt) {
     // the finish kernel's host writes ran at 53 GB/s and slowed a concurrent k_parse 2-3x).
     // The spill area is reserved for rare malformed chunks: it counts neither as expected bytes nor
     // against them (counted in out_used it leaned mid-sized flushes away from the DMA path).
-    const uint64_t est = bt->est_out + 8ull * nej + sizeof(DecRes) * nda + sizeof(nx::bt::AltRes) * (naj ? bt->apc.size() : 0);
-    const uint64_t spill_res = ndc ? spill_cap : 0;
-    const uint64_t used_wo_spill = bt->out_used > spill_res ? bt->out_used - spill_res : 0;
-    const bool dma_out = bt->out_used >= nx::bt::kDmaOutMin && est * 5 >= used_wo_spill * 4;
+    const uint64_t est = bt->est_out + 8ull * F.nej + sizeof(DecRes) * F.nda + sizeof(nx::bt::AltRes) * (F.naj ? F.nap : 0);
+    const uint64_t used_wo_spill = bt->out_used > F.spill_cap ? bt->out_used - F.spill_cap : 0;
+    F.dma_out = bt->out_used >= nx::bt::kDmaOutMin && est * 5 >= used_wo_spill * 4;
     nx::h::DevBuf& mirror = b->dmirror[b->flushes % kStreams];
-    if (dma_out && !mirror.ensure(bt->out_used)) return NX_ERR_HIP;
-    uint8_t* const ob = dma_out ? mirror.as<uint8_t>() : bt->out.d;
-    if (!bt->din.ensure(d0 + bt->direct_used + 16) || !bt->slots.ensure(bt->eslots + dslot_bytes + bt->aslots + Ld.at + 128)) return NX_ERR_HIP;
-    uint8_t* din = bt->din.as<uint8_t>();
-    uint8_t* slots = bt->slots.as<uint8_t>();
-    uint8_t* dslots = slots + bt->eslots;
-    uint8_t* aslots = reinterpret_cast<uint8_t*>(((uintptr_t)(dslots + dslot_bytes) + 15) & ~(uintptr_t)15);
-    uint8_t* D = aslots + bt->aslots;
-    D = reinterpret_cast<uint8_t*>(((uintptr_t)D + 15) & ~(uintptr_t)15);
-    // Host -> device.  Registered inputs (and a small staging arena) move in one gather launch that
-    // reads the mapped pages, its op list itself read from pinned memory: no copy-engine work.  The
-    // copy engines run the batches' result copies in order, and a descriptor copy queued behind the
-    // previous batch's 500 MB result copy held this batch's gather (and, for an op list in pageable
-    // memory, the submitting thread) until that copy ended (round 4 e2e trace).  A large staging
-    // arena (payloads copied at submit) still goes by one DMA copy.
-    // (round 5 measured the whole staging arena through the gather as well, profiles/r05/s10: no better)
+    if (F.dma_out && !mirror.ensure(bt->out_used)) return NX_ERR_HIP;
+    F.ob = F.dma_out ? mirror.as<uint8_t>() : bt->out.d;
+    if (!bt->din.ensure(F.d0 + bt->direct_used + 16) || !bt->slots.ensure(bt->eslots + F.dslot_bytes + bt->aslots + F.kern_used + 128))
+        return NX_ERR_HIP;
+    F.din = bt->din.as<uint8_t>();
+    F.A = F.din + F.up_off;
+    F.eslots = bt->slots.as<uint8_t>();
+    F.dslots = F.eslots + bt->eslots;
+    F.aslots = reinterpret_cast<uint8_t*>(align16((uintptr_t)(F.dslots + F.dslot_bytes)));
+    F.D = reinterpret_cast<uint8_t*>(align16((uintptr_t)(F.aslots + bt->aslots)));
+    return NX_OK;
+}
+
+// Host -> device.  Registered inputs (and a small staging arena) move in one gather launch that
+// reads the mapped pages, its op list itself read from pinned memory: no copy-engine work.  The
+// copy engines run the batches' result copies in order, and a descriptor copy queued behind the
+// previous batch's 500 MB result copy held this batch's gather (and, for an op list in pageable
+// memory, the submitting thread) until that copy ended (round 4 e2e trace).  A large staging
+// arena (payloads copied at submit) still goes by one DMA copy.
+// (round 5 measured the whole staging arena through the gather as well, profiles/r05/s10: no better)
+int32_t transfer_in(const Flush& F) {
+    Batch* bt = F.bt;
     const bool dma_in = bt->direct.empty() && bt->st_used > nx::bt::kGatherStageMax;
     if (dma_in) {
-        NX_HIP_CHECK(hipMemcpyAsync(din, bt->staging.h, bt->st_used, hipMemcpyHostToDevice, s));
+        NX_HIP_CHECK(hipMemcpyAsync(F.din, bt->staging.h, bt->st_used, hipMemcpyHostToDevice, F.s));
     } else if (bt->st_used || !bt->direct.empty()) {
         const uint64_t piece = nx::bt::kGatherPiece;
         const uint32_t nst = (uint32_t)((bt->st_used + piece - 1) / piece);
@@ -1070,126 +1120,164 @@ int32_t launch_inner(nx_batcher* b, Batch* bt) {
             ops[k] = {bt->staging.d + o, o, std::min<uint64_t>(piece, bt->st_used - o)};
         }
         for (uint32_t k = 0; k < (uint32_t)bt->direct.size(); ++k)
-            ops[nst + k] = {bt->direct[k].dsrc, d0 + bt->direct[k].din_off, bt->direct[k].len};
-        hipLaunchKernelGGL(nx::bt::k_gather_host, nx::bt::pcie_grid(ng), dim3(256), 0, s,
-                           reinterpret_cast<const nx::bt::GatherOp*>(bt->gops.d), ng, din);
+            ops[nst + k] = {bt->direct[k].dsrc, F.d0 + bt->direct[k].din_off, bt->direct[k].len};
+        hipLaunchKernelGGL(nx::bt::k_gather_host, nx::bt::pcie_grid(ng), dim3(256), 0, F.s,
+                           reinterpret_cast<const nx::bt::GatherOp*>(bt->gops.d), ng, F.din);
         NX_HIP_CHECK(hipGetLastError());
-        b->launches += 1;
+        F.b->launches += 1;
     }
-    const uint8_t* A = din + st_arr;
+    return NX_OK;
+}
+
+// CRC32C + Snappy.encode of every encoder slice of every channel, then the framed outputs
+int32_t run_snappy_encode(const Flush& F) {
+    if (!F.nes) return NX_OK;
+    int32_t r = nx_crc32c_masked_batch(F.din, F(F.ein), F(F.elen), F(F.ecrc), F.nes, F.s);
+    if (r != NX_OK) return r;
+    r = nx_snappy_encode_batch(F.din, F(F.ein), F(F.elen), F.eslots, F(F.eslot), F(F.eclen), F(F.est), F.nes, F.s);
+    if (r != NX_OK) return r;
+    hipLaunchKernelGGL(nx::bt::k_enc_finish, nx::bt::pcie_grid(F.nej), dim3(256), 0, F.s, F.din, F.eslots, F(F.esl), F(F.eclen),
+                       F(F.est), F(F.ecrc), F(F.ejob), F.nej, F.ob, reinterpret_cast<int64_t*>(F.ob + F.bt->res_enc));
+    NX_HIP_CHECK(hipGetLastError());
+    F.b->launches += 3;
+    F.b->chunks += F.nes;
+    return NX_OK;
+}
+
+// Snappy.decode (+ fused CRC verify) of every compressed chunk, CRC32C of the uncompressed ones, then
+// the jobs' messages
+int32_t run_snappy_decode(const Flush& F) {
+    if (!F.ndj) return NX_OK;
     int32_t r;
-    if (nes) {  // CRC32C + Snappy.encode of every encoder slice of every channel
-        r = nx_crc32c_masked_batch(din, (const uint64_t*)(A + o_ein), (const uint32_t*)(A + o_elen), (uint32_t*)(D + o_ecrc), nes, s);
+    if (F.ndc) {
+        r = nx_snappy_decode_batch(F.din, F(F.dcoff), F(F.dclen), F.dslots, F(F.dslot), nullptr, F(F.dlen), F(F.dcons), F(F.dst),
+                                   F.bt->dc_validate ? F(F.dccrc) : nullptr, F(F.dcrc), F.ndc, F.s);
         if (r != NX_OK) return r;
-        r = nx_snappy_encode_batch(din, (const uint64_t*)(A + o_ein), (const uint32_t*)(A + o_elen), slots, (const uint64_t*)(A + o_eslot),
-                                   (uint32_t*)(D + o_eclen), (int32_t*)(D + o_est), nes, s);
+        F.b->launches += 1;
+    }
+    if (F.ndu) {
+        r = nx_crc32c_masked_batch(F.din, F(F.duoff), F(F.dulen), F(F.ducrc), F.ndu, F.s);
         if (r != NX_OK) return r;
-        hipLaunchKernelGGL(nx::bt::k_enc_finish, nx::bt::pcie_grid(nej), dim3(256), 0, s, din, slots, (const EncSlice*)(A + o_esl),
-                           (const uint32_t*)(D + o_eclen), (const int32_t*)(D + o_est), (const uint32_t*)(D + o_ecrc),
-                           (const EncJob*)(A + o_ejob), nej, ob, (int64_t*)(ob + bt->res_enc));
-        NX_HIP_CHECK(hipGetLastError());
-        b->launches += 3;
-        b->chunks += nes;
+        F.b->launches += 1;
     }
-    if (ndj) {  // Snappy.decode (+ fused CRC verify) of every compressed chunk, CRC32C of uncompressed ones
-        if (ndc) {
-            r = nx_snappy_decode_batch(din, (const uint64_t*)(A + o_dcoff), (const uint32_t*)(A + o_dclen), dslots,
-                                       (const uint64_t*)(A + o_dslot), nullptr, (uint32_t*)(D + o_dlen), (uint32_t*)(D + o_dcons),
-                                       (int32_t*)(D + o_dst), bt->dc_validate ? (const uint32_t*)(A + o_dccrc) : nullptr,
-                                       (uint32_t*)(D + o_dcrc), ndc, s);
-            if (r != NX_OK) return r;
-            b->launches += 1;
-        }
-        if (ndu) {
-            r = nx_crc32c_masked_batch(din, (const uint64_t*)(A + o_duoff), (const uint32_t*)(A + o_dulen), (uint32_t*)(D + o_ducrc), ndu, s);
-            if (r != NX_OK) return r;
-            b->launches += 1;
-        }
-        if (ndc) NX_HIP_CHECK(hipMemsetAsync(D + o_spc, 0, 4, s));
-        hipLaunchKernelGGL(nx::bt::k_dec_finish, nx::bt::pcie_grid(ndj), dim3(256), 0, s, din, dslots, (const uint64_t*)(A + o_dslot),
-                           (const DecAct*)(A + o_dact),
-                           (const DecJob*)(A + o_djob), ndj, (const uint32_t*)(D + o_dlen), (const uint32_t*)(D + o_dcons),
-                           (const int32_t*)(D + o_dst), (const uint32_t*)(D + o_dcrc), (const uint32_t*)(D + o_ducrc), ob,
-                           (DecRes*)(ob + bt->res_dec), bt->res_spill, ndc ? spill_cap : 0u, (uint32_t*)(D + o_spc));
-        NX_HIP_CHECK(hipGetLastError());
+    if (F.ndc) NX_HIP_CHECK(hipMemsetAsync(F(F.spill_cur), 0, 4, F.s));
+    hipLaunchKernelGGL(nx::bt::k_dec_finish, nx::bt::pcie_grid(F.ndj), dim3(256), 0, F.s, F.din, F.dslots, F(F.dslot), F(F.dact),
+                       F(F.djob), F.ndj, F(F.dlen), F(F.dcons), F(F.dst), F(F.dcrc), F(F.ducrc), F.ob,
+                       reinterpret_cast<DecRes*>(F.ob + F.bt->res_dec), F.bt->res_spill, F.spill_cap, F(F.spill_cur));
+    NX_HIP_CHECK(hipGetLastError());
+    F.b->launches += 1;
+    F.b->chunks += F.ndc + F.ndu;
+    return NX_OK;
+}
+
+// FastLZ / LZF / LZ4: one launch per codec kernel for every job of every channel, the decoders'
+// checksums, then the jobs' outputs
+int32_t run_alt(const Flush& F) {
+    if (!F.naj) return NX_OK;
+    nx_batcher* b = F.b;
+    const hipStream_t s = F.s;
+    int32_t r;
+    if (const auto& L = F.al[FLZ_E]; L.n) {  // FastLz.compress + the frame's Adler32 of every block (FastLzFrameEncoder.java:136-158)
+        r = nx_fastlz_compress_batch(F.din, F(L.off), F(L.len), F.aslots, F(L.slot), F(F.fclen), reinterpret_cast<const int32_t*>(F(L.aux)),
+                                     F(L.lim), F(F.fst), L.n, s);
+        if (r != NX_OK) return r;
+        r = nx_adler32_batch(F.din, F(L.off), F(L.len), F(F.fadl), L.n, s);
+        if (r != NX_OK) return r;
+        b->launches += 2;
+    }
+    if (const auto& L = F.al[LZF_E]; L.n) {
+        r = nx_lzf_encode_batch(F.din, F(L.off), F(L.len), F.aslots, F(L.slot), F(F.lolen), F(F.lst), L.n, s);
+        if (r != NX_OK) return r;
         b->launches += 1;
-        b->chunks += ndc + ndu;
     }
-    if (naj) {  // FastLZ / LZF / LZ4: one launch per codec kernel for every job of every channel
-        auto U64 = [&](int c, int f) { return (const uint64_t*)(A + o_al[c][f]); };
-        auto U32 = [&](int c, int f) { return (const uint32_t*)(A + o_al[c][f]); };
-        auto I32 = [&](int c, int f) { return (const int32_t*)(A + o_al[c][f]); };
-        if (nfe) {  // FastLz.compress + the frame's Adler32 of every block (FastLzFrameEncoder.java:136-158)
-            r = nx_fastlz_compress_batch(din, U64(0, 0), U32(0, 1), aslots, U64(0, 2), (uint32_t*)(D + o_fclen), I32(0, 3), I32(0, 4),
-                                         (int32_t*)(D + o_fst), nfe, s);
-            if (r != NX_OK) return r;
-            r = nx_adler32_batch(din, U64(0, 0), U32(0, 1), (uint32_t*)(D + o_fadl), nfe, s);
-            if (r != NX_OK) return r;
-            b->launches += 2;
-        }
-        if (nle) {
-            r = nx_lzf_encode_batch(din, U64(1, 0), U32(1, 1), aslots, U64(1, 2), (uint32_t*)(D + o_lolen), (int32_t*)(D + o_lst), nle, s);
-            if (r != NX_OK) return r;
-            b->launches += 1;
-        }
-        for (uint32_t a0 = 0; a0 < nze;) {  // one launch per compression level (usually one)
-            uint32_t a1 = a0;
-            while (a1 < nze && bt->lz4_e.aux[a1] == bt->lz4_e.aux[a0]) ++a1;
-            // aux = compressionLevel | highCompressor << 8: one launch per (level, compressor)
-            r = nx_lz4_frame_encode_batch_ex(din, U64(2, 0) + a0, U32(2, 1) + a0, aslots, U64(2, 2) + a0, (uint32_t*)(D + o_zolen) + a0,
-                                             (int32_t)(bt->lz4_e.aux[a0] & 0xFFu), (int32_t)(bt->lz4_e.aux[a0] >> 8),
-                                             (int32_t*)(D + o_zst) + a0, a1 - a0, s);
-            if (r != NX_OK) return r;
-            b->launches += 1;
-            a0 = a1;
-        }
-        if (nfd) {  // FastLz.decompress (in_avail = the cumulation's readable bytes from the block on)
-            r = nx_fastlz_decompress_batch(din, U64(3, 0), U32(3, 1), U32(3, 3), aslots, U64(3, 2), (const uint32_t*)I32(3, 4),
-                                           (int32_t*)(D + o_dfr), nfd, s);
-            if (r != NX_OK) return r;
-            b->launches += 1;
-        }
-        if (nld) {
-            r = nx_lzf_decode_batch(din, U64(4, 0), U32(4, 1), aslots, U64(4, 2), U32(4, 3), (int32_t*)(D + o_dlst), nld, s);
-            if (r != NX_OK) return r;
-            b->launches += 1;
-        }
-        if (nzd) {
-            r = nx_lz4_decode_batch(din, U64(5, 0), U32(5, 1), aslots, U64(5, 2), U32(5, 3), (int32_t*)(D + o_dzst), nzd, s);
-            if (r != NX_OK) return r;
-            b->launches += 1;
-        }
-        uint32_t* dcks = (uint32_t*)(D + o_dcks);
-        for (int c = 0; c < 4; ++c) {  // decoder checksums (after the decodes: stream order)
-            if (!nck[c]) continue;
-            const uint8_t* base = (c & 1) ? din : aslots;
-            const uint64_t* co = (const uint64_t*)(A + o_ck[c][0]);
-            const uint32_t* cl = (const uint32_t*)(A + o_ck[c][1]);
-            r = c < 2 ? nx_adler32_batch(base, co, cl, dcks + ck0[c], nck[c], s)
-                      : nx_xxhash32_batch(base, co, cl, nx::af::kLz4Seed, dcks + ck0[c], nck[c], s);
-            if (r != NX_OK) return r;
-            b->launches += 1;
-        }
-        const nx::bt::AltArrays R{(const uint32_t*)(D + o_fclen), (const int32_t*)(D + o_fst), (const uint32_t*)(D + o_fadl),
-                                  (const uint32_t*)(D + o_lolen), (const int32_t*)(D + o_lst), (const uint32_t*)(D + o_zolen),
-                                  (const int32_t*)(D + o_zst), (const int32_t*)(D + o_dfr), (const int32_t*)(D + o_dlst),
-                                  (const int32_t*)(D + o_dzst), dcks};
-        hipLaunchKernelGGL(nx::bt::k_alt_finish, nx::bt::pcie_grid(naj), dim3(256), 0, s, din, aslots, (const nx::bt::AltPiece*)(A + o_apc),
-                           (const nx::bt::AltJobD*)(A + o_ajob), naj, R, ob, (nx::bt::AltRes*)(ob + bt->res_alt));
-        NX_HIP_CHECK(hipGetLastError());
+    const auto& Z = F.al[LZ4_E];
+    const uint32_t* zaux = F.host(Z.aux);  // in launch order (fill_upload)
+    for (uint32_t a0 = 0; a0 < Z.n;) {  // aux = compressionLevel | highCompressor << 8: one launch per value (usually one)
+        uint32_t a1 = a0;
+        while (a1 < Z.n && zaux[a1] == zaux[a0]) ++a1;
+        r = nx_lz4_frame_encode_batch_ex(F.din, F(Z.off) + a0, F(Z.len) + a0, F.aslots, F(Z.slot) + a0, F(F.zolen) + a0,
+                                         (int32_t)(zaux[a0] & 0xFFu), (int32_t)(zaux[a0] >> 8), F(F.zst) + a0, a1 - a0, s);
+        if (r != NX_OK) return r;
         b->launches += 1;
-        b->chunks += nfe + nle + nze + nfd + nld + nzd;
+        a0 = a1;
     }
-    if (dma_out) {
-        NX_HIP_CHECK(hipMemcpyAsync(bt->out.h, ob, bt->out_used, hipMemcpyDeviceToHost, s));
+    if (const auto& L = F.al[FLZ_D]; L.n) {  // FastLz.decompress (aux = in_avail: the cumulation's readable bytes from the block on)
+        r = nx_fastlz_decompress_batch(F.din, F(L.off), F(L.len), F(L.aux), F.aslots, F(L.slot), reinterpret_cast<const uint32_t*>(F(L.lim)),
+                                       F(F.dfr), L.n, s);
+        if (r != NX_OK) return r;
+        b->launches += 1;
+    }
+    if (const auto& L = F.al[LZF_D]; L.n) {
+        r = nx_lzf_decode_batch(F.din, F(L.off), F(L.len), F.aslots, F(L.slot), F(L.aux), F(F.dlst), L.n, s);
+        if (r != NX_OK) return r;
+        b->launches += 1;
+    }
+    if (const auto& L = F.al[LZ4_D]; L.n) {
+        r = nx_lz4_decode_batch(F.din, F(L.off), F(L.len), F.aslots, F(L.slot), F(L.aux), F(F.dzst), L.n, s);
+        if (r != NX_OK) return r;
+        b->launches += 1;
+    }
+    uint32_t* dcks = F(F.dcks);
+    for (int c = 0; c < 4; ++c) {  // decoder checksums (after the decodes: stream order)
+        const uint32_t n = F.cks.n[c];
+        if (!n) continue;
+        const uint8_t* base = (c & 1) ? F.din : F.aslots;
+        r = c < 2 ? nx_adler32_batch(base, F(F.ck_off[c]), F(F.ck_len[c]), dcks + F.cks.first[c], n, s)
+                  : nx_xxhash32_batch(base, F(F.ck_off[c]), F(F.ck_len[c]), nx::af::kLz4Seed, dcks + F.cks.first[c], n, s);
+        if (r != NX_OK) return r;
+        b->launches += 1;
+    }
+    const nx::bt::AltArrays R{F(F.fclen), F(F.fst), F(F.fadl), F(F.lolen), F(F.lst), F(F.zolen), F(F.zst), F(F.dfr), F(F.dlst), F(F.dzst), dcks};
+    hipLaunchKernelGGL(nx::bt::k_alt_finish, nx::bt::pcie_grid(F.naj), dim3(256), 0, s, F.din, F.aslots, F(F.apc), F(F.ajob), F.naj, R,
+                       F.ob, reinterpret_cast<nx::bt::AltRes*>(F.ob + F.bt->res_alt));
+    NX_HIP_CHECK(hipGetLastError());
+    b->launches += 1;
+    for (int c = 0; c < kAltLists; ++c) b->chunks += F.al[c].n;
+    return NX_OK;
+}
+
+// Device -> host for a mirrored result arena, then the batch's event: it is in flight, next in flush order.
+int32_t transfer_out(const Flush& F) {
+    nx_batcher* b = F.b;
+    Batch* bt = F.bt;
+    if (F.dma_out) {
+        NX_HIP_CHECK(hipMemcpyAsync(bt->out.h, F.ob, bt->out_used, hipMemcpyDeviceToHost, F.s));
         b->dma_flushes += 1;
         b->dma_bytes += bt->out_used;
     }
-    NX_HIP_CHECK(hipEventRecord(bt->ev, s));
+    NX_HIP_CHECK(hipEventRecord(bt->ev, F.s));
     bt->inflight = true;
     bt->seq = b->flushes;
     b->flushes += 1;
     return NX_OK;
+}
+
+// Launch everything `bt` collected (batcher lock held).
+int32_t launch_inner(nx_batcher* b, Batch* bt) {
+    NX_CLEAR_STALE_ERROR();
+    const nx::NoGrowScope no_grow;  // the workspaces reserved at nx_batcher_new: a flush never allocates them
+    Flush F(b, bt);
+    int32_t r = fill_upload(F);
+    if (r == NX_OK) r = place(F);
+    if (r == NX_OK) r = transfer_in(F);
+    if (r == NX_OK) r = run_snappy_encode(F);
+    if (r == NX_OK) r = run_snappy_decode(F);
+    if (r == NX_OK) r = run_alt(F);
+    if (r == NX_OK) r = transfer_out(F);
+    return r;
+}
+
+// Job j could not run on the GPU: it completes with the error, and its decoder turns corrupted.
+void complete_launch_failed(Job* j, int32_t code) {
+    j->applied = true;
+    j->status = code;
+    j->err = "GPU batch launch failed";
+    if (j->kind == JobKind::SnappyDec && j->dec) {
+        unwalk(j);
+        j->dec->corrupted = true;
+        trim_hist(j->dec);
+    }
+    if (j->kind == JobKind::AltDec && j->adec) j->adec->corrupted = true;
 }
 
 // A launch that failed part-way: wait for whatever of it reached the stream, then complete every job
@@ -1199,16 +1287,8 @@ int32_t launch_inner(nx_batcher* b, Batch* bt) {
 int32_t fail_batch(nx_batcher* b, Batch* bt, int32_t code) {
     (void)hipStreamSynchronize(b->s[b->flushes % kStreams]);
     for (Job* j : bt->jobs) {
-        j->applied = true;
-        j->status = code;
-        j->err = "GPU batch launch failed";
+        complete_launch_failed(j, code);
         j->msgs.clear();
-        if (j->kind == 1 && j->dec) {
-            unwalk(j);
-            j->dec->corrupted = true;
-            trim_hist(j->dec);
-        }
-        if (j->kind == 3 && j->adec) j->adec->corrupted = true;
     }
     bt->inflight = false;
     bt->done = true;
@@ -1229,7 +1309,7 @@ void apply_alt(Batch* bt, Job* j, const nx::bt::AltRes* ares) {
     using namespace nx::bt;
     j->applied = true;
     const AltJobD& J = bt->ajob[j->index];
-    if (j->kind == 2) {  // encoder
+    if (j->kind == JobKind::AltEnc) {
         uint64_t total = 0;
         for (uint32_t k = J.p0; k < J.p0 + J.np; ++k) {
             if (ares[k].status != NX_OK) {
@@ -1253,28 +1333,31 @@ void apply_alt(Batch* bt, Job* j, const nx::bt::AltRes* ares) {
         const AltRes& R = ares[J.p0 + i];
         const AltPiece& P = bt->apc[J.p0 + i];
         const nx::af::Blk& B = j->ablk[i];
-        if (R.status != NX_OK) {
-            if (j->codec == 0) {
-                int32_t code;
-                std::string msg;
-                const int32_t v = R.status == NX_ERR_FASTLZ_LENGTH_MISMATCH ? (int32_t)R.len : R.status;
-                const uint8_t first = B.clen ? bt->staging.h[P.src] : 0;
-                (void)nx::af::flz_block_error(v, B.olen, first, &code, &msg);
-                fail(code, msg);
-            } else {
-                fail(R.status, j->codec == 1 ? nx::af::lzf_block_error() : nx::af::lz4_block_error());
-            }
-            return;
+        bool emit = true;
+        switch (j->codec) {
+            case Codec::FastLz:
+                if (R.status != NX_OK) {
+                    int32_t code;
+                    std::string msg;
+                    const int32_t v = R.status == NX_ERR_FASTLZ_LENGTH_MISMATCH ? (int32_t)R.len : R.status;
+                    const uint8_t first = B.clen ? bt->staging.h[P.src] : 0;
+                    (void)nx::af::flz_block_error(v, B.olen, first, &code, &msg);
+                    return fail(code, msg);
+                }
+                if (B.has_cks && j->validate && R.cks != B.cks)
+                    return fail(NX_ERR_FASTLZ_CRC_MISMATCH, nx::af::flz_checksum_error(R.cks, B.cks));
+                emit = B.olen > 0;
+                break;
+            case Codec::Lzf:
+                if (R.status != NX_OK) return fail(R.status, nx::af::lzf_block_error());
+                emit = B.comp || B.clen > 0;
+                break;
+            case Codec::Lz4:
+                if (R.status != NX_OK) return fail(R.status, nx::af::lz4_block_error());
+                if (j->validate && (R.cks & 0x0FFFFFFFu) != B.cks)
+                    return fail(NX_ERR_LZ4_CHECKSUM_MISMATCH, nx::af::lz4_checksum_error(R.cks & 0x0FFFFFFFu, B.cks));
+                break;
         }
-        if (j->codec == 0 && B.has_cks && j->validate && R.cks != B.cks) {
-            fail(NX_ERR_FASTLZ_CRC_MISMATCH, nx::af::flz_checksum_error(R.cks, B.cks));
-            return;
-        }
-        if (j->codec == 2 && j->validate && (R.cks & 0x0FFFFFFFu) != B.cks) {
-            fail(NX_ERR_LZ4_CHECKSUM_MISMATCH, nx::af::lz4_checksum_error(R.cks & 0x0FFFFFFFu, B.cks));
-            return;
-        }
-        const bool emit = j->codec == 0 ? B.olen > 0 : (j->codec == 1 ? (B.comp || B.clen > 0) : true);
         if (emit) j->msgs.push_back({bt->out.h + R.off, (size_t)R.len});
     }
     if (j->awerr.set) fail(j->awerr.code, j->awerr.msg);
@@ -1287,11 +1370,11 @@ void apply(nx_batcher* b, Batch* bt) {
     char buf[160];
     const nx::bt::AltRes* ares = reinterpret_cast<const nx::bt::AltRes*>(bt->out.h + bt->res_alt);
     for (Job* j : bt->jobs) {
-        if (j->kind >= 2) {
+        if (j->kind == JobKind::AltEnc || j->kind == JobKind::AltDec) {
             apply_alt(bt, j, ares);
             continue;
         }
-        if (j->kind == 0) {
+        if (j->kind == JobKind::SnappyEnc) {
             const EncJob& E = bt->ejob[j->index];
             const int64_t r = res_len[j->index];
             if (r < 0) {  // a slice the encoder failed: the job fails (no framed bytes)
@@ -1384,15 +1467,11 @@ void queue_continuations(nx_batcher* b) {
         const uint8_t* S = d->hist.at(j->s_base);  // the owned segment rewalk() made, from s_base on
         if (!to || !S || enqueue_dec(to, j, S, 0, nullptr) != NX_OK) {
             // cannot queue it: the job fails as a launch failure would (result() reports it)
-            unwalk(j);
-            j->applied = true;
-            j->status = NX_ERR_HIP;
-            j->err = "GPU batch launch failed";
-            d->corrupted = true;
-            trim_hist(d);
+            complete_launch_failed(j, NX_ERR_HIP);
             from->jobs.push_back(j);  // stays owned by its batch
             continue;
         }
+        to->jobs.push_back(j);
         b->cur = to;
         if (live) {
             if (from->live) from->live -= 1;
@@ -1462,6 +1541,31 @@ int32_t maybe_autoflush(nx_batcher* b, Batch* bt) {
     if (!b->flush_bytes || bt != b->cur || bt->st_used + bt->direct_used < b->flush_bytes) return NX_OK;
     b->cur = nullptr;
     return launch(b, bt);
+}
+
+// Every submit starts here (batcher lock held): the workspace its kernels need is held (ws; Count for a
+// job without GPU work), the collecting batch is open (bt) and the job has the next ticket.  The job is
+// the caller's until register_job(): a submit that fails on the way drops it, its ticket number spent.
+// nullptr: NX_ERR_HIP.
+JobPtr open_job(nx_batcher* b, Batch*& bt, nx::WsKind ws, JobKind kind, Codec codec = Codec::FastLz) {
+    if (ws != nx::WsKind::Count && !ensure_held(b, ws)) return nullptr;
+    if (!(bt = collecting(b))) return nullptr;
+    JobPtr j(new Job());
+    j->ticket = b->next_ticket++;
+    j->kind = kind;
+    j->codec = codec;
+    return j;
+}
+
+// ... and ends here: the batch owns the job and its ticket is out.
+int64_t register_job(nx_batcher* b, Batch* bt, JobPtr job) {
+    Job* j = job.release();
+    bt->jobs.push_back(j);
+    bt->live += 1;
+    b->tickets[j->ticket] = {bt, j};
+    const int64_t t = (int64_t)j->ticket;
+    (void)maybe_autoflush(b, bt);  // a failed launch completes the job with the error (result())
+    return t;
 }
 
 }  // namespace
@@ -1536,26 +1640,17 @@ extern "C" int64_t nx_snappy_frame_encoder_submit(nx_snappy_frame_encoder* e, nx
                                                   int32_t in_registered) {
     if (!e || !b || (!in && n)) return NX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(b->mu);
-    if (!ensure_held(b, nx::WsKind::SnappyEnc)) return NX_ERR_HIP;
-    Batch* bt = collecting(b);
-    if (!bt) return NX_ERR_HIP;
-    Job* j = new Job();
-    j->ticket = b->next_ticket++;
-    j->kind = 0;
+    Batch* bt = nullptr;
+    JobPtr j = open_job(b, bt, nx::WsKind::SnappyEnc, JobKind::SnappyEnc);
+    if (!j) return NX_ERR_HIP;
     EncJob E{};
     E.s0 = (uint32_t)bt->esl.size();
-    if (!bt->reserve_out(nx_snappy_frame_max_encoded_length(n), &E.out_off)) {
-        delete j;
-        return NX_ERR_HIP;
-    }
+    if (!bt->reserve_out(nx_snappy_frame_max_encoded_length(n), &E.out_off)) return NX_ERR_HIP;
     if (n) {  // SnappyFrameEncoder.encode (:79-117): !in.isReadable() writes nothing
         E.stream_start = e->started ? 0u : 1u;  // e->started is set below, once the submit cannot fail
         uint64_t base = 0;
         const uint8_t* dsrc = in_registered ? registered_device_ptr(in, n) : nullptr;
-        if (in_registered && !dsrc) {
-            delete j;
-            return NX_ERR_INVALID_ARG;  // not inside an nx_host_register'd range
-        }
+        if (in_registered && !dsrc) return NX_ERR_INVALID_ARG;  // not inside an nx_host_register'd range
         const bool direct = dsrc != nullptr;
         if (direct) {  // DMA'd into the device arena's direct region at flush; adjacent inputs share one copy
             Batch::Direct* last = bt->direct.empty() ? nullptr : &bt->direct.back();
@@ -1569,10 +1664,7 @@ extern "C" int64_t nx_snappy_frame_encoder_submit(nx_snappy_frame_encoder* e, nx
             bt->direct_used = base + n;
         } else {
             uint8_t* st = bt->stage(n, &base);
-            if (!st) {
-                delete j;
-                return NX_ERR_HIP;
-            }
+            if (!st) return NX_ERR_HIP;
             nx::copy_bytes(st, in, n);
         }
         auto add = [&](uint64_t off, uint32_t len, bool comp) {
@@ -1603,24 +1695,18 @@ extern "C" int64_t nx_snappy_frame_encoder_submit(nx_snappy_frame_encoder* e, nx
     E.ns = (uint32_t)bt->esl.size() - E.s0;
     j->index = (uint32_t)bt->ejob.size();
     bt->ejob.push_back(E);
-    bt->jobs.push_back(j);
-    bt->live += 1;
-    b->tickets[j->ticket] = {bt, j};
-    (void)maybe_autoflush(b, bt);  // a failed launch completes the job with the error (result())
-    return (int64_t)j->ticket;
+    return register_job(b, bt, std::move(j));
 }
 
 namespace {
 int64_t decoder_submit(nx_snappy_frame_decoder* d, nx_batcher* b, const uint8_t* in, size_t n, size_t* consumed, bool registered) {
     if (!d || !b || (!in && n) || !consumed) return NX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(b->mu);
-    if (!ensure_held(b, nx::WsKind::DecRecords)) return NX_ERR_HIP;
-    Batch* bt = collecting(b);
-    if (!bt) return NX_ERR_HIP;
-    Job* j = new Job();
-    j->ticket = b->next_ticket++;
-    j->kind = 1;
-    j->dec = d;
+    Batch* bt = nullptr;
+    JobPtr job = open_job(b, bt, nx::WsKind::DecRecords, JobKind::SnappyDec);
+    if (!job) return NX_ERR_HIP;
+    Job* j = job.get();
+    j->bind(d);
     size_t p = 0;  // bytes of `in` consumed
     // the chunk-header walk runs now, so the decoder's started/skip state advances in call order; it
     // is committed below, once the job is queued
@@ -1650,11 +1736,7 @@ int64_t decoder_submit(nx_snappy_frame_decoder* d, nx_batcher* b, const uint8_t*
     const uint8_t* dS = nullptr;
     if (registered && walked && !carried) {
         dS = registered_device_ptr(in, walked);
-        if (!dS) {  // not inside an nx_host_register'd range
-            j->dec = nullptr;
-            delete j;
-            return NX_ERR_INVALID_ARG;
-        }
+        if (!dS) return NX_ERR_INVALID_ARG;  // not inside an nx_host_register'd range
     }
     // a validating decoder stages the walked bytes whole (headers too): the payloads are slices of
     // that copy, and its history references it instead of copying the bytes a second time
@@ -1662,20 +1744,11 @@ int64_t decoder_submit(nx_snappy_frame_decoder* d, nx_batcher* b, const uint8_t*
     if (d->validate && !dS && walked) {
         uint64_t off = 0;
         uint8_t* st = bt->stage(walked, &off);
-        if (!st) {
-            j->dec = nullptr;
-            delete j;
-            return NX_ERR_HIP;
-        }
+        if (!st) return NX_ERR_HIP;
         nx::copy_bytes(st, S, walked);
         staged = (int64_t)off;
     }
-    if (enqueue_dec(bt, j, S, walked, dS, staged) != NX_OK) {
-        j->dec = nullptr;  // no reference taken yet
-        delete j;
-        return NX_ERR_HIP;
-    }
-    d->refs.fetch_add(1);  // released with the job (~Job)
+    if (enqueue_dec(bt, j, S, walked, dS, staged) != NX_OK) return NX_ERR_HIP;
     *consumed = p;
     if (!skipping) {
         d->started = started;
@@ -1701,10 +1774,7 @@ int64_t decoder_submit(nx_snappy_frame_decoder* d, nx_batcher* b, const uint8_t*
             d->parse_pos += walked;
         }
     }
-    bt->live += 1;
-    b->tickets[j->ticket] = {bt, j};
-    (void)maybe_autoflush(b, bt);  // a failed launch completes the job with the error (result())
-    return (int64_t)j->ticket;
+    return register_job(b, bt, std::move(job));
 }
 }  // namespace
 
@@ -1722,81 +1792,60 @@ extern "C" int64_t nx_snappy_frame_decoder_submit_registered(nx_snappy_frame_dec
 namespace {
 using nx::bt::AltPiece;
 
-inline uint64_t align16(uint64_t x) { return (x + 15) & ~15ull; }
-
-// Register job j (its pieces already in bt->apc from p0 on) with an output reservation of `out_need`.
-int64_t queue_alt(nx_batcher* b, Batch* bt, Job* j, uint32_t p0, size_t out_need) {
-    nx::bt::AltJobD J{};
-    J.p0 = p0;
-    J.np = (uint32_t)bt->apc.size() - p0;
-    if (!bt->reserve_out(out_need + 16, &J.out_off)) return NX_ERR_HIP;
-    j->index = (uint32_t)bt->ajob.size();
-    bt->ajob.push_back(J);
-    bt->jobs.push_back(j);
-    bt->live += 1;
-    b->tickets[j->ticket] = {bt, j};
-    (void)maybe_autoflush(b, bt);  // a failed launch completes the job with the error (result())
-    return (int64_t)j->ticket;
-}
-
-// Undo the pieces / list entries a failed submit added (the batch's other jobs stay valid).
+// Where an alt-codec submit found the batch: its pieces and list entries come after.  undo() takes them
+// out again (the batch's other jobs stay valid).
 struct AltMark {
-    size_t apc, fe, le, ze, fd, ld, zd;
+    size_t apc, n[kAltLists];
     uint64_t aslots;
-    explicit AltMark(const Batch* bt)
-        : apc(bt->apc.size()), fe(bt->flz_e.size()), le(bt->lzf_e.size()), ze(bt->lz4_e.size()), fd(bt->flz_d.size()),
-          ld(bt->lzf_d.size()), zd(bt->lz4_d.size()), aslots(bt->aslots) {}
+    explicit AltMark(const Batch* bt) : apc(bt->apc.size()), aslots(bt->aslots) {
+        for (int c = 0; c < kAltLists; ++c) n[c] = bt->alt[c].size();
+    }
     void undo(Batch* bt) const {
-        auto cut = [](Batch::AltList& L, size_t n) {
-            L.off.resize(n);
-            L.slot.resize(n);
-            L.len.resize(n);
-            L.aux.resize(n);
-            if (!L.lim.empty()) L.lim.resize(n);
-        };
         bt->apc.resize(apc);
-        cut(bt->flz_e, fe);
-        cut(bt->lzf_e, le);
-        cut(bt->lz4_e, ze);
-        cut(bt->flz_d, fd);
-        cut(bt->lzf_d, ld);
-        cut(bt->lz4_d, zd);
+        for (int c = 0; c < kAltLists; ++c) bt->alt[c].resize(n[c]);
         bt->aslots = aslots;
     }
 };
 
-uint32_t push_list(Batch::AltList& L, uint64_t off, uint32_t len, uint64_t slot, uint32_t aux, int32_t lim = 0) {
-    L.off.push_back(off);
-    L.len.push_back(len);
-    L.slot.push_back(slot);
-    L.aux.push_back(aux);
-    L.lim.push_back(lim);
-    return (uint32_t)L.off.size() - 1;
+// Register job j, whose pieces are those added since `mark` (nothing else of the submit can fail once
+// they are), with an output reservation of `out_need`.  On failure the batch is as it was at the mark.
+// A decoder job learns its handle `dec` once registered: a failing launch of its own auto-flush fails the
+// job and leaves the decoder as it is.
+int64_t queue_alt(nx_batcher* b, Batch* bt, JobPtr j, const AltMark& mark, size_t out_need, nx_alt_decoder_base* dec = nullptr) {
+    nx::bt::AltJobD J{};
+    J.p0 = (uint32_t)mark.apc;
+    J.np = (uint32_t)(bt->apc.size() - mark.apc);
+    if (!bt->reserve_out(out_need + 16, &J.out_off)) {
+        mark.undo(bt);
+        return NX_ERR_HIP;
+    }
+    j->index = (uint32_t)bt->ajob.size();
+    bt->ajob.push_back(J);
+    Job* const queued = j.get();
+    const int64_t t = register_job(b, bt, std::move(j));
+    if (dec) queued->bind(dec);
+    return t;
 }
 
-Job* new_alt_job(nx_batcher* b, int kind, int codec) {
-    Job* j = new Job();
-    j->ticket = b->next_ticket++;
-    j->kind = kind;
-    j->codec = codec;
-    return j;
+uint32_t push_list(std::vector<AltEntry>& L, uint64_t off, uint32_t len, uint64_t slot, uint32_t aux, int32_t lim = 0) {
+    L.push_back({off, slot, len, aux, lim});
+    return (uint32_t)L.size() - 1;
 }
 
 // Decoder submit, shared by the three codecs: the header walk runs now (the decoder's state advances
 // in call order, as ByteToMessageDecoder would call decode()); the walked bytes are staged; the blocks
 // decode at flush; apply() delivers messages / the first failure in order.
 template <class D, class St, class Walk>
-int64_t alt_decoder_submit(D* d, St& st, nx_batcher* b, const uint8_t* in, size_t n, size_t* consumed, int codec, bool validate,
+int64_t alt_decoder_submit(D* d, St& st, nx_batcher* b, const uint8_t* in, size_t n, size_t* consumed, Codec codec, bool validate,
                            Walk walk) {
     if (!d || !b || (!in && n) || !consumed) return NX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(b->mu);
-    if (!ensure_held(b, nx::WsKind::DecRecords)) return NX_ERR_HIP;
-    Batch* bt = collecting(b);
-    if (!bt) return NX_ERR_HIP;
-    Job* j = new_alt_job(b, 3, codec);
+    Batch* bt = nullptr;
+    JobPtr j = open_job(b, bt, nx::WsKind::DecRecords, JobKind::AltDec, codec);
+    if (!j) return NX_ERR_HIP;
     j->validate = validate;
+    const bool flz = codec == Codec::FastLz;
     const AltMark mark(bt);
-    const uint32_t p0 = (uint32_t)bt->apc.size();
     size_t p = n;
     size_t out_need = 0;
     St ns = st;
@@ -1807,13 +1856,10 @@ int64_t alt_decoder_submit(D* d, St& st, nx_batcher* b, const uint8_t* in, size_
     }
     if (!j->ablk.empty()) {
         // stage from the first block on; FastLZ's decompress() may read on to the end of the cumulation
-        const size_t lo = j->ablk.front().data, hi = codec == 0 ? n : j->ablk.back().end;
+        const size_t lo = j->ablk.front().data, hi = flz ? n : j->ablk.back().end;
         uint64_t off = 0;
         uint8_t* stg = bt->stage(hi - lo, &off);
-        if (!stg) {
-            delete j;
-            return NX_ERR_HIP;
-        }
+        if (!stg) return NX_ERR_HIP;
         nx::copy_bytes(stg, in + lo, hi - lo);
         j->astage = off - lo;  // block b's payload is at staging offset astage + b.data
         for (const nx::af::Blk& k : j->ablk) {
@@ -1821,35 +1867,28 @@ int64_t alt_decoder_submit(D* d, St& st, nx_batcher* b, const uint8_t* in, size_
             P.src = j->astage + k.data;
             P.len = k.clen;
             P.olen = k.olen;
-            const bool cks = validate && k.has_cks;
-            P.pad = cks ? (codec == 0 ? 1u : 2u) : 0u;  // checksum kind: 1 Adler32, 2 XXH32 (assigned at launch)
+            if (validate && k.has_cks) P.cks = flz ? nx::bt::CK_ADLER32 : nx::bt::CK_XXH32;  // its place in the lists: at flush
             if (!k.comp) {
                 P.kind = nx::bt::AK_DEC_RAW;
             } else {
                 P.slot = bt->aslots;
                 bt->aslots += align16(k.olen) + 16;
-                Batch::AltList& L = codec == 0 ? bt->flz_d : (codec == 1 ? bt->lzf_d : bt->lz4_d);
                 // FastLZ: aux = in_avail (readable bytes from the block on), lim = originalLength;
                 // LZF / LZ4: aux = the decoded length
-                P.res = push_list(L, P.src, k.clen, P.slot, codec == 0 ? (uint32_t)(n - k.data) : k.olen, (int32_t)k.olen);
-                P.kind = codec == 0 ? nx::bt::AK_DEC_FLZ : (codec == 1 ? nx::bt::AK_DEC_LZF : nx::bt::AK_DEC_LZ4);
+                P.res = push_list(bt->alt[FLZ_D + (int)codec], P.src, k.clen, P.slot, flz ? (uint32_t)(n - k.data) : k.olen, (int32_t)k.olen);
+                P.kind = flz ? nx::bt::AK_DEC_FLZ : (codec == Codec::Lzf ? nx::bt::AK_DEC_LZF : nx::bt::AK_DEC_LZ4);
             }
             bt->apc.push_back(P);
             out_need += align16(k.olen);
         }
     }
-    const int64_t t = queue_alt(b, bt, j, p0, out_need);
-    if (t < 0) {
-        mark.undo(bt);
-        delete j;
-        return t;
-    }
-    j->adec = d;
-    d->refs.fetch_add(1);  // released with the job (~Job)
+    const bool walk_failed = j->awerr.set;
+    const int64_t t = queue_alt(b, bt, std::move(j), mark, out_need, d);
+    if (t < 0) return t;
     *consumed = p;
     if (!skipping) {
         st = ns;
-        if (j->awerr.set) d->parse_failed = true;  // later submits skip; corrupted once applied
+        if (walk_failed) d->parse_failed = true;  // later submits skip; corrupted once applied
     }
     return t;
 }
@@ -1858,12 +1897,12 @@ int64_t alt_decoder_submit(D* d, St& st, nx_batcher* b, const uint8_t* in, size_
 extern "C" int64_t nx_fastlz_frame_decoder_submit(nx_fastlz_frame_decoder* d, nx_batcher* b, const uint8_t* in, size_t n,
                                                   size_t* consumed) {
     if (!d) return NX_ERR_INVALID_ARG;
-    return alt_decoder_submit(d, d->st, b, in, n, consumed, 0, d->validate, nx::af::flz_walk);
+    return alt_decoder_submit(d, d->st, b, in, n, consumed, Codec::FastLz, d->validate, nx::af::flz_walk);
 }
 
 extern "C" int64_t nx_lzf_decoder_submit(nx_lzf_decoder* d, nx_batcher* b, const uint8_t* in, size_t n, size_t* consumed) {
     if (!d) return NX_ERR_INVALID_ARG;
-    return alt_decoder_submit(d, d->st, b, in, n, consumed, 1, false, nx::af::lzf_walk);
+    return alt_decoder_submit(d, d->st, b, in, n, consumed, Codec::Lzf, false, nx::af::lzf_walk);
 }
 
 extern "C" int64_t nx_lz4_frame_decoder_submit(nx_lz4_frame_decoder* d, nx_batcher* b, const uint8_t* in, size_t n,
@@ -1871,20 +1910,14 @@ extern "C" int64_t nx_lz4_frame_decoder_submit(nx_lz4_frame_decoder* d, nx_batch
     if (!d || !b || (!in && n) || !consumed) return NX_ERR_INVALID_ARG;
     if (d->st.state == 2 && !d->corrupted && !d->parse_failed) {  // FINISHED: everything is skipped (:250-254)
         std::lock_guard<std::mutex> lk(b->mu);
-        Batch* bt = collecting(b);
-        if (!bt) return NX_ERR_HIP;
-        Job* j = new_alt_job(b, 3, 2);
-        const int64_t t = queue_alt(b, bt, j, (uint32_t)bt->apc.size(), 0);
-        if (t < 0) {
-            delete j;
-            return t;
-        }
-        j->adec = d;
-        d->refs.fetch_add(1);
-        *consumed = n;
+        Batch* bt = nullptr;
+        JobPtr j = open_job(b, bt, nx::WsKind::Count, JobKind::AltDec, Codec::Lz4);
+        if (!j) return NX_ERR_HIP;
+        const int64_t t = queue_alt(b, bt, std::move(j), AltMark(bt), 0, d);
+        if (t >= 0) *consumed = n;
         return t;
     }
-    return alt_decoder_submit(d, d->st, b, in, n, consumed, 2, d->validate, nx::af::lz4_walk);
+    return alt_decoder_submit(d, d->st, b, in, n, consumed, Codec::Lz4, d->validate, nx::af::lz4_walk);
 }
 
 // FastLzFrameEncoder.encode(ctx, in, out) over buf[r0 .. r0 + n) as a job (the reader index enters the
@@ -1892,19 +1925,14 @@ extern "C" int64_t nx_lz4_frame_decoder_submit(nx_lz4_frame_decoder* d, nx_batch
 extern "C" int64_t nx_fastlz_frame_encoder_submit(nx_fastlz_frame_encoder* e, nx_batcher* b, const uint8_t* buf, size_t r0, size_t n) {
     if (!e || !b || (!buf && n)) return NX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(b->mu);
-    if (!ensure_held(b, nx::WsKind::FastLzEnc)) return NX_ERR_HIP;
-    Batch* bt = collecting(b);
-    if (!bt) return NX_ERR_HIP;
-    Job* j = new_alt_job(b, 2, 0);
+    Batch* bt = nullptr;
+    JobPtr j = open_job(b, bt, nx::WsKind::FastLzEnc, JobKind::AltEnc, Codec::FastLz);
+    if (!j) return NX_ERR_HIP;
     const AltMark mark(bt);
-    const uint32_t p0 = (uint32_t)bt->apc.size();
     if (n) {
         uint64_t off = 0;
         uint8_t* stg = bt->stage(n, &off);
-        if (!stg) {
-            delete j;
-            return NX_ERR_HIP;
-        }
+        if (!stg) return NX_ERR_HIP;
         nx::copy_bytes(stg, buf + r0, n);
         std::vector<nx::af::FlzPlan> plan;
         nx::af::flz_plan(r0, n, plan);
@@ -1915,17 +1943,12 @@ extern "C" int64_t nx_fastlz_frame_encoder_submit(nx_fastlz_frame_encoder* e, nx
             P.len = q.ilen;
             P.slot = bt->aslots;
             bt->aslots += align16(nx_fastlz_max_compressed_length(q.ilen) + 16);
-            P.res = push_list(bt->flz_e, P.src, q.ilen, P.slot, (uint32_t)e->level, q.lim);
+            P.res = push_list(bt->alt[FLZ_E], P.src, q.ilen, P.slot, (uint32_t)e->level, q.lim);
             P.aux = e->checksum ? 1u : 0u;
             bt->apc.push_back(P);
         }
     }
-    const int64_t t = queue_alt(b, bt, j, p0, nx_fastlz_frame_max_encoded_length(n));
-    if (t < 0) {
-        mark.undo(bt);
-        delete j;
-    }
-    return t;
+    return queue_alt(b, bt, std::move(j), mark, nx_fastlz_frame_max_encoded_length(n));
 }
 
 // LzfEncoder.encode(ctx, in, out) as a job (LzfEncoder.java:169-246): below the compress threshold the
@@ -1933,19 +1956,14 @@ extern "C" int64_t nx_fastlz_frame_encoder_submit(nx_fastlz_frame_encoder* e, nx
 extern "C" int64_t nx_lzf_encoder_submit(nx_lzf_encoder* e, nx_batcher* b, const uint8_t* in, size_t n) {
     if (!e || !b || (!in && n)) return NX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(b->mu);
-    if (!ensure_held(b, nx::WsKind::LzfEnc)) return NX_ERR_HIP;
-    Batch* bt = collecting(b);
-    if (!bt) return NX_ERR_HIP;
-    Job* j = new_alt_job(b, 2, 1);
+    Batch* bt = nullptr;
+    JobPtr j = open_job(b, bt, nx::WsKind::LzfEnc, JobKind::AltEnc, Codec::Lzf);
+    if (!j) return NX_ERR_HIP;
     const AltMark mark(bt);
-    const uint32_t p0 = (uint32_t)bt->apc.size();
     uint64_t off = 0;
     if (n) {
         uint8_t* stg = bt->stage(n, &off);
-        if (!stg) {
-            delete j;
-            return NX_ERR_HIP;
-        }
+        if (!stg) return NX_ERR_HIP;
         nx::copy_bytes(stg, in, n);
     }
     const bool comp = (int64_t)n >= e->threshold;
@@ -1959,19 +1977,14 @@ extern "C" int64_t nx_lzf_encoder_submit(nx_lzf_encoder* e, nx_batcher* b, const
             P.kind = nx::bt::AK_LZF_ENC;
             P.slot = bt->aslots;
             bt->aslots += align16(nx_lzf_max_compressed_length(len) + 16);
-            P.res = push_list(bt->lzf_e, P.src, len, P.slot, 0);
+            P.res = push_list(bt->alt[LZF_E], P.src, len, P.slot, 0);
         } else {
             P.kind = nx::bt::AK_LZF_RAW;
         }
         bt->apc.push_back(P);
         ip += len;
     } while (ip < n);
-    const int64_t t = queue_alt(b, bt, j, p0, nx_lzf_frame_max_encoded_length(n));
-    if (t < 0) {
-        mark.undo(bt);
-        delete j;
-    }
-    return t;
+    return queue_alt(b, bt, std::move(j), mark, nx_lzf_frame_max_encoded_length(n));
 }
 
 // Lz4FrameEncoder as jobs: op 0 = encode(in) (full blocks of the block buffer leave, :231-248), 1 =
@@ -1989,24 +2002,17 @@ extern "C" int64_t nx_lz4_frame_encoder_submit(nx_lz4_frame_encoder* e, nx_batch
         if (r != NX_OK) return r;
     }
     std::lock_guard<std::mutex> lk(b->mu);
-    if (!ensure_held(b, e->high ? nx::WsKind::Lz4HcEnc : nx::WsKind::Lz4Enc)) return NX_ERR_HIP;
-    Batch* bt = collecting(b);
-    if (!bt) return NX_ERR_HIP;
-    Job* j = new_alt_job(b, 2, 2);
+    Batch* bt = nullptr;
+    JobPtr j = open_job(b, bt, e->high ? nx::WsKind::Lz4HcEnc : nx::WsKind::Lz4Enc, JobKind::AltEnc, Codec::Lz4);
+    if (!j) return NX_ERR_HIP;
     const AltMark mark(bt);
-    const uint32_t p0 = (uint32_t)bt->apc.size();
     std::vector<uint8_t> nbuf;  // the block buffer after this job
     size_t out_need = 0;
-    auto fail = [&](int64_t code) {
-        mark.undo(bt);
-        delete j;
-        return code;
-    };
     if (e->finished) {  // pass-through (:233-239); flush / close after close write nothing
         if (n) {
             uint64_t off = 0;
             uint8_t* stg = bt->stage(n, &off);
-            if (!stg) return fail(NX_ERR_HIP);
+            if (!stg) return NX_ERR_HIP;
             nx::copy_bytes(stg, in, n);
             AltPiece P{};
             P.kind = nx::bt::AK_RAW;
@@ -2022,7 +2028,7 @@ extern "C" int64_t nx_lz4_frame_encoder_submit(nx_lz4_frame_encoder* e, nx_batch
         if (full) {
             uint64_t off = 0;
             uint8_t* stg = bt->stage(full, &off);
-            if (!stg) return fail(NX_ERR_HIP);
+            if (!stg) return NX_ERR_HIP;
             const size_t from_buf = have < full ? have : full;
             nx::copy_bytes(stg, e->buf.data(), from_buf);
             if (full > from_buf) nx::copy_bytes(stg + from_buf, in, full - from_buf);
@@ -2035,7 +2041,7 @@ extern "C" int64_t nx_lz4_frame_encoder_submit(nx_lz4_frame_encoder* e, nx_batch
                 P.slot = bt->aslots;
                 const uint64_t cap = nx::af::kLz4Header + nx_lz4_max_compressed_length(len);
                 bt->aslots += align16(cap) + 16;
-                P.res = push_list(bt->lz4_e, P.src, len, P.slot, (uint32_t)e->level | (e->high ? 0x100u : 0u));
+                P.res = push_list(bt->alt[LZ4_E], P.src, len, P.slot, (uint32_t)e->level | (e->high ? 0x100u : 0u));
                 bt->apc.push_back(P);
                 out_need += cap;
             }
@@ -2051,8 +2057,8 @@ extern "C" int64_t nx_lz4_frame_encoder_submit(nx_lz4_frame_encoder* e, nx_batch
             out_need += nx::af::kLz4Header;
         }
     }
-    const int64_t t = queue_alt(b, bt, j, p0, out_need);
-    if (t < 0) return fail(t);
+    const int64_t t = queue_alt(b, bt, std::move(j), mark, out_need);
+    if (t < 0) return t;
     if (!e->finished) e->buf.swap(nbuf);
     if (op == 2) e->finished = true;
     return t;
@@ -2148,16 +2154,8 @@ extern "C" int32_t nx_batcher_set_flush_bytes(nx_batcher* b, size_t bytes) {
 extern "C" int32_t nx_batcher_reserve_arenas(nx_batcher* b, uint32_t nbatches, size_t staging_bytes, size_t out_bytes) {
     if (!b) return NX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(b->mu);
-    std::vector<Batch*> made;
-    while (b->all.size() < nbatches) {
-        Batch* x = new Batch();
-        if (hipEventCreateWithFlags(&x->ev, hipEventDisableTiming) != hipSuccess) {
-            delete x;
-            return NX_ERR_HIP;
-        }
-        x->staging.cnt = x->out.cnt = x->gops.cnt = &b->arena;
-        b->all.push_back(x);
-    }
+    while (b->all.size() < nbatches)
+        if (!new_batch(b)) return NX_ERR_HIP;
     // A batch that holds jobs is left alone: an in-flight batch's arenas are being written, and the
     // results of an applied batch whose tickets are not all released (nx_batcher_result's messages),
     // or the staged bytes a collecting batch's jobs point into, live in its arenas; growing one
