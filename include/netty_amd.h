@@ -231,6 +231,40 @@ int32_t nx_deflate_encode_batch(const uint8_t* in, const uint64_t* in_off, const
                                 const uint64_t* out_off, uint32_t* out_len, int32_t* status, uint32_t n, int32_t level,
                                 void* stream);
 
+/* Replaces Inflater.inflate(...) as JdkZlibDecoder.decode calls it (JdkZlibDecoder.java:254-296) for n
+ * independent raw deflate (RFC 1951) streams, each resumable at symbol granularity: a call takes
+ * whatever slice of the stream the caller has and whatever output room it offers.
+ *   in[in_off[i] .. +in_len[i])  the stream's next bytes (a call looks at the first 128 MiB).
+ *   out + out_off[i]             the stream's window: its first hist_len[i] bytes (<= 32768) are the
+ *                                last bytes the stream already produced, put there by the caller (fewer
+ *                                than 32768 only at the start of a stream); new bytes are appended
+ *                                after them, at most out_cap[i], out_len[i] = their count.  Copies reach
+ *                                back into the history; a distance beyond hist_len + the bytes produced
+ *                                is zlib's "invalid distance too far back".
+ *   state + i * NX_INFLATE_STATE_BYTES  (in/out) what a resume needs: the phase (block header, stored
+ *                                body and its remaining count, Huffman body, done, failed), BFINAL, the
+ *                                bit offset 0..7 into the first unconsumed byte, the current dynamic
+ *                                block's code lengths, the total output.  All zero = start of a stream.
+ *   consumed[i]                  whole bytes the caller may drop; it passes the rest plus new input
+ *                                next time.  At the end of the final block: up to the next byte.
+ * A symbol (literal; length + extra + distance + extra; end of block) is decoded only when all its bits
+ * are present and its output fits out_cap; otherwise the stream stops before it.  A partly received
+ * dynamic header produces nothing and is read again on resume; a stored block's body is copied as far
+ * as input and room go.  With out_cap >= 258 a call makes progress whenever the input allows: what
+ * zlib delivers when fed the same bytes.
+ *   status[i]  NX_OK: the end of the final block was reached (later calls: NX_OK, nothing consumed);
+ *              NX_INFLATE_NEED_INPUT / NX_INFLATE_OUTPUT_FULL: why the stream stopped;
+ *              NX_ERR_INFLATE_*: zlib's error at that site, in zlib's order of checks (the bytes of the
+ *              symbols before it are in place and counted; later calls return the same code);
+ *              NX_ERR_INVALID_ARG: hist_len > 32768 or a state no call wrote.
+ * One wave per stream; no workspace. */
+#define NX_INFLATE_STATE_BYTES 512
+int32_t nx_inflate_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                         uint8_t* out, const uint64_t* out_off, const uint32_t* hist_len,
+                         const uint32_t* out_cap, uint8_t* state,
+                         uint32_t* consumed, uint32_t* out_len, int32_t* status,
+                         uint32_t n, void* stream);
+
 /* Replaces ChunkEncoder.appendEncodedChunk(...) as LZFEncoder.appendEncoded calls it per 65535-byte
  * chunk (LzfEncoder.java:218-221; compress-lzf 1.0.3 ChunkEncoder.tryCompress): writes a complete
  * "ZV" block (compressed if it saves bytes, else non-compressed).  in_len[i] <= 65535.  Each chunk
@@ -441,6 +475,30 @@ void nx_zlib_encoder_free(nx_zlib_encoder* e);
 size_t nx_zlib_max_encoded_length(size_t n);
 int64_t nx_zlib_encoder_encode(nx_zlib_encoder* e, const uint8_t* in, size_t n, uint8_t* out, size_t out_cap);
 int64_t nx_zlib_encoder_close(nx_zlib_encoder* e, uint8_t* out, size_t out_cap);
+
+/* JdkZlibDecoder(wrapper, decompressConcatenated, maxAllocation)  JdkZlibDecoder.java:117-160,211-312
+ * (decode), :316-520 (the GZIP header and footer states), ZlibDecoder.java:49,74-81 (maxAllocation).
+ * wrapper is ZlibWrapper's ordinal 0..3; ZLIB_OR_NONE decides on the first two bytes (looksLikeZlib,
+ * :529-532).  NULL for max_allocation < 0 or a wrapper outside 0..3.  The preset-dictionary
+ * constructors are not offered: a zlib header with FDICT fails as :276-280.
+ * _decode as nx_lzf_decoder_decode: in[0..n) is the cumulation, *consumed the bytes read.  The GZIP
+ * and ZLIB wrappers are parsed on the host; the deflate body runs through nx_inflate_batch (n = 1)
+ * over a device window of 32 KiB of history plus an output chunk, until it needs input, ends or fails;
+ * the running CRC32 / Adler32 of the output comes from nx_crc32_batch / nx_adler32_batch over that
+ * window.  Message boundaries are the handle's own (Java's follow its buffer growth): the
+ * concatenation of the messages is zlib's output for the bytes received so far, and with
+ * max_allocation == 0 nothing is held back across a call.  With max_allocation > 0 a call delivers
+ * one message of at most that many bytes; when its input would produce more it delivers nothing,
+ * the decoder is closed and the call fails with NX_ERR_ZLIB_MAX_ALLOCATION.  A data-format error
+ * returns its NX_ERR_INFLATE_* / NX_ERR_ZLIB_* code with err = "decompression failure" (:302-303; the
+ * bytes decoded before it are delivered, :304-312), a GZIP header or footer error NX_ERR_FRAME_CORRUPT
+ * with the reference's message.  After the end of the stream (and after a failure) input is skipped. */
+typedef struct nx_zlib_decoder nx_zlib_decoder;
+nx_zlib_decoder* nx_zlib_decoder_new(int32_t wrapper, int32_t decompress_concatenated, int32_t max_allocation);
+void nx_zlib_decoder_free(nx_zlib_decoder* d);
+int32_t nx_zlib_decoder_decode(nx_zlib_decoder* d, const uint8_t* in, size_t n, size_t* consumed,
+                               const nx_msg** msgs, size_t* n_msgs, const char** err_msg);
+int32_t nx_zlib_decoder_is_closed(const nx_zlib_decoder* d);
 
 /* Lz4FrameDecoder(validateChecksums)  Lz4FrameDecoder.java:95-261.  Returns NX_OK or the
  * NX_ERR_LZ4_* code of the first failure (err_msg = the reference's message; the decoder is then

@@ -100,6 +100,34 @@
  * continues from consumed[i] on the next call. */
 #define NX_SCAN_LIST_FULL                     1
 
+/* Device inflater (nx_inflate_batch) and JdkZlibDecoder: one code per error site of zlib's inflate()
+ * (zlib 1.2.11 inflate.c, the library java.util.zip.Inflater wraps), with zlib's own text as the
+ * status string.  JdkZlibDecoder.java:302-303 wraps each in DecompressionException("decompression
+ * failure"). */
+#define NX_ERR_INFLATE_BLOCK_TYPE         (-60)  /* "invalid block type" */
+#define NX_ERR_INFLATE_STORED_LENGTHS     (-61)  /* "invalid stored block lengths" */
+#define NX_ERR_INFLATE_TOO_MANY_SYMBOLS   (-62)  /* "too many length or distance symbols" */
+#define NX_ERR_INFLATE_CODE_LENGTHS       (-63)  /* "invalid code lengths set" */
+#define NX_ERR_INFLATE_BIT_LENGTH_REPEAT  (-64)  /* "invalid bit length repeat" */
+#define NX_ERR_INFLATE_MISSING_EOB        (-65)  /* "invalid code -- missing end-of-block" */
+#define NX_ERR_INFLATE_LITLEN_SET         (-66)  /* "invalid literal/lengths set" */
+#define NX_ERR_INFLATE_DIST_SET           (-67)  /* "invalid distances set" */
+#define NX_ERR_INFLATE_LITLEN_CODE        (-68)  /* "invalid literal/length code" */
+#define NX_ERR_INFLATE_DIST_CODE          (-69)  /* "invalid distance code" */
+#define NX_ERR_INFLATE_DISTANCE_TOO_FAR   (-70)  /* "invalid distance too far back" */
+/* The zlib wrapper, checked by the handle on the host as inflate() does with nowrap = false: */
+#define NX_ERR_ZLIB_HEADER_CHECK          (-71)  /* "incorrect header check" */
+#define NX_ERR_ZLIB_DATA_CHECK            (-72)  /* "incorrect data check" (the Adler32 trailer) */
+#define NX_ERR_ZLIB_METHOD                (-73)  /* "unknown compression method" */
+#define NX_ERR_ZLIB_WINDOW                (-74)  /* "invalid window size" */
+/* JdkZlibDecoder.java:276-280: a zlib stream that asks for a preset dictionary when none was given */
+#define NX_ERR_ZLIB_NEED_DICT             (-75)
+/* ZlibDecoder.java:74-81  "Decompression buffer has reached maximum size: %d" */
+#define NX_ERR_ZLIB_MAX_ALLOCATION        (-76)
+/* Not errors: why a stream of nx_inflate_batch stopped before the end of its final block. */
+#define NX_INFLATE_NEED_INPUT             2
+#define NX_INFLATE_OUTPUT_FULL            3
+
 #define NX_ERR_INVALID_ARG                (-100)
 #define NX_ERR_HIP                        (-101)
 #define NX_ERR_NO_DEVICE                  (-102)

@@ -207,6 +207,28 @@ def deflate_encode(inp, in_off, in_len, out, out_off, level: int = 6):
     return out_len, status
 
 
+INFLATE_STATE_BYTES = 512
+INFLATE_NEED_INPUT, INFLATE_OUTPUT_FULL = 2, 3
+
+
+def inflate(inp, in_off, in_len, out, out_off, hist_len, out_cap, state):
+    """Resumable raw inflate per stream (nx_inflate_batch).  Stream i reads inp[in_off[i] : + in_len[i]];
+    its window is out[out_off[i]:], whose first hist_len[i] bytes are its last output and which takes
+    at most out_cap[i] new bytes after them; state is a uint8 tensor of INFLATE_STATE_BYTES per
+    stream (zeros at the start of a stream), updated in place.  Returns (consumed, out_len, status):
+    status 0 at the end of the stream, INFLATE_NEED_INPUT, INFLATE_OUTPUT_FULL or zlib's error."""
+    n = in_len.numel()
+    dev = inp.device
+    assert state.numel() >= n * INFLATE_STATE_BYTES and state.dtype == torch.uint8
+    consumed = torch.empty(n, dtype=torch.int32, device=dev)
+    out_len = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    _chk(_lib.load().nx_inflate_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(hist_len),
+                                      _ptr(out_cap), _ptr(state), _ptr(consumed), _ptr(out_len), _ptr(status), n, _stream()),
+         "nx_inflate_batch")
+    return consumed, out_len, status
+
+
 def lzf_encode(inp, in_off, in_len, out, out_off):
     n = in_len.numel()
     dev = inp.device

@@ -346,6 +346,31 @@ struct nx_zlib_encoder {
     uint64_t total_in = 0;      // deflater.getTotalIn() (:332)
 };
 
+// JdkZlibDecoder (handlers.cpp): the wrapper states on the host, the inflater's on the device.
+struct nx_zlib_decoder {
+    // GzipState (JdkZlibDecoder.java:60-70)
+    enum Gz { HEADER_START, FLG_READ, XLEN_READ, SKIP_FNAME, SKIP_COMMENT, PROCESS_FHCRC, FOOTER_START, HEADER_END };
+    enum Zs { Z_HEAD, Z_BODY, Z_TRAILER };  // what Inflater(nowrap = false) does around the deflate data
+    nx::h::Gpu g;
+    nx::h::MsgList ml;
+    int32_t max_allocation = 0;
+    bool concatenated = false;
+    bool decide = false;    // decideZlibOrNone (:211-220)
+    bool gzip = false;      // crc != null
+    bool zlib = false;      // !nowrap
+    bool finished = false;  // :200-204
+    bool failed = false;    // a data error was raised: what follows is skipped
+    Gz gz = HEADER_START;
+    Zs zs = Z_HEAD;
+    int32_t flags = 0, xlen = -1;  // :73-74
+    uint32_t hcrc = 0;             // the CRC32 of the GZIP header bytes (:356-379)
+    uint32_t crc = 0, adler = 1;   // of the member's output so far
+    uint64_t total_out = 0;        // inflater.getTotalOut()
+    uint32_t hist = 0;             // bytes of history at the end of the current window's first 32 KiB
+    int cur = 0;                   // the current window
+    nx::h::DevBuf win[2], st, par;
+};
+
 // allocateBuffer's maxEncodeSize check (handlers.cpp; the batcher's submit runs it too)
 int32_t nx_lz4_frame_encoder_check_size(nx_lz4_frame_encoder* e, uint64_t remaining, int32_t* target_out = nullptr);
 int32_t nx_lz4_frame_encoder_check_finished(nx_lz4_frame_encoder* e, size_t n, int32_t target);

@@ -40,6 +40,25 @@ extern "C" const char* nx_status_string(int32_t s) {
             return "java.lang.IllegalArgumentException: data chunk shorter than its 4-byte checksum (ByteBuf read past the chunk)";
         case NX_ERR_SNAPPY_UNSKIPPABLE: return "Found reserved unskippable chunk type";
         case NX_ERR_LZ4_MALFORMED: return "Malformed LZ4 input";
+        case NX_ERR_INFLATE_BLOCK_TYPE: return "invalid block type";
+        case NX_ERR_INFLATE_STORED_LENGTHS: return "invalid stored block lengths";
+        case NX_ERR_INFLATE_TOO_MANY_SYMBOLS: return "too many length or distance symbols";
+        case NX_ERR_INFLATE_CODE_LENGTHS: return "invalid code lengths set";
+        case NX_ERR_INFLATE_BIT_LENGTH_REPEAT: return "invalid bit length repeat";
+        case NX_ERR_INFLATE_MISSING_EOB: return "invalid code -- missing end-of-block";
+        case NX_ERR_INFLATE_LITLEN_SET: return "invalid literal/lengths set";
+        case NX_ERR_INFLATE_DIST_SET: return "invalid distances set";
+        case NX_ERR_INFLATE_LITLEN_CODE: return "invalid literal/length code";
+        case NX_ERR_INFLATE_DIST_CODE: return "invalid distance code";
+        case NX_ERR_INFLATE_DISTANCE_TOO_FAR: return "invalid distance too far back";
+        case NX_ERR_ZLIB_HEADER_CHECK: return "incorrect header check";
+        case NX_ERR_ZLIB_DATA_CHECK: return "incorrect data check";
+        case NX_ERR_ZLIB_METHOD: return "unknown compression method";
+        case NX_ERR_ZLIB_WINDOW: return "invalid window size";
+        case NX_ERR_ZLIB_NEED_DICT: return "decompression failure, unable to set dictionary as non was specified";
+        case NX_ERR_ZLIB_MAX_ALLOCATION: return "Decompression buffer has reached maximum size";
+        case NX_INFLATE_NEED_INPUT: return "inflate stopped: more input needed";
+        case NX_INFLATE_OUTPUT_FULL: return "inflate stopped: the next symbol does not fit the output";
         case NX_SCAN_LIST_FULL: return "chunk list full (call again from consumed)";
         case NX_ERR_INVALID_ARG: return "invalid argument";
         case NX_ERR_HIP: return "HIP runtime error";

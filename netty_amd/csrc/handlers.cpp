@@ -1046,3 +1046,338 @@ extern "C" int64_t nx_zlib_encoder_close(nx_zlib_encoder* e, uint8_t* out, size_
     }
     return (int64_t)op;
 }
+
+// ======================================================================= JdkZlibDecoder
+// JdkZlibDecoder.java:117-160 (constructors), :198-314 (decode), :316-520 (the GZIP header and footer),
+// ZlibDecoder.java:49,62-84 (maxAllocation).  The wrappers are a few bytes per stream and are parsed
+// here; the deflate body runs through nx_inflate_batch with n = 1 over a device window (32 KiB of
+// history, then an output chunk), and the output's CRC32 / Adler32 comes from the batch checksum
+// kernels over that window in the same launch sequence.  One call handles what ByteToMessageDecoder.
+// callDecode's loop would hand to decode() in turn.
+
+namespace {
+constexpr uint32_t kZlibHist = 32768;
+constexpr uint32_t kZlibChunk = 1u << 20;  // output bytes per inflate launch (one message each when maxAllocation == 0)
+constexpr int32_t FHCRC = 0x02, FEXTRA = 0x04, FNAME = 0x08, FCOMMENT = 0x10, FRESERVED = 0xE0;  // :48-52
+
+// java.util.zip.CRC32.update over the header bytes (a few bytes per stream)
+uint32_t crc32_host(uint32_t crc, const uint8_t* p, size_t n) {
+    crc = ~crc;
+    for (size_t i = 0; i < n; ++i) {
+        crc ^= p[i];
+        for (int k = 0; k < 8; ++k) crc = (crc >> 1) ^ (nx::kCrc32Poly & (0u - (crc & 1u)));
+    }
+    return ~crc;
+}
+
+struct ZPar {  // the launch's arguments and results, one small copy each way
+    uint64_t in_off, out_off, sum_off;
+    uint32_t in_len, hist_len, out_cap;
+    uint32_t consumed, out_len;
+    int32_t status;
+    uint32_t sum;
+};
+
+enum { kZNeed = 0, kZOk = 1 };  // (< 0: failed, ml.err holds the message)
+
+// readGZIPHeader (:343-433), state for state.  xlen starts at -1 and the two length bytes are OR-ed
+// into it (:393), so it stays -1 and the extra field is never skipped (:398): a header with a
+// non-empty FEXTRA field leaves that field in front of the deflate data, as the reference does.
+int gzip_header(nx_zlib_decoder* d, const uint8_t* in, size_t n, size_t& rd) {
+    using Z = nx_zlib_decoder;
+    auto skip_if_needed = [&](int32_t mask) {  // skipIfNeeded (:442-458)
+        if (d->flags & mask) {
+            for (;;) {
+                if (rd == n) return false;
+                const uint8_t b = in[rd++];
+                d->hcrc = crc32_host(d->hcrc, &b, 1);
+                if (b == 0) break;
+            }
+        }
+        return true;
+    };
+    switch (d->gz) {
+        case Z::HEADER_START: {
+            if (n - rd < 10) return kZNeed;
+            const uint8_t* h = in + rd;
+            if (h[0] != 31) {
+                d->ml.err = "Input is not in the GZIP format";
+                return NX_ERR_FRAME_CORRUPT;
+            }
+            if (h[2] != 8) {  // Deflater.DEFLATED
+                d->ml.err = "Unsupported compression method " + std::to_string((int)h[2]) + " in the GZIP header";
+                return NX_ERR_FRAME_CORRUPT;
+            }
+            d->flags = h[3];
+            if (d->flags & FRESERVED) {
+                d->ml.err = "Reserved flags are set in the GZIP header";
+                return NX_ERR_FRAME_CORRUPT;
+            }
+            d->hcrc = crc32_host(d->hcrc, h, 10);  // magic, method, flags, mtime, extra flags, operating system
+            rd += 10;
+            d->gz = Z::FLG_READ;
+        }  // fall through
+        case Z::FLG_READ:
+            if (d->flags & FEXTRA) {
+                if (n - rd < 2) return kZNeed;
+                const int32_t xlen1 = in[rd], xlen2 = in[rd + 1];
+                d->hcrc = crc32_host(d->hcrc, in + rd, 2);
+                rd += 2;
+                d->xlen |= xlen1 << 8 | xlen2;
+            }
+            d->gz = Z::XLEN_READ;
+            // fall through
+        case Z::XLEN_READ:
+            if (d->xlen != -1) {  // (never: see above)
+                if (n - rd < (size_t)d->xlen) return kZNeed;
+                d->hcrc = crc32_host(d->hcrc, in + rd, (size_t)d->xlen);
+                rd += (size_t)d->xlen;
+            }
+            d->gz = Z::SKIP_FNAME;
+            // fall through
+        case Z::SKIP_FNAME:
+            if (!skip_if_needed(FNAME)) return kZNeed;
+            d->gz = Z::SKIP_COMMENT;
+            // fall through
+        case Z::SKIP_COMMENT:
+            if (!skip_if_needed(FCOMMENT)) return kZNeed;
+            d->gz = Z::PROCESS_FHCRC;
+            // fall through
+        case Z::PROCESS_FHCRC:
+            if (d->flags & FHCRC) {  // verifyCrc16 (:506-520)
+                if (n - rd < 2) return kZNeed;
+                const int32_t want = in[rd] | (in[rd + 1] << 8), got = (int32_t)(d->hcrc & 0xFFFFu);
+                rd += 2;
+                if (want != got) {
+                    d->ml.err = "CRC16 value mismatch. Expected: " + std::to_string(want) + ", Got: " + std::to_string(got);
+                    return NX_ERR_FRAME_CORRUPT;
+                }
+            }
+            d->hcrc = 0;  // crc.reset()
+            d->crc = 0;
+            d->gz = Z::HEADER_END;
+            // fall through
+        default:
+            return kZOk;
+    }
+}
+
+// readGZIPFooter (:467-483) with verifyCrc (:492-504): all 8 bytes first, then the two checks with
+// Java's formatting (the CRC as unsigned longs, the lengths as ints).
+int gzip_footer(nx_zlib_decoder* d, const uint8_t* in, size_t n, size_t& rd) {
+    if (n - rd < 8) return kZNeed;
+    const uint32_t want_crc = le32(in + rd);
+    const int32_t want_len = (int32_t)le32(in + rd + 4), got_len = (int32_t)(uint32_t)d->total_out;
+    if (want_crc != d->crc) {
+        rd += 4;
+        d->ml.err = "CRC value mismatch. Expected: " + std::to_string((unsigned long long)want_crc) +
+                    ", Got: " + std::to_string((unsigned long long)d->crc);
+        return NX_ERR_FRAME_CORRUPT;
+    }
+    rd += 8;
+    if (want_len != got_len) {
+        d->ml.err = "Number of bytes mismatch. Expected: " + std::to_string(want_len) + ", Got: " + std::to_string(got_len);
+        return NX_ERR_FRAME_CORRUPT;
+    }
+    return kZOk;
+}
+
+// inflater.reset() (:321) and crc.reset(): a new member starts with an empty window
+bool zlib_reset_member(nx_zlib_decoder* d) {
+    d->hist = 0;
+    d->crc = 0;
+    d->adler = 1;
+    d->total_out = 0;
+    return hipMemsetAsync(d->st.p, 0, NX_INFLATE_STATE_BYTES, d->g.s) == hipSuccess;
+}
+}  // namespace
+
+extern "C" nx_zlib_decoder* nx_zlib_decoder_new(int32_t wrapper, int32_t decompress_concatenated, int32_t max_allocation) {
+    if (wrapper < 0 || wrapper > 3 || max_allocation < 0) return nullptr;  // checkPositiveOrZero (ZlibDecoder.java:49)
+    auto* d = new nx_zlib_decoder();
+    if (!d->g.ok || !d->win[0].ensure(kZlibHist + kZlibChunk) || !d->win[1].ensure(kZlibHist + kZlibChunk) ||
+        !d->st.ensure(NX_INFLATE_STATE_BYTES) || !d->par.ensure(sizeof(ZPar)) || !zlib_reset_member(d) || !d->g.sync()) {
+        delete d;
+        return nullptr;
+    }
+    d->max_allocation = max_allocation;
+    d->concatenated = decompress_concatenated != 0;
+    d->gzip = wrapper == 1;    // :141-159
+    d->zlib = wrapper == 0;
+    d->decide = wrapper == 3;
+    return d;
+}
+extern "C" void nx_zlib_decoder_free(nx_zlib_decoder* d) { delete d; }
+extern "C" int32_t nx_zlib_decoder_is_closed(const nx_zlib_decoder* d) { return d && d->finished ? 1 : 0; }
+
+extern "C" int32_t nx_zlib_decoder_decode(nx_zlib_decoder* d, const uint8_t* in, size_t n, size_t* consumed, const nx_msg** msgs,
+                                          size_t* n_msgs, const char** err_msg) {
+    const nx::NoGrowScope no_grow;
+    if (!d || (!in && n) || !consumed || !msgs || !n_msgs) return NX_ERR_INVALID_ARG;
+    using Z = nx_zlib_decoder;
+    MsgList& ml = d->ml;
+    ml.clear();
+    Gpu& g = d->g;
+    size_t rd = 0;
+    std::vector<uint8_t> acc;  // maxAllocation > 0: the call's one message
+    auto finish = [&](int32_t r) {
+        if (!acc.empty()) ml.owned.push_back(std::move(acc));
+        for (auto& o : ml.owned) ml.msgs.push_back({o.data(), o.size()});
+        *consumed = rd;
+        *msgs = ml.msgs.data();
+        *n_msgs = ml.msgs.size();
+        if (err_msg) *err_msg = ml.err.empty() ? nullptr : ml.err.c_str();
+        return r;
+    };
+    auto fail = [&](int32_t code) {  // the exception leaves decode(): what was decoded is forwarded (:304-312)
+        d->failed = true;
+        rd = n;
+        return finish(code);
+    };
+    if (d->finished || d->failed) {  // in.skipBytes(in.readableBytes()) (:200-204)
+        rd = n;
+        return finish(NX_OK);
+    }
+    bool uploaded = false;  // the cumulation is copied to the device once, when a body needs it
+    for (;;) {
+        if (rd == n) break;  // :206-209
+        if (d->decide) {  // :211-220
+            if (n - rd < 2) break;
+            const int32_t cmf_flg = (int16_t)be16(in + rd);  // looksLikeZlib on a Java short (:529-532)
+            d->zlib = (cmf_flg & 0x7800) == 0x7800 && cmf_flg % 31 == 0;
+            d->decide = false;
+        }
+        if (d->gzip && d->gz != Z::HEADER_END) {  // :222-242
+            if (d->gz == Z::FOOTER_START) {
+                const int r = gzip_footer(d, in, n, rd);
+                if (r == kZNeed) break;
+                if (r < 0) return fail(r);
+                if (!d->concatenated) {  // handleGzipFooter (:316-328); the next decode() skips the rest
+                    d->finished = true;
+                    rd = n;
+                    break;
+                }
+                if (!zlib_reset_member(d)) return finish(NX_ERR_HIP);
+                d->gz = Z::HEADER_START;
+            }
+            const int r = gzip_header(d, in, n, rd);
+            if (r == kZNeed) break;
+            if (r < 0) return fail(r);
+            continue;
+        }
+        if (d->zlib && d->zs != Z::Z_BODY) {  // inflate()'s HEAD / DICTID / CHECK states (zlib inflate.c)
+            if (d->zs == Z::Z_HEAD) {
+                if (n - rd < 2) break;
+                const uint32_t cmf = in[rd], flg = in[rd + 1];
+                int32_t code = NX_OK;
+                if (((cmf << 8) + flg) % 31) code = NX_ERR_ZLIB_HEADER_CHECK;
+                else if ((cmf & 15u) != 8u) code = NX_ERR_ZLIB_METHOD;
+                else if ((cmf >> 4) + 8u > 15u) code = NX_ERR_ZLIB_WINDOW;
+                if (code == NX_OK && (flg & 0x20u)) {  // FDICT: zlib reads the dictionary id, then asks for it (:276-280)
+                    if (n - rd < 6) break;
+                    ml.err = "decompression failure, unable to set dictionary as non was specified";
+                    return fail(NX_ERR_ZLIB_NEED_DICT);
+                }
+                if (code != NX_OK) {
+                    ml.err = "decompression failure";
+                    return fail(code);
+                }
+                rd += 2;
+                d->zs = Z::Z_BODY;
+                continue;
+            }
+            if (n - rd < 4) break;  // the Adler32 trailer, most significant byte first
+            if (be32(in + rd) != d->adler) {
+                ml.err = "decompression failure";
+                return fail(NX_ERR_ZLIB_DATA_CHECK);
+            }
+            rd += 4;
+            d->finished = true;  // inflater.finished() (:284-286)
+            rd = n;
+            break;
+        }
+        // the deflate body: inflate until the input runs out, the stream ends or an error (:257-294)
+        if (!uploaded) {
+            if (!g.din.ensure(n) || !g.h2d(g.din.p, in, n)) return finish(NX_ERR_HIP);
+            uploaded = true;
+        }
+        bool ended = false;
+        for (;;) {
+            uint8_t* W = d->win[d->cur].as<uint8_t>();
+            ZPar p{};
+            p.in_off = rd;
+            p.in_len = (uint32_t)(n - rd < 0x7FFFFFFFu ? n - rd : 0x7FFFFFFFu);
+            p.out_off = kZlibHist - d->hist;
+            p.hist_len = d->hist;
+            p.out_cap = kZlibChunk;
+            p.sum_off = kZlibHist;
+            uint8_t* P = d->par.as<uint8_t>();
+            if (!g.h2d(P, &p, offsetof(ZPar, consumed))) return finish(NX_ERR_HIP);
+            int32_t r = nx_inflate_batch(g.din.as<uint8_t>(), (const uint64_t*)(P + offsetof(ZPar, in_off)),
+                                         (const uint32_t*)(P + offsetof(ZPar, in_len)), W,
+                                         (const uint64_t*)(P + offsetof(ZPar, out_off)),
+                                         (const uint32_t*)(P + offsetof(ZPar, hist_len)),
+                                         (const uint32_t*)(P + offsetof(ZPar, out_cap)), d->st.as<uint8_t>(),
+                                         (uint32_t*)(P + offsetof(ZPar, consumed)), (uint32_t*)(P + offsetof(ZPar, out_len)),
+                                         (int32_t*)(P + offsetof(ZPar, status)), 1, g.s);
+            if (r != NX_OK) return finish(r);
+            if (d->gzip || d->zlib) {  // the checksum of what this launch produced (crc.update, :265-267)
+                auto sum = d->gzip ? nx_crc32_batch : nx_adler32_batch;
+                r = sum(W, (const uint64_t*)(P + offsetof(ZPar, sum_off)), (const uint32_t*)(P + offsetof(ZPar, out_len)),
+                        (uint32_t*)(P + offsetof(ZPar, sum)), 1, g.s);
+                if (r != NX_OK) return finish(r);
+            }
+            if (!g.d2h(&p.consumed, P + offsetof(ZPar, consumed), sizeof(ZPar) - offsetof(ZPar, consumed)) || !g.sync())
+                return finish(NX_ERR_HIP);
+            if (p.status == NX_ERR_INVALID_ARG || p.status == NX_ERR_INTERNAL) return finish(p.status);
+            const uint32_t m = p.out_len;
+            rd += p.consumed;
+            if (m) {
+                if (d->max_allocation > 0) {
+                    if (acc.size() + m > (size_t)d->max_allocation) {  // prepareDecompressBuffer (ZlibDecoder.java:74-81)
+                        acc.clear();
+                        ml.owned.clear();
+                        d->finished = true;  // decompressionBufferExhausted (:331-333)
+                        ml.err = "Decompression buffer has reached maximum size: " + std::to_string(d->max_allocation);
+                        rd = n;
+                        return finish(NX_ERR_ZLIB_MAX_ALLOCATION);
+                    }
+                    const size_t at = acc.size();
+                    acc.resize(at + m);
+                    if (!g.d2h(acc.data() + at, W + kZlibHist, m)) return finish(NX_ERR_HIP);
+                } else {
+                    ml.owned.emplace_back(m);
+                    if (!g.d2h(ml.owned.back().data(), W + kZlibHist, m)) return finish(NX_ERR_HIP);
+                }
+                if (d->gzip) d->crc = nx_crc32_combine(d->crc, p.sum, m);
+                else if (d->zlib) d->adler = nx_adler32_combine(d->adler, p.sum, m);
+                d->total_out += m;
+                // the last 32 KiB of the stream's output become the other window's history
+                const uint32_t h = d->hist + m < kZlibHist ? d->hist + m : kZlibHist;
+                if (hipMemcpyAsync(d->win[d->cur ^ 1].as<uint8_t>() + kZlibHist - h, W + kZlibHist + m - h, h,
+                                   hipMemcpyDeviceToDevice, g.s) != hipSuccess)
+                    return finish(NX_ERR_HIP);
+                d->hist = h;
+                d->cur ^= 1;
+                if (!g.sync()) return finish(NX_ERR_HIP);
+            }
+            if (p.status < 0) {  // DataFormatException -> DecompressionException("decompression failure") (:302-303)
+                ml.err = "decompression failure";
+                return fail(p.status);
+            }
+            if (p.status == NX_OK) ended = true;
+            if (p.status != NX_INFLATE_OUTPUT_FULL) break;
+        }
+        if (!ended) break;  // the inflater needs input
+        if (d->gzip) {
+            d->gz = Z::FOOTER_START;  // :298-301
+        } else if (d->zlib) {
+            d->zs = Z::Z_TRAILER;
+        } else {
+            d->finished = true;  // :284-286
+            rd = n;
+            break;
+        }
+    }
+    return finish(NX_OK);
+}

@@ -340,6 +340,31 @@ class JdkZlibEncoder(_Encoder):
         return self._ret(_lib.load().nx_zlib_encoder_close(self._h, out, 32), out)
 
 
+class JdkZlibDecoder(_Decoder):
+    """JdkZlibDecoder.java:117-160,198-314 over the GPU inflater (nx_zlib_decoder_*): ZLIB, GZIP (every
+    header field, optionally concatenated members), NONE and ZLIB_OR_NONE, maxAllocation as
+    ZlibDecoder.java:49,62-84.  The concatenation of the messages is zlib's output for the bytes
+    received so far (the boundaries are this decoder's own); with max_allocation > 0 a read delivers
+    one message of at most that many bytes or fails with "Decompression buffer has reached maximum
+    size".  A data error raises DecompressionException("decompression failure") with the inflater's
+    code as .status; the preset-dictionary constructors are not offered."""
+
+    _free = "nx_zlib_decoder_free"
+    _decode_fn = "nx_zlib_decoder_decode"
+
+    def __init__(self, wrapper: ZlibWrapper = ZlibWrapper.ZLIB, decompress_concatenated: bool = False, max_allocation: int = 0):
+        super().__init__()
+        if max_allocation < 0:  # ObjectUtil.checkPositiveOrZero (ZlibDecoder.java:49)
+            raise ValueError(f"maxAllocation : {max_allocation} (expected: >= 0)")
+        self.wrapper = ZlibWrapper(wrapper)
+        self._h = _new(_lib.load().nx_zlib_decoder_new(int(self.wrapper), int(bool(decompress_concatenated)), int(max_allocation)),
+                       "JdkZlibDecoder")
+
+    def is_closed(self) -> bool:
+        """ZlibDecoder.isClosed(): the end of the compressed stream has been reached"""
+        return bool(_lib.load().nx_zlib_decoder_is_closed(self._h))
+
+
 class Lz4FrameDecoder(_Decoder):
     """Lz4FrameDecoder.java:36-277 (validateChecksums default false, :100-102)."""
 
