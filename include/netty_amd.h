@@ -599,6 +599,43 @@ int64_t nx_lzf_decoder_submit(nx_lzf_decoder* d, nx_batcher* b, const uint8_t* i
 int64_t nx_lz4_frame_decoder_submit(nx_lz4_frame_decoder* d, nx_batcher* b, const uint8_t* in, size_t n,
                                     size_t* consumed);
 
+/* JdkZlibEncoder and JdkZlibDecoder as batcher jobs.  Both return a ticket or a negative status,
+ * never touch the GPU and never block; the bytes are copied at submit and nothing is computed over
+ * them on the host.  A job holds a reference to its handle: the handle may be freed while its jobs
+ * are queued or in flight.  A flush issues a constant number of launches for any number of zlib jobs:
+ * every encoder slice of a level class is one entry of one nx_deflate_encode_batch launch (one for
+ * level 0, one for the matcher levels), every decoder job one stream of ONE nx_inflate_batch call.
+ *
+ * nx_zlib_encoder_submit: op 0 = encode(in); op 2 = encode(in) then finishEncode (close); the
+ *   numbering is nx_lz4_frame_encoder_submit's, op 1 (and anything else) is NX_ERR_INVALID_ARG.  The
+ *   result of a ticket is byte for byte what nx_zlib_encoder_encode (op 2: followed by
+ *   nx_zlib_encoder_close, concatenated) returns for the same call sequence, as one message; after a
+ *   close a job passes its bytes through.  The header, total-in and the closed state advance at
+ *   submit; the running CRC32 / Adler32 is folded when the job is applied, in flush order, and a
+ *   close's trailer is written then.  While a handle has unapplied jobs, nx_zlib_encoder_encode and
+ *   nx_zlib_encoder_close return NX_ERR_INVALID_ARG; with none pending they work as before and
+ *   continue the same stream.  The first submit holds NX_WS_DEFLATE_ENC for the batcher (or
+ *   nx_batcher_reserve with that bit, up front).
+ *
+ * nx_zlib_decoder_submit: *consumed = n always: the handle keeps the bytes its jobs have not used
+ *   yet (as Inflater.setInput takes everything readable).  A decoder that has been submitted to a
+ *   batcher stays on that batcher: afterwards nx_zlib_decoder_decode, and a submit to another
+ *   batcher, return NX_ERR_INVALID_ARG.  Feed the same slices in the same order to a fresh handle's
+ *   nx_zlib_decoder_decode: the messages of ticket k, concatenated, are those of the k-th call,
+ *   concatenated (the message boundaries are the decoder's own), and so are the status, the error
+ *   text, the messages delivered before a failure and nx_zlib_decoder_is_closed once the ticket is
+ *   complete; after a failure later tickets deliver nothing with NX_OK; max_allocation > 0 gives one
+ *   message of at most that size, or NX_ERR_ZLIB_MAX_ALLOCATION, per ticket.
+ *   One job of a decoder is in flight at a time.  A job parses wrapper bytes on the host and puts one
+ *   body step into the collecting batch; when the step ends with its output room full, or the stream
+ *   ends with input left (a footer, a further member), the same ticket continues in the next batch,
+ *   launched by the next poll / wait, and completes when the input is used up, the stream is finished
+ *   or the decoder has failed.  A submit on a decoder with an unapplied job is held with its bytes
+ *   and enters a batch when the earlier job has been applied: two submits of one decoder before a
+ *   flush take two flush rounds (the batcher's value is across channels, not within one). */
+int64_t nx_zlib_encoder_submit(nx_zlib_encoder* e, nx_batcher* b, const uint8_t* in, size_t n, int32_t op);
+int64_t nx_zlib_decoder_submit(nx_zlib_decoder* d, nx_batcher* b, const uint8_t* in, size_t n, size_t* consumed);
+
 #ifdef __cplusplus
 }
 #endif

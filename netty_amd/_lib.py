@@ -91,6 +91,8 @@ _SIGS = {
     "nx_fastlz_frame_decoder_submit": (i64, [vp, vp, vp, sz, C.POINTER(sz)]),
     "nx_lzf_decoder_submit": (i64, [vp, vp, vp, sz, C.POINTER(sz)]),
     "nx_lz4_frame_decoder_submit": (i64, [vp, vp, vp, sz, C.POINTER(sz)]),
+    "nx_zlib_encoder_submit": (i64, [vp, vp, vp, sz, i32]),
+    "nx_zlib_decoder_submit": (i64, [vp, vp, vp, sz, C.POINTER(sz)]),
     # host handler layer
     "nx_snappy_frame_encoder_new": (vp, [i32]),
     "nx_snappy_frame_encoder_free": (None, [vp]),

@@ -344,7 +344,15 @@ struct nx_zlib_encoder {
     uint32_t crc = 0;           // GZIP: CRC32 of everything encoded (:58,262-264)
     uint32_t adler = 1;         // ZLIB: the Deflater's Adler32
     uint64_t total_in = 0;      // deflater.getTotalIn() (:332)
+    // Batcher: write_header, finished and total_in advance at submit; crc / adler are folded when a job is
+    // applied, in flush order, so the synchronous calls are refused while jobs are unapplied (pending).  A
+    // job holds a reference: nx_zlib_encoder_free drops the owner's.
+    std::atomic<int> pending{0};
+    std::atomic<int> refs{1};
 };
+inline void nx_zlib_encoder_unref(nx_zlib_encoder* e) {
+    if (e && e->refs.fetch_sub(1) == 1) delete e;
+}
 
 // JdkZlibDecoder (handlers.cpp): the wrapper states on the host, the inflater's on the device.
 struct nx_zlib_decoder {
@@ -369,7 +377,44 @@ struct nx_zlib_decoder {
     uint32_t hist = 0;             // bytes of history at the end of the current window's first 32 KiB
     int cur = 0;                   // the current window
     nx::h::DevBuf win[2], st, par;
+    bool st_fresh = false;         // a member reset since the last body step: that step starts from the all-zero state
+    // Batcher (batcher.cpp): the batcher this decoder's jobs run on, once one was submitted (the synchronous
+    // decode is refused from then on); the bytes its jobs have not used yet; the owner's reference plus one
+    // per job.
+    std::atomic<nx_batcher*> owner{nullptr};
+    std::vector<uint8_t> pend;
+    std::atomic<int> refs{1};
 };
+inline void nx_zlib_decoder_unref(nx_zlib_decoder* d) {
+    if (d && d->refs.fetch_sub(1) == 1) delete d;
+}
+
+// JdkZlibDecoder.decode (:198-314) as steps (handlers.cpp), driven by nx_zlib_decoder_decode and by the
+// batcher's decoder jobs alike.
+namespace nx {
+namespace zl {
+constexpr uint32_t kHist = 32768;  // the inflater's window
+struct Call {  // one decode() call, or one ticket
+    const uint8_t* in = nullptr;  // the cumulation
+    size_t n = 0, rd = 0;         // its length; the bytes used so far
+    std::vector<uint8_t> acc;     // maxAllocation > 0: the call's one message
+    std::string err;
+};
+struct BodyIo {  // what the two drivers do differently with an inflate launch's result
+    virtual bool take(uint8_t* dst, uint32_t m) = 0;  // its m output bytes: into dst, or (nullptr) a message of their own
+    virtual void drop() = 0;                           // forget the call's messages (maxAllocation exceeded)
+    virtual bool carry(uint32_t h, uint32_t m) = 0;    // the last h bytes of [history | output] become the other window's history
+    virtual ~BodyIo() = default;
+};
+// What comes next: kStop = the call is over (input used up, stream finished, or skipping); kBody = an
+// inflate launch over in[rd, n); kWrapper = wrapper_step again; < 0 = the call failed with that status
+// (err set); <= kHalt: the launch itself failed with status (value - kHalt), the decoder is as it was.
+enum : int { kStop = 0, kBody = 1, kWrapper = 2, kHalt = -1000000 };
+int wrapper_step(nx_zlib_decoder* d, Call& c);
+int body_result(nx_zlib_decoder* d, Call& c, uint32_t consumed, uint32_t out_len, int32_t status, uint32_t sum, BodyIo& io);
+size_t write_header(const nx_zlib_encoder* e, uint8_t* out);  // JdkZlibEncoder's header bytes (at most 10)
+}  // namespace zl
+}  // namespace nx
 
 // allocateBuffer's maxEncodeSize check (handlers.cpp; the batcher's submit runs it too)
 int32_t nx_lz4_frame_encoder_check_size(nx_lz4_frame_encoder* e, uint64_t remaining, int32_t* target_out = nullptr);

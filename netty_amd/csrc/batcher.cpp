@@ -52,7 +52,9 @@
 #include "handles.hpp"
 #include "alt_frames.hpp"
 #include "nx_common.hpp"
+#include "wave_copy.hpp"
 #include "workspace.hpp"
+#include "zlib_jobs.hpp"
 
 namespace nx {
 namespace bt {
@@ -95,9 +97,6 @@ struct DecRes {  // per action, written by k_dec_finish
     uint32_t cons;   // compressed: input bytes consumed
 };
 
-// Copy n bytes device -> mapped host with the whole wave: 16-byte stores at 16-byte-aligned
-// destinations (one PCIe write per lane), bytes at the ragged ends.
-//
 // The kernels that move bytes across PCIe (k_gather_host reads mapped host pages, the finish kernels
 // write the results into them) run on a capped grid, kPcieBlocks workgroups looping over the jobs:
 // their speed is the link's, not the CUs', and a grid of one wave per job held every CU for the
@@ -111,25 +110,6 @@ constexpr uint64_t kDmaOutMin = 64ull << 20;  // place(): result arenas at least
 constexpr uint64_t kGatherStageMax = 8ull << 20;  // transfer_in(): staging arenas up to this size move by k_gather_host
 constexpr uint64_t kGatherPiece = 64ull << 10;    // ... in ops of this many bytes
 inline dim3 pcie_grid(uint32_t jobs) { return dim3(std::min((jobs + 3u) / 4u, kPcieBlocks)); }
-__device__ void wave_copy(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, uint32_t n, int lane) {
-    typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-    typedef v4 __attribute__((aligned(1))) v4u;
-    const uint32_t head = (uint32_t)((16u - ((uintptr_t)dst & 15u)) & 15u) < n ? (uint32_t)((16u - ((uintptr_t)dst & 15u)) & 15u) : n;
-    if ((uint32_t)lane < head) dst[lane] = src[lane];
-    const uint32_t nv = (n - head) >> 4;
-    uint32_t i = lane;
-    for (; i + 192u < nv; i += 256u) {  // 4 KiB per wave per step: four loads in flight, then four stores
-        v4 x[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) x[u] = *reinterpret_cast<const v4u*>(src + head + 16u * (i + 64u * u));
-#pragma unroll
-        for (int u = 0; u < 4; ++u) *reinterpret_cast<v4*>(dst + head + 16u * (i + 64u * u)) = x[u];
-    }
-    for (; i < nv; i += 64u) *reinterpret_cast<v4*>(dst + head + 16u * i) = *reinterpret_cast<const v4u*>(src + head + 16u * i);
-    const uint32_t t = head + (nv << 4);
-    if (t + (uint32_t)lane < n) dst[t + lane] = src[t + lane];
-}
-
 // Registered host inputs -> the device input arena: one wave per input range, 16-byte loads from the
 // mapped host pages (one launch instead of one DMA command per pooled-buffer message).
 struct GatherOp {
@@ -282,6 +262,9 @@ enum : uint32_t {
     AK_DEC_LZF,      // an LZF block decoded into its slot
     AK_DEC_LZ4,      // an LZ4 block decoded into its slot
     AK_DEC_RAW,      // a non-compressed block: its payload (input)
+    AK_DFL_ENC,      // a JdkZlibEncoder slice deflated into its slot (aux: its checksum, as for decoder pieces)
+    AK_CONST,        // len <= 16 literal bytes held in src (the first 8, little-endian) and slot: JdkZlibEncoder's
+                     // header, and its final block with the trailer's place (the host writes the trailer at apply)
 };
 struct AltPiece {
     uint64_t src;   // input arena offset of the raw bytes / payload
@@ -292,9 +275,9 @@ struct AltPiece {
     uint32_t res;   // index into the codec's result arrays
     uint32_t aux;   // AK_FLZ_ENC: bit 0 = with Adler32; AK_LZ4_END: compression level; decoder pieces with a
                     // checksum: 1 + its index in AltArrays::dcks (assigned at flush)
-    uint32_t cks;   // decoder pieces, host only: the checksum to compute (CK_NONE / CK_ADLER32 / CK_XXH32)
+    uint32_t cks;   // decoder and deflate pieces, host only: the checksum to compute (CK_*)
 };
-enum : uint32_t { CK_NONE = 0, CK_ADLER32 = 1, CK_XXH32 = 2 };
+enum : uint32_t { CK_NONE = 0, CK_ADLER32 = 1, CK_XXH32 = 2, CK_CRC32 = 3 };
 struct AltJobD {
     uint64_t out_off;  // in the mapped output arena
     uint32_t p0, np;   // pieces
@@ -317,7 +300,9 @@ struct AltArrays {  // the flush's codec result arrays (device)
     const int32_t* dflz_r;
     const int32_t* dlzf_st;
     const int32_t* dlz4_st;
-    const uint32_t* dcks;  // decoder checksums, indexed by AltPiece::aux - 1
+    const uint32_t* dcks;  // decoder and deflate piece checksums, indexed by AltPiece::aux - 1
+    const uint32_t* dfl_olen;  // deflate slices: the stored-only launch's, then the matcher launch's
+    const int32_t* dfl_st;
 };
 
 __global__ void __launch_bounds__(256) k_alt_finish(const uint8_t* __restrict__ din, const uint8_t* __restrict__ aslots,
@@ -423,6 +408,20 @@ __global__ void __launch_bounds__(256) k_alt_finish(const uint8_t* __restrict__ 
                     r.len = P.olen;
                     break;
                 }
+                case AK_DFL_ENC: {
+                    const int32_t st = R.dfl_st[P.res];
+                    if (st != NX_OK) {
+                        r.status = st;
+                        break;
+                    }
+                    r.len = R.dfl_olen[P.res];
+                    wave_copy(o, aslots + P.slot, r.len, lane);
+                    break;
+                }
+                case AK_CONST:
+                    if ((uint32_t)lane < P.len && lane < 16) o[lane] = (uint8_t)((lane < 8 ? P.src : P.slot) >> (8 * (lane & 7)));
+                    r.len = P.len < 16u ? P.len : 16u;
+                    break;
                 default:
                     r.status = NX_ERR_INTERNAL;
             }
@@ -486,9 +485,10 @@ struct Pinned {  // hipHostMalloc'd, mapped into the device address space; grows
 
 inline uint64_t align16(uint64_t x) { return (x + 15) & ~15ull; }
 
-enum class JobKind { SnappyEnc, SnappyDec, AltEnc, AltDec };
+enum class JobKind { SnappyEnc, SnappyDec, AltEnc, AltDec, ZlibEnc, ZlibDec };
 enum class Codec { FastLz, Lzf, Lz4 };  // of an alt-codec job
 
+struct Batch;
 struct Job {
     uint64_t ticket = 0;
     JobKind kind = JobKind::SnappyEnc;
@@ -514,6 +514,19 @@ struct Job {
     std::vector<nx::af::Blk> ablk;      // decoder: the walked blocks, in order
     nx::af::WalkErr awerr;              // decoder: the walk's header failure after them
     uint64_t astage = 0;                // decoder: staging offset of the walked bytes (block data are relative)
+    // JdkZlibEncoder jobs (pieces like an alt encoder's): the handle, and for a close the trailer's
+    // length and the total-in it states
+    nx_zlib_encoder* zenc = nullptr;
+    uint32_t ztrailer = 0;
+    uint64_t ztotal_in = 0;
+    // JdkZlibDecoder jobs: the handle; the ticket's call state (its cumulation is the handle's pending
+    // buffer); a held job's own bytes until it starts; the batch that owns the job
+    nx_zlib_decoder* zdec = nullptr;
+    nx::zl::Call zcall;
+    std::vector<uint8_t> zin;
+    bool zheld = false;
+    Batch* zq = nullptr;    // the batch its current body step is queued in
+    Batch* home = nullptr;
     Job() = default;
     Job(const Job&) = delete;
     Job& operator=(const Job&) = delete;
@@ -527,9 +540,19 @@ struct Job {
         adec = d;
         d->refs.fetch_add(1);
     }
+    void bind(nx_zlib_encoder* e) {
+        zenc = e;
+        e->refs.fetch_add(1);
+    }
+    void bind(nx_zlib_decoder* d) {
+        zdec = d;
+        d->refs.fetch_add(1);
+    }
     ~Job() {
         nx_decoder_unref(dec);
         nx_alt_decoder_unref(adec);
+        nx_zlib_encoder_unref(zenc);
+        nx_zlib_decoder_unref(zdec);
     }
 };
 using JobPtr = std::unique_ptr<Job>;  // a job not yet handed to its batch (register_job)
@@ -539,7 +562,8 @@ struct AltEntry {  // one block for a codec kernel; the flush lays each list out
     uint32_t len, aux;  // aux: FastLZ encode level / decode in_avail; LZ4 encode level | highCompressor << 8; decode olen
     int32_t lim;        // FastLZ encode: readU16 limit; decode: originalLength
 };
-enum AltIx { FLZ_E, LZF_E, LZ4_E, FLZ_D, LZF_D, LZ4_D, kAltLists };  // encode / decode x codec, in Codec's order
+enum AltIx { FLZ_E, LZF_E, LZ4_E, FLZ_D, LZF_D, LZ4_D, DFL_S, DFL_M, kAltLists };  // encode / decode x codec, in Codec's order;
+                                                                                   // deflate slices: stored-only (level 0), matcher
 
 struct Batch {
     Pinned staging;  // chunk payloads, then the device arrays (one H2D copy at flush)
@@ -567,6 +591,18 @@ struct Batch {
     std::vector<nx::bt::AltJobD> ajob;
     uint64_t aslots = 0;  // alt slot bytes
     std::vector<AltEntry> alt[kAltLists];
+    // JdkZlibDecoder jobs: one stream per job (its body step), the window region's bytes, the streams'
+    // places in the launch order (set at flush: by checksum), the held jobs it owns
+    struct ZStream {
+        nx::zj::DecStream d;
+        uint64_t in_off;
+        uint32_t in_len;
+        uint32_t ck;  // CK_CRC32 / CK_ADLER32 / CK_NONE
+    };
+    std::vector<ZStream> zst;
+    std::vector<uint32_t> zpos;
+    uint64_t zwin = 0, res_z = 0;
+    uint32_t zheld_n = 0;
     Pinned out;  // mapped result arena: job outputs, then the result records
     uint64_t out_used = 0, res_enc = 0, res_dec = 0, res_alt = 0;
     // Bytes the finish kernels are known to write into `out`: decoded messages (lengths from the
@@ -604,6 +640,9 @@ struct Batch {
         ajob.clear();
         aslots = 0;
         for (std::vector<AltEntry>& L : alt) L.clear();
+        zst.clear();
+        zpos.clear();
+        zwin = res_z = 0;
         for (Job* j : jobs) delete j;
         jobs.clear();
         inflight = done = false;
@@ -667,7 +706,15 @@ struct nx_batcher {
     uint64_t applied = 0;     // batches applied, in flush order (Batch::seq < applied)
     size_t flush_bytes = 0;   // auto-flush threshold on a batch's input bytes (0 = only explicit flushes)
     ArenaCount arena;         // pinned staging / result arenas of all batches
-    std::vector<std::pair<Job*, Batch*>> cont;  // re-walked jobs to queue again (found by apply())
+    std::vector<std::pair<Job*, Batch*>> cont;  // re-walked jobs / zlib decoder jobs with a further body step to queue
+                                                // again (found by apply())
+    // JdkZlibDecoder handles with unapplied jobs: the one whose steps run (active), and the jobs submitted
+    // behind it (held, in submit order; each stays in the batch that collected it until it starts)
+    struct ZChan {
+        Job* active = nullptr;
+        std::deque<Job*> held;
+    };
+    std::unordered_map<nx_zlib_decoder*, ZChan> zchan;
     bool kick = false;        // the collecting batch holds a re-walked job: launch it at the next poll/wait
 };
 
@@ -688,7 +735,7 @@ Batch* new_batch(nx_batcher* b) {  // a batch object with its event, its pinned 
 
 Batch* reuse_or_new_batch(nx_batcher* b) {
     for (Batch* x : b->all) {
-        if (!x->inflight && x->live == 0 && x != b->cur) {
+        if (!x->inflight && x->live == 0 && x->zheld_n == 0 && x != b->cur) {
             x->reset();
             return x;
         }
@@ -877,18 +924,22 @@ struct Dev {  // filled by the kernels: device only, after the alt slots in `slo
     uint64_t off;
 };
 
-// Decoder checksums run as four launches: Adler32 over decoded slots / over raw blocks' input bytes, XXH32
-// over the same two.  The list of a piece that wants one, or -1:
+// Piece checksums run as up to six launches: Adler32 over decoded slots / over raw blocks' input bytes, XXH32
+// over the same two, and for JdkZlibEncoder slices Adler32 / CRC32 over their input bytes.  The list of a
+// piece that wants one, or -1:
+constexpr int kCkLists = 6;
 inline int ck_list(const nx::bt::AltPiece& q) {
     if (q.kind < nx::bt::AK_DEC_FLZ || !q.cks) return -1;
+    if (q.kind == nx::bt::AK_DFL_ENC) return q.cks == nx::bt::CK_CRC32 ? 5 : 4;
     return (q.cks == nx::bt::CK_XXH32 ? 2 : 0) + (q.kind == nx::bt::AK_DEC_RAW ? 1 : 0);
 }
+inline bool ck_of_input(int c) { return c == 1 || c == 3 || c >= 4; }  // the list's bytes lie in the input arena
 struct CkCount {
-    uint32_t n[4] = {}, first[4] = {}, total = 0;  // first: the list's first result in AltArrays::dcks
+    uint32_t n[kCkLists] = {}, first[kCkLists] = {}, total = 0;  // first: the list's first result in AltArrays::dcks
     explicit CkCount(const std::vector<nx::bt::AltPiece>& apc) {
         for (const nx::bt::AltPiece& q : apc)
             if (const int c = ck_list(q); c >= 0) n[c] += 1;
-        for (int c = 0; c < 4; ++c) {
+        for (int c = 0; c < kCkLists; ++c) {
             first[c] = total;
             total += n[c];
         }
@@ -982,10 +1033,13 @@ struct Flush {
         const uint32_t n = (uint32_t)bt->alt[c].size();
         return {room<uint64_t>(n), room<uint64_t>(n), room<uint32_t>(n), room<uint32_t>(n), room<int32_t>(n), n};
     }
-    const AltIn al[kAltLists] = {alt_room(FLZ_E), alt_room(LZF_E), alt_room(LZ4_E), alt_room(FLZ_D), alt_room(LZF_D), alt_room(LZ4_D)};
+    const AltIn al[kAltLists] = {alt_room(FLZ_E), alt_room(LZF_E), alt_room(LZ4_E), alt_room(FLZ_D),
+                                 alt_room(LZF_D), alt_room(LZ4_D), alt_room(DFL_S), alt_room(DFL_M)};
     const CkCount cks{bt->apc};
-    const In<uint64_t> ck_off[4] = {room<uint64_t>(cks.n[0]), room<uint64_t>(cks.n[1]), room<uint64_t>(cks.n[2]), room<uint64_t>(cks.n[3])};
-    const In<uint32_t> ck_len[4] = {room<uint32_t>(cks.n[0]), room<uint32_t>(cks.n[1]), room<uint32_t>(cks.n[2]), room<uint32_t>(cks.n[3])};
+    const In<uint64_t> ck_off[kCkLists] = {room<uint64_t>(cks.n[0]), room<uint64_t>(cks.n[1]), room<uint64_t>(cks.n[2]),
+                                           room<uint64_t>(cks.n[3]), room<uint64_t>(cks.n[4]), room<uint64_t>(cks.n[5])};
+    const In<uint32_t> ck_len[kCkLists] = {room<uint32_t>(cks.n[0]), room<uint32_t>(cks.n[1]), room<uint32_t>(cks.n[2]),
+                                           room<uint32_t>(cks.n[3]), room<uint32_t>(cks.n[4]), room<uint32_t>(cks.n[5])};
     const In<nx::bt::AltPiece> apc = put(bt->apc);
     const In<nx::bt::AltJobD> ajob = put(bt->ajob);
     const Dev<uint32_t> fclen = out<uint32_t>(al[FLZ_E].n), fadl = out<uint32_t>(al[FLZ_E].n);
@@ -994,6 +1048,19 @@ struct Flush {
     const Dev<int32_t> lst = out<int32_t>(al[LZF_E].n), zst = out<int32_t>(al[LZ4_E].n);
     const Dev<int32_t> dfr = out<int32_t>(al[FLZ_D].n), dlst = out<int32_t>(al[LZF_D].n), dzst = out<int32_t>(al[LZ4_D].n);
     const Dev<uint32_t> dcks = out<uint32_t>(cks.total);
+    const Dev<uint32_t> dfolen = out<uint32_t>(al[DFL_S].n + al[DFL_M].n);  // the stored-only launch's results, then the matcher's
+    const Dev<int32_t> dfst = out<int32_t>(al[DFL_S].n + al[DFL_M].n);
+    // JdkZlibDecoder: the streams of the one inflate call, ordered by checksum (CRC32, Adler32, none); the
+    // windows lie after the kernels' arrays (zwin)
+    const uint32_t nz = (uint32_t)bt->zst.size();
+    uint32_t nz_crc = 0, nz_adler = 0;
+    const In<nx::zj::DecStream> zrec = room<nx::zj::DecStream>(nz);
+    const In<uint64_t> zin = room<uint64_t>(nz), zout = room<uint64_t>(nz), zsumoff = room<uint64_t>(nz);
+    const In<uint32_t> zilen = room<uint32_t>(nz), zhist = room<uint32_t>(nz), zcap = room<uint32_t>(nz);
+    const Dev<uint8_t> zstate = out<uint8_t>((size_t)NX_INFLATE_STATE_BYTES * nz);
+    const Dev<uint32_t> zdcons = out<uint32_t>(nz), zdolen = out<uint32_t>(nz), zdsum = out<uint32_t>(nz);
+    const Dev<int32_t> zdstat = out<int32_t>(nz);
+    uint8_t* zwin = nullptr;
 
     Flush(nx_batcher* b_, Batch* bt_) : b(b_), bt(bt_), s(b_->s[b_->flushes % kStreams]) {}
 };
@@ -1046,17 +1113,37 @@ int32_t fill_upload(Flush& F) {
     // the uploaded pieces: an LZ4 block's results are at its place in the launch order; a decoder piece with
     // a checksum joins its list and learns its result's index (aux, 1-based)
     nx::bt::AltPiece* apc = F.host(F.apc);
-    uint32_t nck[4] = {};
+    uint32_t nck[kCkLists] = {};
     for (uint32_t p = 0; p < F.nap; ++p) {
         nx::bt::AltPiece& q = apc[p];
         if (q.kind == nx::bt::AK_LZ4_ENC) q.res = lz4_pos[q.res];
+        if (q.kind == nx::bt::AK_DFL_ENC && q.olen) q.res += F.al[DFL_S].n;  // olen: the slice is on the matcher list
         const int c = ck_list(q);
         if (c < 0) continue;
-        const bool raw = q.kind == nx::bt::AK_DEC_RAW;
+        const bool raw = ck_of_input(c);
         const uint32_t i = nck[c]++;
         F.host(F.ck_off[c])[i] = raw ? q.src : q.slot;
         F.host(F.ck_len[c])[i] = raw ? q.len : q.olen;
         q.aux = F.cks.first[c] + i + 1;
+    }
+    // the inflate call's streams: CRC32 streams first, then Adler32, then those without a checksum
+    bt->zpos.resize(F.nz);
+    for (const Batch::ZStream& z : bt->zst) {
+        F.nz_crc += z.ck == nx::bt::CK_CRC32;
+        F.nz_adler += z.ck == nx::bt::CK_ADLER32;
+    }
+    uint32_t at[3] = {0, F.nz_crc, F.nz_crc + F.nz_adler};
+    for (uint32_t i = 0; i < F.nz; ++i) {
+        const Batch::ZStream& z = bt->zst[i];
+        const uint32_t k = at[z.ck == nx::bt::CK_CRC32 ? 0 : z.ck == nx::bt::CK_ADLER32 ? 1 : 2]++;
+        bt->zpos[i] = k;
+        F.host(F.zrec)[k] = z.d;
+        F.host(F.zin)[k] = z.in_off;
+        F.host(F.zilen)[k] = z.in_len;
+        F.host(F.zout)[k] = z.d.win + nx::zj::kHist - z.d.hist;  // the window's history starts here
+        F.host(F.zsumoff)[k] = z.d.win + nx::zj::kHist;
+        F.host(F.zhist)[k] = z.d.hist;
+        F.host(F.zcap)[k] = z.d.out_cap;
     }
     return NX_OK;
 }
@@ -1067,6 +1154,7 @@ int32_t place(Flush& F) {
     nx_batcher* b = F.b;
     Batch* bt = F.bt;
     if (F.naj && !bt->reserve_out(sizeof(nx::bt::AltRes) * F.nap + 8, &bt->res_alt)) return NX_ERR_HIP;
+    if (F.nz && !bt->reserve_out(sizeof(nx::zj::DecRes) * F.nz + 8, &bt->res_z)) return NX_ERR_HIP;
     if (!bt->reserve_out(8ull * F.nej + 8, &bt->res_enc) || !bt->reserve_out(sizeof(DecRes) * F.nda + 8, &bt->res_dec)) return NX_ERR_HIP;
     // spill area: a chunk that decodes longer than its preamble said (Java grows its buffer up to
     // 65 536, SnappyFrameDecoder.java:203) has no room in its message reservation; k_dec_finish moves
@@ -1086,7 +1174,7 @@ int32_t place(Flush& F) {
     nx::h::DevBuf& mirror = b->dmirror[b->flushes % kStreams];
     if (F.dma_out && !mirror.ensure(bt->out_used)) return NX_ERR_HIP;
     F.ob = F.dma_out ? mirror.as<uint8_t>() : bt->out.d;
-    if (!bt->din.ensure(F.d0 + bt->direct_used + 16) || !bt->slots.ensure(bt->eslots + F.dslot_bytes + bt->aslots + F.kern_used + 128))
+    if (!bt->din.ensure(F.d0 + bt->direct_used + 16) || !bt->slots.ensure(bt->eslots + F.dslot_bytes + bt->aslots + F.kern_used + bt->zwin + 256))
         return NX_ERR_HIP;
     F.din = bt->din.as<uint8_t>();
     F.A = F.din + F.up_off;
@@ -1094,6 +1182,7 @@ int32_t place(Flush& F) {
     F.dslots = F.eslots + bt->eslots;
     F.aslots = reinterpret_cast<uint8_t*>(align16((uintptr_t)(F.dslots + F.dslot_bytes)));
     F.D = reinterpret_cast<uint8_t*>(align16((uintptr_t)(F.aslots + bt->aslots)));
+    F.zwin = reinterpret_cast<uint8_t*>(((uintptr_t)(F.D + F.kern_used) + 127) & ~(uintptr_t)127);
     return NX_OK;
 }
 
@@ -1217,22 +1306,65 @@ int32_t run_alt(const Flush& F) {
         if (r != NX_OK) return r;
         b->launches += 1;
     }
+    // JdkZlibEncoder slices: nx_deflate_encode_batch takes one level per launch, so one launch for the
+    // stored-only slices (level 0) and one for the matcher's (1..9 and -1 run the same matcher)
+    for (int c = DFL_S; c <= DFL_M; ++c) {
+        const auto& L = F.al[c];
+        if (!L.n) continue;
+        const uint32_t r0 = c == DFL_M ? F.al[DFL_S].n : 0u;
+        r = nx_deflate_encode_batch(F.din, F(L.off), F(L.len), F.aslots, F(L.slot), F(F.dfolen) + r0, F(F.dfst) + r0, L.n,
+                                    c == DFL_S ? 0 : 6, s);
+        if (r != NX_OK) return r;
+        b->launches += 1;
+    }
     uint32_t* dcks = F(F.dcks);
-    for (int c = 0; c < 4; ++c) {  // decoder checksums (after the decodes: stream order)
+    for (int c = 0; c < kCkLists; ++c) {  // piece checksums (after the decodes: stream order)
         const uint32_t n = F.cks.n[c];
         if (!n) continue;
-        const uint8_t* base = (c & 1) ? F.din : F.aslots;
-        r = c < 2 ? nx_adler32_batch(base, F(F.ck_off[c]), F(F.ck_len[c]), dcks + F.cks.first[c], n, s)
+        const uint8_t* base = ck_of_input(c) ? F.din : F.aslots;
+        r = c == 5 ? nx_crc32_batch(base, F(F.ck_off[c]), F(F.ck_len[c]), dcks + F.cks.first[c], n, s)
+            : c < 2 || c == 4 ? nx_adler32_batch(base, F(F.ck_off[c]), F(F.ck_len[c]), dcks + F.cks.first[c], n, s)
                   : nx_xxhash32_batch(base, F(F.ck_off[c]), F(F.ck_len[c]), nx::af::kLz4Seed, dcks + F.cks.first[c], n, s);
         if (r != NX_OK) return r;
         b->launches += 1;
     }
-    const nx::bt::AltArrays R{F(F.fclen), F(F.fst), F(F.fadl), F(F.lolen), F(F.lst), F(F.zolen), F(F.zst), F(F.dfr), F(F.dlst), F(F.dzst), dcks};
+    const nx::bt::AltArrays R{F(F.fclen), F(F.fst), F(F.fadl), F(F.lolen), F(F.lst), F(F.zolen), F(F.zst), F(F.dfr), F(F.dlst), F(F.dzst), dcks, F(F.dfolen), F(F.dfst)};
     hipLaunchKernelGGL(nx::bt::k_alt_finish, nx::bt::pcie_grid(F.naj), dim3(256), 0, s, F.din, F.aslots, F(F.apc), F(F.ajob), F.naj, R,
                        F.ob, reinterpret_cast<nx::bt::AltRes*>(F.ob + F.bt->res_alt));
     NX_HIP_CHECK(hipGetLastError());
     b->launches += 1;
     for (int c = 0; c < kAltLists; ++c) b->chunks += F.al[c].n;
+    return NX_OK;
+}
+
+// JdkZlibDecoder jobs: every stream's history and state into the batch, ONE inflate call, the outputs'
+// checksums (their lengths are the inflate's out_len array, on the device), then state, carry, output and
+// result record of every stream back out.  Five launches at most, however many jobs.
+int32_t run_zlib_decode(const Flush& F) {
+    if (!F.nz) return NX_OK;
+    const hipStream_t s = F.s;
+    int32_t r = nx::zj::dec_begin(F(F.zrec), F.nz, F.zwin, F(F.zstate), s);
+    if (r != NX_OK) return r;
+    r = nx_inflate_batch(F.din, F(F.zin), F(F.zilen), F.zwin, F(F.zout), F(F.zhist), F(F.zcap), F(F.zstate), F(F.zdcons), F(F.zdolen),
+                         F(F.zdstat), F.nz, s);
+    if (r != NX_OK) return r;
+    F.b->launches += 2;
+    if (F.nz_crc) {
+        r = nx_crc32_batch(F.zwin, F(F.zsumoff), F(F.zdolen), F(F.zdsum), F.nz_crc, s);
+        if (r != NX_OK) return r;
+        F.b->launches += 1;
+    }
+    if (F.nz_adler) {
+        const uint32_t a = F.nz_crc;
+        r = nx_adler32_batch(F.zwin, F(F.zsumoff) + a, F(F.zdolen) + a, F(F.zdsum) + a, F.nz_adler, s);
+        if (r != NX_OK) return r;
+        F.b->launches += 1;
+    }
+    r = nx::zj::dec_finish(F(F.zrec), F.nz, F.zwin, F(F.zstate), F(F.zdcons), F(F.zdolen), F(F.zdstat), F(F.zdsum), F.ob,
+                           reinterpret_cast<nx::zj::DecRes*>(F.ob + F.bt->res_z), s);
+    if (r != NX_OK) return r;
+    F.b->launches += 1;
+    F.b->chunks += F.nz;
     return NX_OK;
 }
 
@@ -1263,9 +1395,12 @@ int32_t launch_inner(nx_batcher* b, Batch* bt) {
     if (r == NX_OK) r = run_snappy_encode(F);
     if (r == NX_OK) r = run_snappy_decode(F);
     if (r == NX_OK) r = run_alt(F);
+    if (r == NX_OK) r = run_zlib_decode(F);
     if (r == NX_OK) r = transfer_out(F);
     return r;
 }
+
+void zdec_fail(nx_batcher* b, Job* j, int32_t code);
 
 // Job j could not run on the GPU: it completes with the error, and its decoder turns corrupted.
 void complete_launch_failed(Job* j, int32_t code) {
@@ -1286,7 +1421,13 @@ void complete_launch_failed(Job* j, int32_t code) {
 // flush order (it never got a sequence number) and is reused once its jobs are released.
 int32_t fail_batch(nx_batcher* b, Batch* bt, int32_t code) {
     (void)hipStreamSynchronize(b->s[b->flushes % kStreams]);
-    for (Job* j : bt->jobs) {
+    for (size_t k = 0; k < bt->jobs.size(); ++k) {
+        Job* j = bt->jobs[k];
+        if (j->kind == JobKind::ZlibDec) {  // only a job whose body step this launch held fails with it
+            if (!j->applied && !j->zheld && j->zq == bt) zdec_fail(b, j, code);
+            continue;
+        }
+        if (j->kind == JobKind::ZlibEnc && !j->applied) j->zenc->pending.fetch_sub(1);  // (its checksum is lost: the stream is broken)
         complete_launch_failed(j, code);
         j->msgs.clear();
     }
@@ -1298,6 +1439,193 @@ int32_t fail_batch(nx_batcher* b, Batch* bt, int32_t code) {
 int32_t launch(nx_batcher* b, Batch* bt) {
     const int32_t r = launch_inner(b, bt);
     return r == NX_OK ? NX_OK : fail_batch(b, bt, r);
+}
+
+// ---------------------------------------------------------------- JdkZlibEncoder / JdkZlibDecoder jobs
+// A JdkZlibEncoder job's pieces are an alt encoder's (apply_alt's sum); here the handle's running
+// checksum takes the slices' in flush order, and a close's trailer is written into the place its
+// AK_CONST piece reserved (JdkZlibEncoder.java:326-337).
+void apply_zlib_enc(Batch* bt, Job* j, const nx::bt::AltRes* ares) {
+    using namespace nx::bt;
+    j->applied = true;
+    nx_zlib_encoder* e = j->zenc;
+    e->pending.fetch_sub(1);
+    const AltJobD& J = bt->ajob[j->index];
+    uint64_t total = 0;
+    for (uint32_t k = J.p0; k < J.p0 + J.np; ++k) {
+        if (ares[k].status != NX_OK) {
+            j->status = ares[k].status;
+            j->err = nx_status_string(ares[k].status);
+            return;
+        }
+        total += ares[k].len;
+    }
+    for (uint32_t k = J.p0; k < J.p0 + J.np; ++k) {
+        const AltPiece& P = bt->apc[k];
+        if (P.kind != AK_DFL_ENC) continue;
+        if (e->wrapper == 1) e->crc = nx_crc32_combine(e->crc, ares[k].cks, P.len);
+        else if (e->wrapper == 0) e->adler = nx_adler32_combine(e->adler, ares[k].cks, P.len);
+    }
+    if (j->ztrailer) {
+        uint8_t* t = bt->out.h + J.out_off + total - j->ztrailer;
+        if (e->wrapper == 0) {  // Adler32, most significant byte first
+            for (int k = 0; k < 4; ++k) t[k] = (uint8_t)(e->adler >> (8 * (3 - k)));
+        } else {  // writeIntLE(crc), writeIntLE(totalIn) (:331-335)
+            for (int k = 0; k < 4; ++k) t[k] = (uint8_t)(e->crc >> (8 * k));
+            for (int k = 0; k < 4; ++k) t[4 + k] = (uint8_t)((uint32_t)j->ztotal_in >> (8 * k));
+        }
+    }
+    j->msgs.push_back({bt->out.h + J.out_off, (size_t)total});
+}
+
+// Output room of one body step, from the staged input: four times the input bytes (text deflates to about
+// a third to a quarter), within [64 KiB, 1 MiB] (the synchronous handle's chunk).  A step that fills it
+// stops with NX_INFLATE_OUTPUT_FULL and the job continues in the next flush.
+uint32_t zlib_out_cap(size_t in_len) {
+    const uint64_t want = 4ull * in_len;
+    const uint64_t c = want < (64u << 10) ? (64u << 10) : want > (1u << 20) ? (1u << 20) : want;
+    return (uint32_t)((c + 127) & ~127ull);
+}
+
+// Queue the body step job j needs as one stream of batch `to`: the unused bytes of the ticket's cumulation
+// are staged, the window and the output reservation are laid out.
+int32_t zdec_enqueue(Batch* to, Job* j) {
+    nx_zlib_decoder* d = j->zdec;
+    const nx::zl::Call& c = j->zcall;
+    const size_t left = c.n - c.rd;
+    const uint32_t in_len = (uint32_t)(left < 0x7FFFFFFFu ? left : 0x7FFFFFFFu);
+    Batch::ZStream z{};
+    z.d.out_cap = zlib_out_cap(in_len);
+    uint8_t* st = to->stage(in_len, &z.in_off);
+    if (!st || !to->reserve_out(z.d.out_cap, &z.d.out_off)) return NX_ERR_HIP;
+    nx::copy_bytes(st, c.in + c.rd, in_len);
+    z.in_len = in_len;
+    z.d.state = d->st.as<uint8_t>();
+    z.d.carry_in = d->win[d->cur].as<uint8_t>();
+    z.d.carry_out = d->win[d->cur ^ 1].as<uint8_t>();
+    z.d.win = to->zwin;
+    to->zwin += nx::zj::kHist + z.d.out_cap;  // (a multiple of 128)
+    z.d.hist = d->hist;
+    z.d.fresh = d->st_fresh ? 1u : 0u;
+    z.ck = d->gzip ? nx::bt::CK_CRC32 : d->zlib ? nx::bt::CK_ADLER32 : nx::bt::CK_NONE;
+    j->index = (uint32_t)to->zst.size();
+    j->zq = to;
+    to->zst.push_back(z);
+    return NX_OK;
+}
+
+// The ticket is complete: its used bytes leave the handle's pending buffer.
+void zdec_complete(Job* j, int32_t status) {
+    nx_zlib_decoder* d = j->zdec;
+    nx::zl::Call& c = j->zcall;
+    d->pend.erase(d->pend.begin(), d->pend.begin() + (ptrdiff_t)(c.rd < d->pend.size() ? c.rd : d->pend.size()));
+    if (!c.acc.empty()) {  // maxAllocation > 0: the ticket's one message
+        j->owned.push_back(std::move(c.acc));
+        j->msgs.push_back({j->owned.back().data(), j->owned.back().size()});
+    }
+    j->status = status;
+    j->err = c.err;
+    j->applied = true;
+    j->zq = nullptr;
+}
+
+// Job j starts (it is its decoder's only running job): its cumulation is the handle's pending buffer, with
+// the bytes a held job kept.  Runs the wrapper states; true = it needs a body step, false = complete.
+bool zdec_start(Job* j) {
+    nx_zlib_decoder* d = j->zdec;
+    d->pend.insert(d->pend.end(), j->zin.begin(), j->zin.end());
+    std::vector<uint8_t>().swap(j->zin);
+    nx::zl::Call& c = j->zcall;
+    c.in = d->pend.data();
+    c.n = d->pend.size();
+    c.rd = 0;
+    const int step = nx::zl::wrapper_step(d, c);
+    if (step == nx::zl::kBody) return true;
+    zdec_complete(j, step < 0 ? step : NX_OK);
+    return false;
+}
+
+// Decoder d's running job is complete: the next held one starts.  One that needs the device becomes the
+// running job and joins the collecting batch (queue_continuations); the others complete at once.
+void zdec_next(nx_batcher* b, nx_zlib_decoder* d) {
+    auto it = b->zchan.find(d);
+    if (it == b->zchan.end()) return;
+    nx_batcher::ZChan& ch = it->second;
+    ch.active = nullptr;
+    while (!ch.held.empty()) {
+        Job* h = ch.held.front();
+        ch.held.pop_front();
+        h->zheld = false;
+        h->home->zheld_n -= 1;
+        if (zdec_start(h)) {
+            ch.active = h;
+            b->cont.push_back({h, h->home});
+            return;
+        }
+    }
+    b->zchan.erase(it);
+}
+
+// A body step could not run (a failed launch, no room to queue it): the ticket fails with the code, the
+// decoder skips what follows (its held jobs deliver nothing).
+void zdec_fail(nx_batcher* b, Job* j, int32_t code) {
+    nx_zlib_decoder* d = j->zdec;
+    d->failed = true;
+    j->msgs.clear();
+    j->zcall.acc.clear();
+    j->zcall.rd = j->zcall.n;
+    j->zcall.err = "GPU batch launch failed";
+    zdec_complete(j, code);
+    auto it = b->zchan.find(d);
+    if (it == b->zchan.end()) return;
+    for (Job* h : it->second.held) {
+        h->zheld = false;
+        h->home->zheld_n -= 1;
+        (void)zdec_start(h);  // skips: the decoder has failed
+    }
+    b->zchan.erase(it);
+}
+
+// A decoder job's body step ran in batch bt: account for it (nx::zl::body_result), go on with the wrapper
+// states, and either complete the ticket or ask for the next step (b->cont).
+void apply_zlib_dec(nx_batcher* b, Batch* bt, Job* j, const nx::zj::DecRes* zres) {
+    namespace zl = nx::zl;
+    nx_zlib_decoder* d = j->zdec;
+    zl::Call& c = j->zcall;
+    const nx::zj::DecRes& R = zres[bt->zpos[j->index]];
+    const Batch::ZStream& Z = bt->zst[j->index];
+    struct JobIo : zl::BodyIo {  // the bytes are in the result arena; the carry was written by k_zlib_dec_finish
+        Job* j;
+        const uint8_t* src;
+        bool take(uint8_t* dst, uint32_t m) override {
+            if (dst) memcpy(dst, src, m);
+            else j->msgs.push_back({src, (size_t)m});
+            return true;
+        }
+        void drop() override {
+            j->msgs.clear();
+            j->owned.clear();
+        }
+        bool carry(uint32_t, uint32_t) override { return true; }
+    } io;
+    io.j = j;
+    io.src = bt->out.h + Z.d.out_off;
+    d->st_fresh = false;
+    const uint32_t m = R.out_len < Z.d.out_cap ? R.out_len : Z.d.out_cap;
+    int step = zl::body_result(d, c, R.consumed <= Z.in_len ? R.consumed : Z.in_len, m, R.status, R.sum, io);
+    if (step == zl::kWrapper) step = zl::wrapper_step(d, c);
+    if (step == zl::kBody) {  // NX_INFLATE_OUTPUT_FULL, or a further member: the same ticket, the next flush
+        for (nx_msg& q : j->msgs) {  // bt's arena may be reused before the ticket completes
+            if (q.data < bt->out.h || q.data >= bt->out.h + bt->out.cap) continue;
+            j->owned.emplace_back(q.data, q.data + q.len);
+            q.data = j->owned.back().data();
+        }
+        j->zq = nullptr;
+        b->cont.push_back({j, bt});
+        return;
+    }
+    zdec_complete(j, step <= zl::kHalt ? step - zl::kHalt : step < 0 ? step : NX_OK);
+    zdec_next(b, d);
 }
 
 // An alt-codec job's result (its batch complete): an encoder's framed bytes as one message, or the
@@ -1369,7 +1697,17 @@ void apply(nx_batcher* b, Batch* bt) {
     const DecRes* dres = reinterpret_cast<const DecRes*>(bt->out.h + bt->res_dec);
     char buf[160];
     const nx::bt::AltRes* ares = reinterpret_cast<const nx::bt::AltRes*>(bt->out.h + bt->res_alt);
-    for (Job* j : bt->jobs) {
+    const nx::zj::DecRes* zres = reinterpret_cast<const nx::zj::DecRes*>(bt->out.h + bt->res_z);
+    for (size_t k = 0; k < bt->jobs.size(); ++k) {
+        Job* j = bt->jobs[k];
+        if (j->kind == JobKind::ZlibEnc) {
+            apply_zlib_enc(bt, j, ares);
+            continue;
+        }
+        if (j->kind == JobKind::ZlibDec) {  // (complete since its submit, held, or running elsewhere: not this batch's)
+            if (!j->applied && !j->zheld && j->zq == bt) apply_zlib_dec(b, bt, j, zres);
+            continue;
+        }
         if (j->kind == JobKind::AltEnc || j->kind == JobKind::AltDec) {
             apply_alt(bt, j, ares);
             continue;
@@ -1461,17 +1799,26 @@ void queue_continuations(nx_batcher* b) {
     }
     for (auto& [j, from] : b->cont) {
         Batch* to = b->cur ? b->cur : reuse_or_new_batch(b);
-        nx_snappy_frame_decoder* d = j->dec;
         auto it = b->tickets.find(j->ticket);
         const bool live = it != b->tickets.end();
-        const uint8_t* S = d->hist.at(j->s_base);  // the owned segment rewalk() made, from s_base on
-        if (!to || !S || enqueue_dec(to, j, S, 0, nullptr) != NX_OK) {
-            // cannot queue it: the job fails as a launch failure would (result() reports it)
-            complete_launch_failed(j, NX_ERR_HIP);
-            from->jobs.push_back(j);  // stays owned by its batch
-            continue;
+        if (j->kind == JobKind::ZlibDec) {
+            if (!to || zdec_enqueue(to, j) != NX_OK) {
+                zdec_fail(b, j, NX_ERR_HIP);
+                from->jobs.push_back(j);
+                continue;
+            }
+        } else {
+            nx_snappy_frame_decoder* d = j->dec;
+            const uint8_t* S = d->hist.at(j->s_base);  // the owned segment rewalk() made, from s_base on
+            if (!to || !S || enqueue_dec(to, j, S, 0, nullptr) != NX_OK) {
+                // cannot queue it: the job fails as a launch failure would (result() reports it)
+                complete_launch_failed(j, NX_ERR_HIP);
+                from->jobs.push_back(j);  // stays owned by its batch
+                continue;
+            }
         }
         to->jobs.push_back(j);
+        j->home = to;
         b->cur = to;
         if (live) {
             if (from->live) from->live -= 1;
@@ -1519,6 +1866,14 @@ bool poll_batch(nx_batcher* b, Batch* bt, bool block) {
     return advance(b, bt->seq, block) && bt->done;
 }
 
+// The batch whose completion moves job j forward: its own, or, for a held JdkZlibDecoder job, the batch of
+// its decoder's running job.
+Batch* progress_batch(nx_batcher* b, const Job* j, Batch* own) {
+    if (j->kind != JobKind::ZlibDec || !j->zheld) return own;
+    auto it = b->zchan.find(j->zdec);
+    return it != b->zchan.end() && it->second.active ? it->second.active->home : own;
+}
+
 // Hold the shared workspace of kind k for the batcher's flushes (they run in a NoGrowScope): the full
 // reservation, or a smaller one when the device cannot spare it (a flush caps its grid to what is
 // held).  Done by the first submit that needs the kind, or up front by nx_batcher_reserve.
@@ -1561,6 +1916,7 @@ JobPtr open_job(nx_batcher* b, Batch*& bt, nx::WsKind ws, JobKind kind, Codec co
 int64_t register_job(nx_batcher* b, Batch* bt, JobPtr job) {
     Job* j = job.release();
     bt->jobs.push_back(j);
+    j->home = bt;
     bt->live += 1;
     b->tickets[j->ticket] = {bt, j};
     const int64_t t = (int64_t)j->ticket;
@@ -2064,6 +2420,116 @@ extern "C" int64_t nx_lz4_frame_encoder_submit(nx_lz4_frame_encoder* e, nx_batch
     return t;
 }
 
+// ---------------------------------------------------------------- JdkZlibEncoder / JdkZlibDecoder submits
+// JdkZlibEncoder.encode / finishEncode as a job (JdkZlibEncoder.java:214-276, 308-340): the header on the
+// first non-empty job or the close, one deflate slice per 64 KiB on the list of its level class, the final
+// block and the trailer's place on a close.  write_header, finished and total_in advance now; the running
+// checksum at apply().
+extern "C" int64_t nx_zlib_encoder_submit(nx_zlib_encoder* e, nx_batcher* b, const uint8_t* in, size_t n, int32_t op) {
+    if (!e || !b || (!in && n) || (op != 0 && op != 2)) return NX_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(b->mu);
+    Batch* bt = nullptr;
+    JobPtr j = open_job(b, bt, nx::WsKind::DeflateEnc, JobKind::ZlibEnc);
+    if (!j) return NX_ERR_HIP;
+    const AltMark mark(bt);
+    size_t out_need = 0;
+    auto constant = [&](const uint8_t* p, size_t len) {
+        AltPiece P{};
+        P.kind = nx::bt::AK_CONST;
+        P.len = (uint32_t)len;
+        for (size_t k = 0; k < len; ++k) (k < 8 ? P.src : P.slot) |= (uint64_t)p[k] << (8 * (k & 7));
+        bt->apc.push_back(P);
+        out_need += len;
+    };
+    uint64_t off = 0;
+    if (n) {
+        uint8_t* stg = bt->stage(n, &off);
+        if (!stg) return NX_ERR_HIP;
+        nx::copy_bytes(stg, in, n);
+    }
+    const bool close = op == 2 && !e->finished;
+    if (e->finished) {  // out.writeBytes(uncompressed) (:215-218); a second close writes nothing (:309-312)
+        if (n) {
+            AltPiece P{};
+            P.kind = nx::bt::AK_RAW;
+            P.src = off;
+            P.len = (uint32_t)n;  // (a message is a ByteBuf: below 2 GiB)
+            bt->apc.push_back(P);
+            out_need = n;
+        }
+    } else {
+        uint8_t hdr[16];
+        if (e->write_header && (n || close)) constant(hdr, nx::zl::write_header(e, hdr));
+        for (size_t q = 0; q < n; q += 65536) {
+            const uint32_t len = (uint32_t)(n - q < 65536 ? n - q : 65536);
+            const bool stored = e->level == 0;
+            AltPiece P{};
+            P.kind = nx::bt::AK_DFL_ENC;
+            P.src = off + q;
+            P.len = len;
+            P.olen = stored ? 0u : 1u;  // which launch (fill_upload)
+            P.cks = e->wrapper == 1 ? nx::bt::CK_CRC32 : e->wrapper == 0 ? nx::bt::CK_ADLER32 : nx::bt::CK_NONE;
+            P.slot = bt->aslots;
+            const size_t cap = nx_deflate_max_compressed_length(len);
+            bt->aslots += (cap + 127) & ~(size_t)127;
+            P.res = push_list(bt->alt[stored ? DFL_S : DFL_M], P.src, len, P.slot, 0);
+            bt->apc.push_back(P);
+            out_need += cap;
+        }
+        if (close) {  // the final block (an empty fixed-Huffman block), then the trailer's place
+            const uint8_t fin[10] = {0x03, 0x00};
+            j->ztrailer = e->wrapper == 0 ? 4u : e->wrapper == 1 ? 8u : 0u;
+            constant(fin, 2 + j->ztrailer);
+        }
+    }
+    j->ztotal_in = e->total_in + n;
+    const bool had_header = e->write_header && !e->finished && (n || close);
+    Job* const queued = j.get();
+    queued->bind(e);
+    e->pending.fetch_add(1);
+    const int64_t t = queue_alt(b, bt, std::move(j), mark, out_need);
+    if (t < 0) {  // (the job, dropped, gave its reference back)
+        e->pending.fetch_sub(1);
+        return t;
+    }
+    if (!e->finished) {
+        if (had_header) e->write_header = false;
+        e->total_in += n;
+        if (close) e->finished = true;
+    }
+    return t;
+}
+
+// JdkZlibDecoder.decode over the bytes handed over so far, as a job.  One job of a decoder runs at a time:
+// it starts here when none is unapplied (wrapper bytes are parsed now; a body step joins the collecting
+// batch), else it is held with its bytes until the earlier ones are applied.
+extern "C" int64_t nx_zlib_decoder_submit(nx_zlib_decoder* d, nx_batcher* b, const uint8_t* in, size_t n, size_t* consumed) {
+    if (!d || !b || (!in && n) || !consumed) return NX_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(b->mu);
+    nx_batcher* none = nullptr;
+    if (!d->owner.compare_exchange_strong(none, b) && none != b) return NX_ERR_INVALID_ARG;  // its jobs run on another batcher
+    Batch* bt = nullptr;
+    JobPtr job = open_job(b, bt, nx::WsKind::Count, JobKind::ZlibDec);
+    if (!job) return NX_ERR_HIP;
+    Job* j = job.get();
+    j->bind(d);
+    j->zin.assign(in, in + n);
+    auto ch = b->zchan.find(d);
+    if (ch != b->zchan.end()) {  // an earlier job is unapplied: held
+        j->zheld = true;
+        bt->zheld_n += 1;
+        ch->second.held.push_back(j);
+    } else if (zdec_start(j)) {
+        if (zdec_enqueue(bt, j) != NX_OK) {
+            zdec_fail(b, j, NX_ERR_HIP);
+        } else {
+            b->zchan[d].active = j;
+        }
+    }
+    *consumed = n;
+    return register_job(b, bt, std::move(job));
+}
+
 extern "C" int32_t nx_batcher_flush(nx_batcher* b) {
     if (!b) return NX_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(b->mu);
@@ -2080,7 +2546,7 @@ extern "C" int32_t nx_batcher_poll(nx_batcher* b, int64_t ticket) {
     auto it = b->tickets.find((uint64_t)ticket);
     if (it == b->tickets.end()) return NX_ERR_INVALID_ARG;
     Job* j = it->second.second;
-    (void)poll_batch(b, it->second.first, false);
+    (void)poll_batch(b, progress_batch(b, j, it->second.first), false);
     kick(b);
     return j->applied ? 1 : 0;  // a re-walked job continues in a later batch
 }
@@ -2094,8 +2560,9 @@ extern "C" int32_t nx_batcher_wait(nx_batcher* b, int64_t ticket) {
             std::lock_guard<std::mutex> lk(b->mu);
             auto it = b->tickets.find((uint64_t)ticket);
             if (it == b->tickets.end()) return NX_ERR_INVALID_ARG;
-            bt = it->second.first;
             j = it->second.second;
+            if (j->applied) return NX_OK;  // (a zlib decoder job that needed no body step: complete since its submit)
+            bt = progress_batch(b, j, it->second.first);
             if (bt == b->cur) {  // not flushed yet: flush now
                 b->cur = nullptr;
                 (void)launch(b, bt);  // a failed launch completes the batch's jobs with the error
@@ -2109,7 +2576,7 @@ extern "C" int32_t nx_batcher_wait(nx_batcher* b, int64_t ticket) {
         // its new batch if it moved.
         auto it = b->tickets.find((uint64_t)ticket);
         if (it == b->tickets.end()) return NX_ERR_INVALID_ARG;
-        if (it->second.first != bt) continue;
+        if (progress_batch(b, j, it->second.first) != bt) continue;
         if (!poll_batch(b, bt, true)) return NX_ERR_HIP;
         kick(b);
         if (j->applied) return NX_OK;

@@ -932,7 +932,8 @@ constexpr uint8_t kGzipHeader[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0};  // gz
 
 // the two bytes java.util.zip.Deflater (zlib's deflateInit) writes for a level: CMF 0x78, FLG with
 // the level class in its top two bits and the check bits that make the pair a multiple of 31
-size_t zlib_write_header(const nx_zlib_encoder* e, uint8_t* out) {
+}  // namespace
+size_t nx::zl::write_header(const nx_zlib_encoder* e, uint8_t* out) {
     if (e->wrapper == 1) {
         memcpy(out, kGzipHeader, 10);
         return 10;
@@ -945,7 +946,6 @@ size_t zlib_write_header(const nx_zlib_encoder* e, uint8_t* out) {
     }
     return 0;
 }
-}  // namespace
 
 extern "C" nx_zlib_encoder* nx_zlib_encoder_new(int32_t wrapper, int32_t level) {
     if (level < -1 || level > 9) return nullptr;     // checkInRange (:124-125)
@@ -959,12 +959,13 @@ extern "C" nx_zlib_encoder* nx_zlib_encoder_new(int32_t wrapper, int32_t level) 
     e->level = level;
     return e;
 }
-extern "C" void nx_zlib_encoder_free(nx_zlib_encoder* e) { delete e; }
+extern "C" void nx_zlib_encoder_free(nx_zlib_encoder* e) { nx_zlib_encoder_unref(e); }
 extern "C" size_t nx_zlib_max_encoded_length(size_t n) { return 20 + n + (n / kZlibSlice + 1) * 15; }
 
 extern "C" int64_t nx_zlib_encoder_encode(nx_zlib_encoder* e, const uint8_t* in, size_t n, uint8_t* out, size_t out_cap) {
     const nx::NoGrowScope no_grow;
     if (!e || (n && (!in || !out))) return NX_ERR_INVALID_ARG;
+    if (e->pending.load()) return NX_ERR_INVALID_ARG;  // unapplied batcher jobs hold the running checksum
     if (e->finished) {  // out.writeBytes(uncompressed) (:215-218)
         if (out_cap < n) return NX_ERR_INVALID_ARG;
         nx::copy_bytes(out, in, n);
@@ -1008,7 +1009,7 @@ extern "C" int64_t nx_zlib_encoder_encode(nx_zlib_encoder* e, const uint8_t* in,
     size_t op = 0;
     if (e->write_header) {
         e->write_header = false;
-        op = zlib_write_header(e, out);
+        op = nx::zl::write_header(e, out);
     }
     for (uint32_t i = 0; i < ns && ok; ++i) {  // each slice's bytes only, concatenated in place
         ok = g.d2h(out + op, g.dout.as<uint8_t>() + ooff[i], olen[i]);
@@ -1026,14 +1027,14 @@ extern "C" int64_t nx_zlib_encoder_encode(nx_zlib_encoder* e, const uint8_t* in,
 // finishEncode (:308-340): the header if nothing was written, the final block (an empty fixed-Huffman
 // block, what deflater.finish() adds after a sync flush), then the wrapper's trailer.
 extern "C" int64_t nx_zlib_encoder_close(nx_zlib_encoder* e, uint8_t* out, size_t out_cap) {
-    if (!e) return NX_ERR_INVALID_ARG;
+    if (!e || e->pending.load()) return NX_ERR_INVALID_ARG;
     if (e->finished) return 0;  // :309-312
     if (!out || out_cap < 20) return NX_ERR_INVALID_ARG;
     e->finished = true;
     size_t op = 0;
     if (e->write_header) {
         e->write_header = false;
-        op = zlib_write_header(e, out);
+        op = nx::zl::write_header(e, out);
     }
     out[op++] = 0x03;
     out[op++] = 0x00;
@@ -1083,7 +1084,7 @@ enum { kZNeed = 0, kZOk = 1 };  // (< 0: failed, ml.err holds the message)
 // readGZIPHeader (:343-433), state for state.  xlen starts at -1 and the two length bytes are OR-ed
 // into it (:393), so it stays -1 and the extra field is never skipped (:398): a header with a
 // non-empty FEXTRA field leaves that field in front of the deflate data, as the reference does.
-int gzip_header(nx_zlib_decoder* d, const uint8_t* in, size_t n, size_t& rd) {
+int gzip_header(nx_zlib_decoder* d, std::string& err, const uint8_t* in, size_t n, size_t& rd) {
     using Z = nx_zlib_decoder;
     auto skip_if_needed = [&](int32_t mask) {  // skipIfNeeded (:442-458)
         if (d->flags & mask) {
@@ -1101,16 +1102,16 @@ int gzip_header(nx_zlib_decoder* d, const uint8_t* in, size_t n, size_t& rd) {
             if (n - rd < 10) return kZNeed;
             const uint8_t* h = in + rd;
             if (h[0] != 31) {
-                d->ml.err = "Input is not in the GZIP format";
+                err = "Input is not in the GZIP format";
                 return NX_ERR_FRAME_CORRUPT;
             }
             if (h[2] != 8) {  // Deflater.DEFLATED
-                d->ml.err = "Unsupported compression method " + std::to_string((int)h[2]) + " in the GZIP header";
+                err = "Unsupported compression method " + std::to_string((int)h[2]) + " in the GZIP header";
                 return NX_ERR_FRAME_CORRUPT;
             }
             d->flags = h[3];
             if (d->flags & FRESERVED) {
-                d->ml.err = "Reserved flags are set in the GZIP header";
+                err = "Reserved flags are set in the GZIP header";
                 return NX_ERR_FRAME_CORRUPT;
             }
             d->hcrc = crc32_host(d->hcrc, h, 10);  // magic, method, flags, mtime, extra flags, operating system
@@ -1149,7 +1150,7 @@ int gzip_header(nx_zlib_decoder* d, const uint8_t* in, size_t n, size_t& rd) {
                 const int32_t want = in[rd] | (in[rd + 1] << 8), got = (int32_t)(d->hcrc & 0xFFFFu);
                 rd += 2;
                 if (want != got) {
-                    d->ml.err = "CRC16 value mismatch. Expected: " + std::to_string(want) + ", Got: " + std::to_string(got);
+                    err = "CRC16 value mismatch. Expected: " + std::to_string(want) + ", Got: " + std::to_string(got);
                     return NX_ERR_FRAME_CORRUPT;
                 }
             }
@@ -1164,31 +1165,32 @@ int gzip_header(nx_zlib_decoder* d, const uint8_t* in, size_t n, size_t& rd) {
 
 // readGZIPFooter (:467-483) with verifyCrc (:492-504): all 8 bytes first, then the two checks with
 // Java's formatting (the CRC as unsigned longs, the lengths as ints).
-int gzip_footer(nx_zlib_decoder* d, const uint8_t* in, size_t n, size_t& rd) {
+int gzip_footer(nx_zlib_decoder* d, std::string& err, const uint8_t* in, size_t n, size_t& rd) {
     if (n - rd < 8) return kZNeed;
     const uint32_t want_crc = le32(in + rd);
     const int32_t want_len = (int32_t)le32(in + rd + 4), got_len = (int32_t)(uint32_t)d->total_out;
     if (want_crc != d->crc) {
         rd += 4;
-        d->ml.err = "CRC value mismatch. Expected: " + std::to_string((unsigned long long)want_crc) +
+        err = "CRC value mismatch. Expected: " + std::to_string((unsigned long long)want_crc) +
                     ", Got: " + std::to_string((unsigned long long)d->crc);
         return NX_ERR_FRAME_CORRUPT;
     }
     rd += 8;
     if (want_len != got_len) {
-        d->ml.err = "Number of bytes mismatch. Expected: " + std::to_string(want_len) + ", Got: " + std::to_string(got_len);
+        err = "Number of bytes mismatch. Expected: " + std::to_string(want_len) + ", Got: " + std::to_string(got_len);
         return NX_ERR_FRAME_CORRUPT;
     }
     return kZOk;
 }
 
-// inflater.reset() (:321) and crc.reset(): a new member starts with an empty window
-bool zlib_reset_member(nx_zlib_decoder* d) {
+// inflater.reset() (:321) and crc.reset(): a new member starts with an empty window and, at its first
+// body step, from the all-zero inflate state (st_fresh: whoever runs that step clears the state)
+void zlib_reset_member(nx_zlib_decoder* d) {
     d->hist = 0;
     d->crc = 0;
     d->adler = 1;
     d->total_out = 0;
-    return hipMemsetAsync(d->st.p, 0, NX_INFLATE_STATE_BYTES, d->g.s) == hipSuccess;
+    d->st_fresh = true;
 }
 }  // namespace
 
@@ -1196,7 +1198,8 @@ extern "C" nx_zlib_decoder* nx_zlib_decoder_new(int32_t wrapper, int32_t decompr
     if (wrapper < 0 || wrapper > 3 || max_allocation < 0) return nullptr;  // checkPositiveOrZero (ZlibDecoder.java:49)
     auto* d = new nx_zlib_decoder();
     if (!d->g.ok || !d->win[0].ensure(kZlibHist + kZlibChunk) || !d->win[1].ensure(kZlibHist + kZlibChunk) ||
-        !d->st.ensure(NX_INFLATE_STATE_BYTES) || !d->par.ensure(sizeof(ZPar)) || !zlib_reset_member(d) || !d->g.sync()) {
+        !d->st.ensure(NX_INFLATE_STATE_BYTES) || !d->par.ensure(sizeof(ZPar)) ||
+        hipMemsetAsync(d->st.p, 0, NX_INFLATE_STATE_BYTES, d->g.s) != hipSuccess || !d->g.sync()) {
         delete d;
         return nullptr;
     }
@@ -1207,177 +1210,223 @@ extern "C" nx_zlib_decoder* nx_zlib_decoder_new(int32_t wrapper, int32_t decompr
     d->decide = wrapper == 3;
     return d;
 }
-extern "C" void nx_zlib_decoder_free(nx_zlib_decoder* d) { delete d; }
+extern "C" void nx_zlib_decoder_free(nx_zlib_decoder* d) { nx_zlib_decoder_unref(d); }
 extern "C" int32_t nx_zlib_decoder_is_closed(const nx_zlib_decoder* d) { return d && d->finished ? 1 : 0; }
 
-extern "C" int32_t nx_zlib_decoder_decode(nx_zlib_decoder* d, const uint8_t* in, size_t n, size_t* consumed, const nx_msg** msgs,
-                                          size_t* n_msgs, const char** err_msg) {
-    const nx::NoGrowScope no_grow;
-    if (!d || (!in && n) || !consumed || !msgs || !n_msgs) return NX_ERR_INVALID_ARG;
+// ---------------------------------------------------------------- the decoder's state machine
+// JdkZlibDecoder.decode (:198-314) as two steps that nx_zlib_decoder_decode below and the batcher's
+// decoder jobs (batcher.cpp) both drive: wrapper_step parses wrapper bytes until the deflate body needs
+// the device; body_result accounts for one inflate launch of one stream.  What differs between the two
+// drivers (where the launch runs, how its bytes reach the host, who copies the carry) is nx::zl::BodyIo.
+namespace nx {
+namespace zl {
+
+int fail(nx_zlib_decoder* d, Call& c, int32_t code) {  // the exception leaves decode(): what was decoded is forwarded (:304-312)
+    d->failed = true;
+    c.rd = c.n;
+    return code;
+}
+
+int wrapper_step(nx_zlib_decoder* d, Call& c) {
     using Z = nx_zlib_decoder;
-    MsgList& ml = d->ml;
-    ml.clear();
-    Gpu& g = d->g;
-    size_t rd = 0;
-    std::vector<uint8_t> acc;  // maxAllocation > 0: the call's one message
-    auto finish = [&](int32_t r) {
-        if (!acc.empty()) ml.owned.push_back(std::move(acc));
-        for (auto& o : ml.owned) ml.msgs.push_back({o.data(), o.size()});
-        *consumed = rd;
-        *msgs = ml.msgs.data();
-        *n_msgs = ml.msgs.size();
-        if (err_msg) *err_msg = ml.err.empty() ? nullptr : ml.err.c_str();
-        return r;
-    };
-    auto fail = [&](int32_t code) {  // the exception leaves decode(): what was decoded is forwarded (:304-312)
-        d->failed = true;
-        rd = n;
-        return finish(code);
-    };
+    const uint8_t* in = c.in;
+    const size_t n = c.n;
+    size_t& rd = c.rd;
     if (d->finished || d->failed) {  // in.skipBytes(in.readableBytes()) (:200-204)
         rd = n;
-        return finish(NX_OK);
+        return kStop;
     }
-    bool uploaded = false;  // the cumulation is copied to the device once, when a body needs it
     for (;;) {
-        if (rd == n) break;  // :206-209
+        if (rd == n) return kStop;  // :206-209
         if (d->decide) {  // :211-220
-            if (n - rd < 2) break;
+            if (n - rd < 2) return kStop;
             const int32_t cmf_flg = (int16_t)be16(in + rd);  // looksLikeZlib on a Java short (:529-532)
             d->zlib = (cmf_flg & 0x7800) == 0x7800 && cmf_flg % 31 == 0;
             d->decide = false;
         }
         if (d->gzip && d->gz != Z::HEADER_END) {  // :222-242
             if (d->gz == Z::FOOTER_START) {
-                const int r = gzip_footer(d, in, n, rd);
-                if (r == kZNeed) break;
-                if (r < 0) return fail(r);
+                const int r = gzip_footer(d, c.err, in, n, rd);
+                if (r == kZNeed) return kStop;
+                if (r < 0) return fail(d, c, r);
                 if (!d->concatenated) {  // handleGzipFooter (:316-328); the next decode() skips the rest
                     d->finished = true;
                     rd = n;
-                    break;
+                    return kStop;
                 }
-                if (!zlib_reset_member(d)) return finish(NX_ERR_HIP);
+                zlib_reset_member(d);
                 d->gz = Z::HEADER_START;
             }
-            const int r = gzip_header(d, in, n, rd);
-            if (r == kZNeed) break;
-            if (r < 0) return fail(r);
+            const int r = gzip_header(d, c.err, in, n, rd);
+            if (r == kZNeed) return kStop;
+            if (r < 0) return fail(d, c, r);
             continue;
         }
         if (d->zlib && d->zs != Z::Z_BODY) {  // inflate()'s HEAD / DICTID / CHECK states (zlib inflate.c)
             if (d->zs == Z::Z_HEAD) {
-                if (n - rd < 2) break;
+                if (n - rd < 2) return kStop;
                 const uint32_t cmf = in[rd], flg = in[rd + 1];
                 int32_t code = NX_OK;
                 if (((cmf << 8) + flg) % 31) code = NX_ERR_ZLIB_HEADER_CHECK;
                 else if ((cmf & 15u) != 8u) code = NX_ERR_ZLIB_METHOD;
                 else if ((cmf >> 4) + 8u > 15u) code = NX_ERR_ZLIB_WINDOW;
                 if (code == NX_OK && (flg & 0x20u)) {  // FDICT: zlib reads the dictionary id, then asks for it (:276-280)
-                    if (n - rd < 6) break;
-                    ml.err = "decompression failure, unable to set dictionary as non was specified";
-                    return fail(NX_ERR_ZLIB_NEED_DICT);
+                    if (n - rd < 6) return kStop;
+                    c.err = "decompression failure, unable to set dictionary as non was specified";
+                    return fail(d, c, NX_ERR_ZLIB_NEED_DICT);
                 }
                 if (code != NX_OK) {
-                    ml.err = "decompression failure";
-                    return fail(code);
+                    c.err = "decompression failure";
+                    return fail(d, c, code);
                 }
                 rd += 2;
                 d->zs = Z::Z_BODY;
                 continue;
             }
-            if (n - rd < 4) break;  // the Adler32 trailer, most significant byte first
+            if (n - rd < 4) return kStop;  // the Adler32 trailer, most significant byte first
             if (be32(in + rd) != d->adler) {
-                ml.err = "decompression failure";
-                return fail(NX_ERR_ZLIB_DATA_CHECK);
+                c.err = "decompression failure";
+                return fail(d, c, NX_ERR_ZLIB_DATA_CHECK);
             }
             rd += 4;
             d->finished = true;  // inflater.finished() (:284-286)
             rd = n;
-            break;
+            return kStop;
         }
-        // the deflate body: inflate until the input runs out, the stream ends or an error (:257-294)
+        return kBody;  // the deflate body: inflate until the input runs out, the stream ends or an error (:257-294)
+    }
+}
+
+int body_result(nx_zlib_decoder* d, Call& c, uint32_t consumed, uint32_t m, int32_t status, uint32_t sum, BodyIo& io) {
+    using Z = nx_zlib_decoder;
+    if (status == NX_ERR_INVALID_ARG || status == NX_ERR_INTERNAL) return kHalt + status;
+    c.rd += consumed;
+    if (m) {
+        if (d->max_allocation > 0) {
+            if (c.acc.size() + m > (size_t)d->max_allocation) {  // prepareDecompressBuffer (ZlibDecoder.java:74-81)
+                c.acc.clear();
+                io.drop();
+                d->finished = true;  // decompressionBufferExhausted (:331-333)
+                c.err = "Decompression buffer has reached maximum size: " + std::to_string(d->max_allocation);
+                c.rd = c.n;
+                return NX_ERR_ZLIB_MAX_ALLOCATION;
+            }
+            const size_t at = c.acc.size();
+            c.acc.resize(at + m);
+            if (!io.take(c.acc.data() + at, m)) return kHalt + NX_ERR_HIP;
+        } else if (!io.take(nullptr, m)) {
+            return kHalt + NX_ERR_HIP;
+        }
+        if (d->gzip) d->crc = nx_crc32_combine(d->crc, sum, m);
+        else if (d->zlib) d->adler = nx_adler32_combine(d->adler, sum, m);
+        d->total_out += m;
+        // the last 32 KiB of the stream's output become the other window's history
+        const uint32_t h = d->hist + m < kZlibHist ? d->hist + m : kZlibHist;
+        if (!io.carry(h, m)) return kHalt + NX_ERR_HIP;
+        d->hist = h;
+        d->cur ^= 1;
+    }
+    if (status < 0) {  // DataFormatException -> DecompressionException("decompression failure") (:302-303)
+        c.err = "decompression failure";
+        return fail(d, c, status);
+    }
+    if (status == NX_INFLATE_OUTPUT_FULL) return kBody;
+    if (status != NX_OK) return kStop;  // the inflater needs input
+    if (d->gzip) {
+        d->gz = Z::FOOTER_START;  // :298-301
+    } else if (d->zlib) {
+        d->zs = Z::Z_TRAILER;
+    } else {
+        d->finished = true;  // :284-286
+        c.rd = c.n;
+        return kStop;
+    }
+    return kWrapper;
+}
+
+}  // namespace zl
+}  // namespace nx
+
+extern "C" int32_t nx_zlib_decoder_decode(nx_zlib_decoder* d, const uint8_t* in, size_t n, size_t* consumed, const nx_msg** msgs,
+                                          size_t* n_msgs, const char** err_msg) {
+    const nx::NoGrowScope no_grow;
+    if (!d || (!in && n) || !consumed || !msgs || !n_msgs) return NX_ERR_INVALID_ARG;
+    if (d->owner.load()) return NX_ERR_INVALID_ARG;  // a batcher decoder stays a batcher decoder
+    namespace zl = nx::zl;
+    MsgList& ml = d->ml;
+    ml.clear();
+    Gpu& g = d->g;
+    zl::Call c;
+    c.in = in;
+    c.n = n;
+    auto finish = [&](int32_t r) {
+        ml.err = c.err;
+        if (!c.acc.empty()) ml.owned.push_back(std::move(c.acc));
+        for (auto& o : ml.owned) ml.msgs.push_back({o.data(), o.size()});
+        *consumed = c.rd;
+        *msgs = ml.msgs.data();
+        *n_msgs = ml.msgs.size();
+        if (err_msg) *err_msg = ml.err.empty() ? nullptr : ml.err.c_str();
+        return r;
+    };
+    struct SyncIo : zl::BodyIo {  // the launch's bytes come by a copy of their own; the carry is a device copy
+        nx_zlib_decoder* d;
+        bool take(uint8_t* dst, uint32_t m) override {
+            const uint8_t* W = d->win[d->cur].as<uint8_t>();
+            if (!dst) {
+                d->ml.owned.emplace_back(m);
+                dst = d->ml.owned.back().data();
+            }
+            return d->g.d2h(dst, W + kZlibHist, m);
+        }
+        void drop() override { d->ml.owned.clear(); }
+        bool carry(uint32_t h, uint32_t m) override {
+            const uint8_t* W = d->win[d->cur].as<uint8_t>();
+            return hipMemcpyAsync(d->win[d->cur ^ 1].as<uint8_t>() + kZlibHist - h, W + kZlibHist + m - h, h, hipMemcpyDeviceToDevice,
+                                  d->g.s) == hipSuccess &&
+                   d->g.sync();
+        }
+    } io;
+    io.d = d;
+    bool uploaded = false;  // the cumulation is copied to the device once, when a body needs it
+    int step = zl::kWrapper;
+    for (;;) {
+        if (step == zl::kWrapper) step = zl::wrapper_step(d, c);
+        if (step != zl::kBody) break;
         if (!uploaded) {
             if (!g.din.ensure(n) || !g.h2d(g.din.p, in, n)) return finish(NX_ERR_HIP);
             uploaded = true;
         }
-        bool ended = false;
-        for (;;) {
-            uint8_t* W = d->win[d->cur].as<uint8_t>();
-            ZPar p{};
-            p.in_off = rd;
-            p.in_len = (uint32_t)(n - rd < 0x7FFFFFFFu ? n - rd : 0x7FFFFFFFu);
-            p.out_off = kZlibHist - d->hist;
-            p.hist_len = d->hist;
-            p.out_cap = kZlibChunk;
-            p.sum_off = kZlibHist;
-            uint8_t* P = d->par.as<uint8_t>();
-            if (!g.h2d(P, &p, offsetof(ZPar, consumed))) return finish(NX_ERR_HIP);
-            int32_t r = nx_inflate_batch(g.din.as<uint8_t>(), (const uint64_t*)(P + offsetof(ZPar, in_off)),
-                                         (const uint32_t*)(P + offsetof(ZPar, in_len)), W,
-                                         (const uint64_t*)(P + offsetof(ZPar, out_off)),
-                                         (const uint32_t*)(P + offsetof(ZPar, hist_len)),
-                                         (const uint32_t*)(P + offsetof(ZPar, out_cap)), d->st.as<uint8_t>(),
-                                         (uint32_t*)(P + offsetof(ZPar, consumed)), (uint32_t*)(P + offsetof(ZPar, out_len)),
-                                         (int32_t*)(P + offsetof(ZPar, status)), 1, g.s);
+        if (d->st_fresh) {  // inflater.reset() (:321): a new member starts from the all-zero state
+            if (hipMemsetAsync(d->st.p, 0, NX_INFLATE_STATE_BYTES, g.s) != hipSuccess) return finish(NX_ERR_HIP);
+            d->st_fresh = false;
+        }
+        uint8_t* W = d->win[d->cur].as<uint8_t>();
+        ZPar p{};
+        p.in_off = c.rd;
+        p.in_len = (uint32_t)(n - c.rd < 0x7FFFFFFFu ? n - c.rd : 0x7FFFFFFFu);
+        p.out_off = kZlibHist - d->hist;
+        p.hist_len = d->hist;
+        p.out_cap = kZlibChunk;
+        p.sum_off = kZlibHist;
+        uint8_t* P = d->par.as<uint8_t>();
+        if (!g.h2d(P, &p, offsetof(ZPar, consumed))) return finish(NX_ERR_HIP);
+        int32_t r = nx_inflate_batch(g.din.as<uint8_t>(), (const uint64_t*)(P + offsetof(ZPar, in_off)),
+                                     (const uint32_t*)(P + offsetof(ZPar, in_len)), W, (const uint64_t*)(P + offsetof(ZPar, out_off)),
+                                     (const uint32_t*)(P + offsetof(ZPar, hist_len)), (const uint32_t*)(P + offsetof(ZPar, out_cap)),
+                                     d->st.as<uint8_t>(), (uint32_t*)(P + offsetof(ZPar, consumed)),
+                                     (uint32_t*)(P + offsetof(ZPar, out_len)), (int32_t*)(P + offsetof(ZPar, status)), 1, g.s);
+        if (r != NX_OK) return finish(r);
+        if (d->gzip || d->zlib) {  // the checksum of what this launch produced (crc.update, :265-267)
+            auto sum = d->gzip ? nx_crc32_batch : nx_adler32_batch;
+            r = sum(W, (const uint64_t*)(P + offsetof(ZPar, sum_off)), (const uint32_t*)(P + offsetof(ZPar, out_len)),
+                    (uint32_t*)(P + offsetof(ZPar, sum)), 1, g.s);
             if (r != NX_OK) return finish(r);
-            if (d->gzip || d->zlib) {  // the checksum of what this launch produced (crc.update, :265-267)
-                auto sum = d->gzip ? nx_crc32_batch : nx_adler32_batch;
-                r = sum(W, (const uint64_t*)(P + offsetof(ZPar, sum_off)), (const uint32_t*)(P + offsetof(ZPar, out_len)),
-                        (uint32_t*)(P + offsetof(ZPar, sum)), 1, g.s);
-                if (r != NX_OK) return finish(r);
-            }
-            if (!g.d2h(&p.consumed, P + offsetof(ZPar, consumed), sizeof(ZPar) - offsetof(ZPar, consumed)) || !g.sync())
-                return finish(NX_ERR_HIP);
-            if (p.status == NX_ERR_INVALID_ARG || p.status == NX_ERR_INTERNAL) return finish(p.status);
-            const uint32_t m = p.out_len;
-            rd += p.consumed;
-            if (m) {
-                if (d->max_allocation > 0) {
-                    if (acc.size() + m > (size_t)d->max_allocation) {  // prepareDecompressBuffer (ZlibDecoder.java:74-81)
-                        acc.clear();
-                        ml.owned.clear();
-                        d->finished = true;  // decompressionBufferExhausted (:331-333)
-                        ml.err = "Decompression buffer has reached maximum size: " + std::to_string(d->max_allocation);
-                        rd = n;
-                        return finish(NX_ERR_ZLIB_MAX_ALLOCATION);
-                    }
-                    const size_t at = acc.size();
-                    acc.resize(at + m);
-                    if (!g.d2h(acc.data() + at, W + kZlibHist, m)) return finish(NX_ERR_HIP);
-                } else {
-                    ml.owned.emplace_back(m);
-                    if (!g.d2h(ml.owned.back().data(), W + kZlibHist, m)) return finish(NX_ERR_HIP);
-                }
-                if (d->gzip) d->crc = nx_crc32_combine(d->crc, p.sum, m);
-                else if (d->zlib) d->adler = nx_adler32_combine(d->adler, p.sum, m);
-                d->total_out += m;
-                // the last 32 KiB of the stream's output become the other window's history
-                const uint32_t h = d->hist + m < kZlibHist ? d->hist + m : kZlibHist;
-                if (hipMemcpyAsync(d->win[d->cur ^ 1].as<uint8_t>() + kZlibHist - h, W + kZlibHist + m - h, h,
-                                   hipMemcpyDeviceToDevice, g.s) != hipSuccess)
-                    return finish(NX_ERR_HIP);
-                d->hist = h;
-                d->cur ^= 1;
-                if (!g.sync()) return finish(NX_ERR_HIP);
-            }
-            if (p.status < 0) {  // DataFormatException -> DecompressionException("decompression failure") (:302-303)
-                ml.err = "decompression failure";
-                return fail(p.status);
-            }
-            if (p.status == NX_OK) ended = true;
-            if (p.status != NX_INFLATE_OUTPUT_FULL) break;
         }
-        if (!ended) break;  // the inflater needs input
-        if (d->gzip) {
-            d->gz = Z::FOOTER_START;  // :298-301
-        } else if (d->zlib) {
-            d->zs = Z::Z_TRAILER;
-        } else {
-            d->finished = true;  // :284-286
-            rd = n;
-            break;
-        }
+        if (!g.d2h(&p.consumed, P + offsetof(ZPar, consumed), sizeof(ZPar) - offsetof(ZPar, consumed)) || !g.sync())
+            return finish(NX_ERR_HIP);
+        step = zl::body_result(d, c, p.consumed, p.out_len, p.status, p.sum, io);
+        if (step <= zl::kHalt) return finish(step - zl::kHalt);  // the launch itself failed: the decoder is as it was
     }
-    return finish(NX_OK);
+    return finish(step < 0 ? step : NX_OK);
 }

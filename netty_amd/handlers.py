@@ -456,7 +456,8 @@ class Batcher:
         """encode() of any encoder handler as a job: SnappyFrameEncoder (with registered_ptr, an address
         inside memory passed to register(), the bytes are DMA'd from there at flush and must stay valid
         until completion), FastLzFrameEncoder (``reader_index`` as in encode()), LzfEncoder,
-        Lz4FrameEncoder (``op`` 0 encode, 1 encode + flush, 2 encode + close)."""
+        Lz4FrameEncoder (``op`` 0 encode, 1 encode + flush, 2 encode + close), JdkZlibEncoder (``op`` 0
+        encode, 2 encode + finish_encode).  Any other handle is a TypeError."""
         L = _lib.load()
         if isinstance(encoder, FastLzFrameEncoder):
             buf = bytes(reader_index) + bytes(data)
@@ -470,6 +471,11 @@ class Batcher:
             t = L.nx_lz4_frame_encoder_submit(encoder._h, self._h, buf, len(buf), op)
             encoder.raise_for(t)
             return self._ticket(t, "nx_lz4_frame_encoder_submit")
+        if isinstance(encoder, JdkZlibEncoder):
+            buf = bytes(data)
+            return self._ticket(L.nx_zlib_encoder_submit(encoder._h, self._h, buf, len(buf), op), "nx_zlib_encoder_submit")
+        if not isinstance(encoder, SnappyFrameEncoder):
+            raise TypeError(f"Batcher.submit_encode: {type(encoder).__name__} is not an encoder handler of this package")
         if registered_ptr is not None:
             t = L.nx_snappy_frame_encoder_submit(encoder._h, self._h, C.c_void_p(registered_ptr), len(data), 1)
         else:
@@ -482,14 +488,16 @@ class Batcher:
     _DECODE_SUBMIT = {"SnappyFrameDecoder": "nx_snappy_frame_decoder_submit",
                       "FastLzFrameDecoder": "nx_fastlz_frame_decoder_submit",
                       "LzfDecoder": "nx_lzf_decoder_submit",
-                      "Lz4FrameDecoder": "nx_lz4_frame_decoder_submit"}
+                      "Lz4FrameDecoder": "nx_lz4_frame_decoder_submit",
+                      "JdkZlibDecoder": "nx_zlib_decoder_submit"}
 
     def submit_decode(self, decoder, data) -> int:
         """decode() of any decoder handler over its cumulation + data as a job; the consumed bytes leave
         the cumulation now (ByteToMessageDecoder.channelRead)."""
         L = _lib.load()
-        fn = next(v for k, v in self._DECODE_SUBMIT.items() if type(decoder).__name__ == k or
-                  any(c.__name__ == k for c in type(decoder).__mro__))
+        fn = next((v for k, v in self._DECODE_SUBMIT.items() if any(c.__name__ == k for c in type(decoder).__mro__)), None)
+        if fn is None:
+            raise TypeError(f"Batcher.submit_decode: {type(decoder).__name__} is not a decoder handler of this package")
         decoder._cum += bytes(data)
         buf = bytes(decoder._cum)
         consumed = C.c_size_t(0)
@@ -540,6 +548,7 @@ class Batcher:
             msg = err.value.decode() if err.value else _lib.status_string(rc)
             e = DecoderException(msg) if msg.startswith("java.lang.") else DecompressionException(msg)
             e.decoded = out
+            e.status = rc
             raise e
         return out
 
