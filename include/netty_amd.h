@@ -230,6 +230,18 @@ size_t nx_deflate_max_compressed_length(size_t n);
 int32_t nx_deflate_encode_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
                                 const uint64_t* out_off, uint32_t* out_len, int32_t* status, uint32_t n, int32_t level,
                                 void* stream);
+/* The same with a history prefix per chunk: prefix_len (a device array; NULL: all zero, which is
+ * nx_deflate_encode_batch, kernels and bytes) gives chunk i the prefix_len[i] bytes right before it in
+ * the arena, in[in_off[i] - prefix_len[i], in_off[i]), as history: matches may start there (and run on
+ * into the chunk), none of it is emitted, and the output inflates to the chunk with that history as the
+ * window's content (zlib: inflateSetDictionary / zdict).  What deflateSetDictionary gives zlib's matcher;
+ * preset dictionaries (nx_zlib_encoder_new_dict) are its user.  prefix_len[i] <= 32768, prefix_len[i] +
+ * in_len[i] <= 65536 and prefix_len[i] <= in_off[i], else status[i] = NX_ERR_INVALID_ARG and
+ * out_len[i] = 0 for that chunk alone.  Level 0 checks the limits and matches nothing; an empty chunk
+ * writes nothing. */
+int32_t nx_deflate_encode_batch_ex(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint32_t* prefix_len,
+                                   uint8_t* out, const uint64_t* out_off, uint32_t* out_len, int32_t* status, uint32_t n,
+                                   int32_t level, void* stream);
 
 /* Replaces Inflater.inflate(...) as JdkZlibDecoder.decode calls it (JdkZlibDecoder.java:254-296) for n
  * independent raw deflate (RFC 1951) streams, each resumable at symbol granularity: a call takes
@@ -460,7 +472,15 @@ int64_t nx_lz4_frame_encoder_close(nx_lz4_frame_encoder* e, uint8_t* out, size_t
 
 /* JdkZlibEncoder(wrapper, compressionLevel)  JdkZlibEncoder.java:123-137,214-276,308-340.  wrapper is
  * ZlibWrapper's ordinal (0 ZLIB, 1 GZIP, 2 NONE); NULL for 3 (ZLIB_OR_NONE, :128-132) and for a level
- * outside -1..9 (:124-125).  The preset-dictionary constructors are not offered.
+ * outside -1..9 (:124-125).
+ * _new_dict: JdkZlibEncoder(compressionLevel, dictionary) (:149-177), always ZLIB (:173); NULL for a NULL
+ * dictionary (checkNotNull) or a bad level.  The header is what zlib writes after deflateSetDictionary:
+ * with a non-empty dictionary FLG carries FDICT and the check bits for it, and DICTID, the Adler32 of the
+ * whole dictionary, follows most significant byte first (6 bytes); an empty dictionary gives the plain
+ * header.  Only the dictionary's last min(dict_len, 32768) bytes can be matched, and only by the
+ * stream's first non-empty slice, which is cut to 65536 less that many bytes and takes them as its
+ * history prefix (nx_deflate_encode_batch_ex); later slices are independent as without a dictionary.
+ * The trailer's Adler32 covers the data only.
  * _encode: an empty message writes nothing (:220-223); otherwise the header once (GZIP: the ten bytes
  * of :59; ZLIB: the two bytes Deflater writes for the level; NONE: none), then the message deflated in
  * 64 KiB slices of one batch, each closed by a sync flush, so the bytes written so far always
@@ -471,6 +491,7 @@ int64_t nx_lz4_frame_encoder_close(nx_lz4_frame_encoder* e, uint8_t* out, size_t
  * _close returns 0.  Returns bytes written or a negative NX_ERR_*. */
 typedef struct nx_zlib_encoder nx_zlib_encoder;
 nx_zlib_encoder* nx_zlib_encoder_new(int32_t wrapper, int32_t level);
+nx_zlib_encoder* nx_zlib_encoder_new_dict(int32_t level, const uint8_t* dict, size_t dict_len);
 void nx_zlib_encoder_free(nx_zlib_encoder* e);
 size_t nx_zlib_max_encoded_length(size_t n);
 int64_t nx_zlib_encoder_encode(nx_zlib_encoder* e, const uint8_t* in, size_t n, uint8_t* out, size_t out_cap);
@@ -479,8 +500,14 @@ int64_t nx_zlib_encoder_close(nx_zlib_encoder* e, uint8_t* out, size_t out_cap);
 /* JdkZlibDecoder(wrapper, decompressConcatenated, maxAllocation)  JdkZlibDecoder.java:117-160,211-312
  * (decode), :316-520 (the GZIP header and footer states), ZlibDecoder.java:49,74-81 (maxAllocation).
  * wrapper is ZlibWrapper's ordinal 0..3; ZLIB_OR_NONE decides on the first two bytes (looksLikeZlib,
- * :529-532).  NULL for max_allocation < 0 or a wrapper outside 0..3.  The preset-dictionary
- * constructors are not offered: a zlib header with FDICT fails as :276-280.
+ * :529-532).  NULL for max_allocation < 0 or a wrapper outside 0..3.  Without a dictionary a zlib
+ * header with FDICT fails as :276-280 (NX_ERR_ZLIB_NEED_DICT).
+ * _new_dict: JdkZlibDecoder(dictionary, maxAllocation) (:96-111): ZLIB, not concatenated; NULL for a NULL
+ * dictionary.  A stream without FDICT decodes as with nx_zlib_decoder_new.  On FDICT the handle reads
+ * DICTID: if it is not the dictionary's Adler32 the call fails with NX_ERR_ZLIB_DICT_MISMATCH
+ * (Inflater.setDictionary's IllegalArgumentException; the text is not pinned) and what follows is
+ * skipped; else the dictionary's last min(dict_len, 32768) bytes become the window's history (a device
+ * copy; the inflate kernel is unchanged) and the Adler32 of the trailer covers the output only.
  * _decode as nx_lzf_decoder_decode: in[0..n) is the cumulation, *consumed the bytes read.  The GZIP
  * and ZLIB wrappers are parsed on the host; the deflate body runs through nx_inflate_batch (n = 1)
  * over a device window of 32 KiB of history plus an output chunk, until it needs input, ends or fails;
@@ -495,6 +522,7 @@ int64_t nx_zlib_encoder_close(nx_zlib_encoder* e, uint8_t* out, size_t out_cap);
  * with the reference's message.  After the end of the stream (and after a failure) input is skipped. */
 typedef struct nx_zlib_decoder nx_zlib_decoder;
 nx_zlib_decoder* nx_zlib_decoder_new(int32_t wrapper, int32_t decompress_concatenated, int32_t max_allocation);
+nx_zlib_decoder* nx_zlib_decoder_new_dict(const uint8_t* dict, size_t dict_len, int32_t max_allocation);
 void nx_zlib_decoder_free(nx_zlib_decoder* d);
 int32_t nx_zlib_decoder_decode(nx_zlib_decoder* d, const uint8_t* in, size_t n, size_t* consumed,
                                const nx_msg** msgs, size_t* n_msgs, const char** err_msg);

@@ -124,6 +124,11 @@
 #define NX_ERR_ZLIB_NEED_DICT             (-75)
 /* ZlibDecoder.java:74-81  "Decompression buffer has reached maximum size: %d" */
 #define NX_ERR_ZLIB_MAX_ALLOCATION        (-76)
+/* JdkZlibDecoder(dictionary) (:281): the stream's DICTID is not the Adler32 of the handle's dictionary.
+ * Inflater.setDictionary throws IllegalArgumentException, which ByteToMessageDecoder wraps in
+ * DecoderException (not DecompressionException).  The text is NOT pinned: zlib sets no message for this
+ * error and no JVM run recorded Java's. */
+#define NX_ERR_ZLIB_DICT_MISMATCH         (-77)
 /* Not errors: why a stream of nx_inflate_batch stopped before the end of its final block. */
 #define NX_INFLATE_NEED_INPUT             2
 #define NX_INFLATE_OUTPUT_FULL            3

@@ -195,15 +195,23 @@ def deflate_max_compressed_length(n: int) -> int:
     return _lib.load().nx_deflate_max_compressed_length(n)
 
 
-def deflate_encode(inp, in_off, in_len, out, out_off, level: int = 6):
+def deflate_encode(inp, in_off, in_len, out, out_off, level: int = 6, prefix_len=None):
     """Raw deflate with a sync flush per chunk of at most 65536 bytes (nx_deflate_encode_batch): slots
-    of deflate_max_compressed_length bytes; level as java.util.zip.Deflater.  Returns (out_len, status)."""
+    of deflate_max_compressed_length bytes; level as java.util.zip.Deflater.  prefix_len (an int32 tensor;
+    nx_deflate_encode_batch_ex): chunk i may match into the prefix_len[i] <= 32768 bytes before it in inp,
+    prefix_len[i] + in_len[i] <= 65536.  Returns (out_len, status)."""
     n = in_len.numel()
     dev = inp.device
     out_len = torch.empty(n, dtype=torch.int32, device=dev)
     status = torch.empty(n, dtype=torch.int32, device=dev)
-    _chk(_lib.load().nx_deflate_encode_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_len),
-                                             _ptr(status), n, int(level), _stream()), "nx_deflate_encode_batch")
+    if prefix_len is None:
+        _chk(_lib.load().nx_deflate_encode_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_len),
+                                                 _ptr(status), n, int(level), _stream()), "nx_deflate_encode_batch")
+    else:
+        assert prefix_len.numel() == n and prefix_len.dtype == torch.int32
+        _chk(_lib.load().nx_deflate_encode_batch_ex(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(prefix_len), _ptr(out),
+                                                    _ptr(out_off), _ptr(out_len), _ptr(status), n, int(level), _stream()),
+             "nx_deflate_encode_batch_ex")
     return out_len, status
 
 

@@ -344,6 +344,14 @@ struct nx_zlib_encoder {
     uint32_t crc = 0;           // GZIP: CRC32 of everything encoded (:58,262-264)
     uint32_t adler = 1;         // ZLIB: the Deflater's Adler32
     uint64_t total_in = 0;      // deflater.getTotalIn() (:332)
+    // JdkZlibEncoder(level, dictionary) (:149-177): deflater.setDictionary.  The header carries FDICT and
+    // DICTID (the Adler32 of the whole dictionary) when it is not empty; its last 32 KiB at most can be
+    // matched, by the stream's first non-empty slice only (dict_armed until then), which is staged behind
+    // them and takes them as its history prefix (nx_deflate_encode_batch_ex).
+    bool has_dict = false, dict_armed = false;
+    uint32_t dictid = 1;
+    std::vector<uint8_t> dict;  // the matchable tail: what a batcher job stages in front of the slice
+    nx::h::DevBuf ddict;        // the same on the device, for the synchronous encode
     // Batcher: write_header, finished and total_in advance at submit; crc / adler are folded when a job is
     // applied, in flush order, so the synchronous calls are refused while jobs are unapplied (pending).  A
     // job holds a reference: nx_zlib_encoder_free drops the owner's.
@@ -378,6 +386,11 @@ struct nx_zlib_decoder {
     int cur = 0;                   // the current window
     nx::h::DevBuf win[2], st, par;
     bool st_fresh = false;         // a member reset since the last body step: that step starts from the all-zero state
+    // JdkZlibDecoder(dictionary) (:96-111): inflater.setDictionary when the header asks (:276-282).  dict_n
+    // bytes, the dictionary's last 32 KiB at most, become the window's history once DICTID matches dictid.
+    bool has_dict = false;
+    uint32_t dictid = 1, dict_n = 0;
+    nx::h::DevBuf ddict;
     // Batcher (batcher.cpp): the batcher this decoder's jobs run on, once one was submitted (the synchronous
     // decode is refused from then on); the bytes its jobs have not used yet; the owner's reference plus one
     // per job.
@@ -413,6 +426,18 @@ enum : int { kStop = 0, kBody = 1, kWrapper = 2, kHalt = -1000000 };
 int wrapper_step(nx_zlib_decoder* d, Call& c);
 int body_result(nx_zlib_decoder* d, Call& c, uint32_t consumed, uint32_t out_len, int32_t status, uint32_t sum, BodyIo& io);
 size_t write_header(const nx_zlib_encoder* e, uint8_t* out);  // JdkZlibEncoder's header bytes (at most 10)
+// The slices of an n-byte message: the first is cut so that it and the armed dictionary tail (`tail` bytes,
+// 0 when none) stay within one chunk of the matcher, the rest every 64 KiB.
+template <class F>
+inline void for_slices(size_t n, uint32_t tail, F&& f) {  // f(offset in the message, length, prefix_len)
+    size_t q = 0;
+    if (tail && n) {
+        const size_t first = n < 65536u - tail ? n : 65536u - tail;
+        f(q, (uint32_t)first, tail);
+        q = first;
+    }
+    for (; q < n; q += 65536) f(q, (uint32_t)(n - q < 65536 ? n - q : 65536), 0u);
+}
 }  // namespace zl
 }  // namespace nx
 

@@ -1312,8 +1312,12 @@ int32_t run_alt(const Flush& F) {
         const auto& L = F.al[c];
         if (!L.n) continue;
         const uint32_t r0 = c == DFL_M ? F.al[DFL_S].n : 0u;
-        r = nx_deflate_encode_batch(F.din, F(L.off), F(L.len), F.aslots, F(L.slot), F(F.dfolen) + r0, F(F.dfst) + r0, L.n,
-                                    c == DFL_S ? 0 : 6, s);
+        // the matcher list carries each slice's prefix_len (aux: a dictionary handle's first slice); a list
+        // without one launches the plain entry point's kernels
+        bool prefixed = false;
+        for (uint32_t i = 0; c == DFL_M && i < L.n && !prefixed; ++i) prefixed = F.host(L.aux)[i] != 0u;
+        r = nx_deflate_encode_batch_ex(F.din, F(L.off), F(L.len), prefixed ? F(L.aux) : nullptr, F.aslots, F(L.slot),
+                                       F(F.dfolen) + r0, F(F.dfst) + r0, L.n, c == DFL_S ? 0 : 6, s);
         if (r != NX_OK) return r;
         b->launches += 1;
     }
@@ -2441,11 +2445,16 @@ extern "C" int64_t nx_zlib_encoder_submit(nx_zlib_encoder* e, nx_batcher* b, con
         bt->apc.push_back(P);
         out_need += len;
     };
+    // a dictionary handle's first non-empty message is staged behind the dictionary's tail, the history
+    // prefix of its first slice
+    const uint32_t tail = n && !e->finished && e->dict_armed ? (uint32_t)e->dict.size() : 0u;
     uint64_t off = 0;
     if (n) {
-        uint8_t* stg = bt->stage(n, &off);
+        uint8_t* stg = bt->stage(tail + n, &off);
         if (!stg) return NX_ERR_HIP;
-        nx::copy_bytes(stg, in, n);
+        nx::copy_bytes(stg, e->dict.data(), tail);
+        nx::copy_bytes(stg + tail, in, n);
+        off += tail;
     }
     const bool close = op == 2 && !e->finished;
     if (e->finished) {  // out.writeBytes(uncompressed) (:215-218); a second close writes nothing (:309-312)
@@ -2460,8 +2469,7 @@ extern "C" int64_t nx_zlib_encoder_submit(nx_zlib_encoder* e, nx_batcher* b, con
     } else {
         uint8_t hdr[16];
         if (e->write_header && (n || close)) constant(hdr, nx::zl::write_header(e, hdr));
-        for (size_t q = 0; q < n; q += 65536) {
-            const uint32_t len = (uint32_t)(n - q < 65536 ? n - q : 65536);
+        nx::zl::for_slices(n, tail, [&](size_t q, uint32_t len, uint32_t pre) {
             const bool stored = e->level == 0;
             AltPiece P{};
             P.kind = nx::bt::AK_DFL_ENC;
@@ -2472,10 +2480,10 @@ extern "C" int64_t nx_zlib_encoder_submit(nx_zlib_encoder* e, nx_batcher* b, con
             P.slot = bt->aslots;
             const size_t cap = nx_deflate_max_compressed_length(len);
             bt->aslots += (cap + 127) & ~(size_t)127;
-            P.res = push_list(bt->alt[stored ? DFL_S : DFL_M], P.src, len, P.slot, 0);
+            P.res = push_list(bt->alt[stored ? DFL_S : DFL_M], P.src, len, P.slot, pre);  // aux: the slice's prefix_len
             bt->apc.push_back(P);
             out_need += cap;
-        }
+        });
         if (close) {  // the final block (an empty fixed-Huffman block), then the trailer's place
             const uint8_t fin[10] = {0x03, 0x00};
             j->ztrailer = e->wrapper == 0 ? 4u : e->wrapper == 1 ? 8u : 0u;
@@ -2495,6 +2503,7 @@ extern "C" int64_t nx_zlib_encoder_submit(nx_zlib_encoder* e, nx_batcher* b, con
     if (!e->finished) {
         if (had_header) e->write_header = false;
         e->total_in += n;
+        if (n) e->dict_armed = false;
         if (close) e->finished = true;
     }
     return t;

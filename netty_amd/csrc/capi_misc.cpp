@@ -56,6 +56,7 @@ extern "C" const char* nx_status_string(int32_t s) {
         case NX_ERR_ZLIB_METHOD: return "unknown compression method";
         case NX_ERR_ZLIB_WINDOW: return "invalid window size";
         case NX_ERR_ZLIB_NEED_DICT: return "decompression failure, unable to set dictionary as non was specified";
+        case NX_ERR_ZLIB_DICT_MISMATCH: return "java.lang.IllegalArgumentException";
         case NX_ERR_ZLIB_MAX_ALLOCATION: return "Decompression buffer has reached maximum size";
         case NX_INFLATE_NEED_INPUT: return "inflate stopped: more input needed";
         case NX_INFLATE_OUTPUT_FULL: return "inflate stopped: the next symbol does not fit the output";

@@ -41,11 +41,26 @@ typedef uint32_t __attribute__((aligned(1))) u32u;
 __device__ __forceinline__ uint32_t ld32(const uint8_t* p) { return *reinterpret_cast<const u32u*>(p); }
 
 // ---------------------------------------------------------------------------------------- pass 1
-__device__ void match_chunk(const uint8_t* __restrict__ in, uint32_t n, uint64_t* __restrict__ table, uint32_t* __restrict__ hdr,
-                            uint32_t stamp) {
+//
+// PREFIX: `in` is the chunk's history followed by the chunk, one flat range of n = pre + length bytes
+// (at most 65536, so a position still fits the entry's 16 bits).  The pre history positions are entered
+// first (plain stores in rising order: a slot keeps the nearest occurrence; the last three read their
+// word across the boundary), then matching starts at pre.  Tokens and the literal tail are the chunk's
+// own: a distance may reach into the history, nothing else refers to it.
+template <bool PREFIX>
+__device__ __forceinline__ void match_chunk(const uint8_t* __restrict__ in, uint32_t n, uint32_t pre, uint64_t* __restrict__ table,
+                                            uint32_t* __restrict__ hdr, uint32_t stamp) {
     uint32_t* tok32 = hdr + 2;
     const uint32_t stag = stamp << 16;
     uint32_t nt = 0, pend = 0, ip = 0;
+    if (PREFIX) {
+        for (uint32_t q = 0; q < pre && q + 4u <= n; ++q) {
+            const uint32_t wq = ld32(in + q);
+            __hip_atomic_store(table + ((wq * 2654435761u) >> (32u - kHashLog)), ((uint64_t)(stag | q) << 32) | wq,
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        ip = pre;
+    }
 #define NX_PUT_TOKEN(t)                                      \
     do {                                                     \
         if (nt & 1u) tok32[nt >> 1] = pend | ((t) << 16);    \
@@ -92,7 +107,7 @@ __device__ void match_chunk(const uint8_t* __restrict__ in, uint32_t n, uint64_t
 #undef NX_PUT_TOKEN
     if (nt & 1u) tok32[nt >> 1] = pend;
     hdr[0] = nt;
-    hdr[1] = ip;  // bytes [ip, n) are literals pass 2 reads from the input
+    hdr[1] = PREFIX ? ip - pre : ip;  // the chunk's bytes from here on are literals pass 2 reads from the input
 }
 
 template <bool SPREAD>
@@ -105,7 +120,29 @@ __global__ void __launch_bounds__(256) k_deflate_match(const uint8_t* __restrict
     const uint32_t len = in_len[tid];
     if (len == 0 || len > kMaxChunk) return;
     uint8_t* slot = workspace + (size_t)tid * kSlotBytes;
-    match_chunk(in + in_off[tid], len, reinterpret_cast<uint64_t*>(slot), reinterpret_cast<uint32_t*>(slot + kTokOff), stamp);
+    match_chunk<false>(in + in_off[tid], len, 0u, reinterpret_cast<uint64_t*>(slot), reinterpret_cast<uint32_t*>(slot + kTokOff), stamp);
+}
+
+// A chunk's history must lie in the arena, fit the window and leave its positions 16 bits.
+__device__ __forceinline__ bool prefix_ok(uint32_t pre, uint32_t len, uint64_t off) {
+    return pre <= kMaxDist && pre + len <= kMaxChunk && pre <= off;
+}
+
+// The same with a history prefix per chunk: the prefix_len[i] bytes before in_off[i] (nx_deflate_encode_batch_ex).
+template <bool SPREAD>
+__global__ void __launch_bounds__(256) k_deflate_match_prefix(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
+                                                              const uint32_t* __restrict__ in_len,
+                                                              const uint32_t* __restrict__ prefix_len, uint32_t n,
+                                                              uint8_t* __restrict__ workspace, uint32_t stamp) {
+    uint32_t tid, nthreads;
+    if (!chunk_slot<SPREAD>(tid, nthreads)) return;
+    if (tid >= n) return;
+    const uint32_t len = in_len[tid], pre = prefix_len[tid];
+    const uint64_t off = in_off[tid];
+    if (len == 0 || len > kMaxChunk || !prefix_ok(pre, len, off)) return;
+    uint8_t* slot = workspace + (size_t)tid * kSlotBytes;
+    match_chunk<true>(in + (off - pre), pre + len, pre, reinterpret_cast<uint64_t*>(slot), reinterpret_cast<uint32_t*>(slot + kTokOff),
+                      stamp);
 }
 
 // ---------------------------------------------------------------------------------------- pass 2
@@ -307,7 +344,9 @@ __device__ __forceinline__ void finish_bits(BitOut& o, uint32_t lane) {
     __syncthreads();
 }
 
-// One chunk by one wave (a block of 64): returns the bytes written.
+// One chunk by one wave (a block of 64): returns the bytes written.  (A template so that each of the two
+// kernels below has an instance of its own, inlined as into its one caller.)
+template <bool PREFIX>
 __device__ uint32_t emit_chunk(Lds& L, const uint8_t* __restrict__ in, uint32_t n, const uint32_t* __restrict__ hdr,
                                uint8_t* __restrict__ dst, bool stored_only, uint32_t lane) {
     const uint32_t nblk = (n + 65534u) / 65535u;
@@ -466,11 +505,39 @@ __global__ void __launch_bounds__(64) k_deflate_emit(const uint8_t* __restrict__
         const uint32_t len = in_len[c];
         uint32_t w = 0;
         if (len != 0u && len <= kMaxChunk)
-            w = emit_chunk(L, in + in_off[c], len, reinterpret_cast<const uint32_t*>(workspace + (size_t)c * kSlotBytes + kTokOff),
+            w = emit_chunk<false>(L, in + in_off[c], len, reinterpret_cast<const uint32_t*>(workspace + (size_t)c * kSlotBytes + kTokOff),
                            out + out_off[c], stored_only != 0u, lane);
         if (lane == 0u) {
             out_len[c] = w;
             status[c] = len <= kMaxChunk ? NX_OK : NX_ERR_INVALID_ARG;
+        }
+        __syncthreads();
+    }
+}
+
+// Pass 2 beside k_deflate_match_prefix: a chunk whose prefix breaks a limit writes nothing and fails
+// alone (pass 1 left its slot alone).  The prefix itself is never read here.
+__global__ void __launch_bounds__(64) k_deflate_emit_prefix(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
+                                                            const uint32_t* __restrict__ in_len,
+                                                            const uint32_t* __restrict__ prefix_len, uint8_t* __restrict__ out,
+                                                            const uint64_t* __restrict__ out_off, uint32_t* __restrict__ out_len,
+                                                            int32_t* __restrict__ status, uint32_t n,
+                                                            const uint8_t* __restrict__ workspace, uint32_t stored_only) {
+    __shared__ Lds L;
+    const uint32_t lane = threadIdx.x;
+    L.ring[lane] = 0;
+    L.ring[lane + 64u] = 0;
+    __syncthreads();
+    for (uint32_t c = blockIdx.x; c < n; c += gridDim.x) {
+        const uint32_t len = in_len[c];
+        const bool ok = len <= kMaxChunk && prefix_ok(prefix_len[c], len, in_off[c]);
+        uint32_t w = 0;
+        if (len != 0u && ok)
+            w = emit_chunk<true>(L, in + in_off[c], len, reinterpret_cast<const uint32_t*>(workspace + (size_t)c * kSlotBytes + kTokOff),
+                           out + out_off[c], stored_only != 0u, lane);
+        if (lane == 0u) {
+            out_len[c] = w;
+            status[c] = ok ? NX_OK : NX_ERR_INVALID_ARG;
         }
         __syncthreads();
     }
@@ -494,9 +561,13 @@ extern "C" size_t nx_deflate_max_compressed_length(size_t n) { return n + 5 * ((
 // 256-276, 308-340) for n independent chunks of at most 65536 bytes: chunk i's output is a
 // byte-aligned run of non-final deflate blocks ending in 00 00 FF FF (nothing for an empty chunk).
 // level as java.util.zip.Deflater: 0 stored blocks, 1..9 and -1 the one matcher.
-extern "C" int32_t nx_deflate_encode_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
-                                           const uint64_t* out_off, uint32_t* out_len, int32_t* status, uint32_t n, int32_t level,
-                                           void* stream) {
+//
+// prefix_len (nx_deflate_encode_batch_ex; NULL: none, the kernels of nx_deflate_encode_batch): chunk i's
+// history is the prefix_len[i] bytes before in_off[i], which matches may refer to and which are never
+// emitted (what deflateSetDictionary gives zlib's matcher).
+namespace {
+int32_t deflate_encode(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint32_t* prefix_len, uint8_t* out,
+                       const uint64_t* out_off, uint32_t* out_len, int32_t* status, uint32_t n, int32_t level, void* stream) {
     NX_CLEAR_STALE_ERROR();
     if (level < -1 || level > 9) return NX_ERR_INVALID_ARG;
     if (n == 0) return NX_OK;
@@ -514,25 +585,51 @@ extern "C" int32_t nx_deflate_encode_batch(const uint8_t* in, const uint64_t* in
         const uint32_t left = (uint32_t)(n - base);
         const nx::LaneGrid g = nx::ws_grid(nx::WsKind::DeflateEnc, left, cus, W.slots);
         const uint32_t m = (uint32_t)(left < g.slots ? left : g.slots);
+        const uint32_t* pre = prefix_len ? prefix_len + base : nullptr;
         if (level != 0) {
             if (W.stamp + 1u >= kMaxStamp) {
                 NX_HIP_CHECK(hipMemsetAsync(W.p, 0, W.slots * (size_t)nx::deflate::kSlotBytes, st));
                 W.stamp = 0;
             }
             W.stamp += 1u;
-            if (g.spread)
+            if (pre) {
+                if (g.spread)
+                    hipLaunchKernelGGL(nx::deflate::k_deflate_match_prefix<true>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base,
+                                       in_len + base, pre, m, ws, W.stamp);
+                else
+                    hipLaunchKernelGGL(nx::deflate::k_deflate_match_prefix<false>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base,
+                                       in_len + base, pre, m, ws, W.stamp);
+            } else if (g.spread) {
                 hipLaunchKernelGGL(nx::deflate::k_deflate_match<true>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base,
                                    in_len + base, m, ws, W.stamp);
-            else
+            } else {
                 hipLaunchKernelGGL(nx::deflate::k_deflate_match<false>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base,
                                    in_len + base, m, ws, W.stamp);
+            }
             NX_HIP_CHECK(hipGetLastError());
         }
         const unsigned waves = (unsigned)cus * 16u;
-        hipLaunchKernelGGL(nx::deflate::k_deflate_emit, dim3(m < waves ? m : waves), dim3(64), 0, st, in, in_off + base, in_len + base,
-                           out, out_off + base, out_len + base, status + base, m, ws, level == 0 ? 1u : 0u);
+        if (pre)
+            hipLaunchKernelGGL(nx::deflate::k_deflate_emit_prefix, dim3(m < waves ? m : waves), dim3(64), 0, st, in, in_off + base,
+                               in_len + base, pre, out, out_off + base, out_len + base, status + base, m, ws, level == 0 ? 1u : 0u);
+        else
+            hipLaunchKernelGGL(nx::deflate::k_deflate_emit, dim3(m < waves ? m : waves), dim3(64), 0, st, in, in_off + base,
+                               in_len + base, out, out_off + base, out_len + base, status + base, m, ws, level == 0 ? 1u : 0u);
         NX_HIP_CHECK(hipGetLastError());
         base += m;
     }
     return NX_OK;
+}
+}  // namespace
+
+extern "C" int32_t nx_deflate_encode_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                                           const uint64_t* out_off, uint32_t* out_len, int32_t* status, uint32_t n, int32_t level,
+                                           void* stream) {
+    return deflate_encode(in, in_off, in_len, nullptr, out, out_off, out_len, status, n, level, stream);
+}
+
+extern "C" int32_t nx_deflate_encode_batch_ex(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                                              const uint32_t* prefix_len, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
+                                              int32_t* status, uint32_t n, int32_t level, void* stream) {
+    return deflate_encode(in, in_off, in_len, prefix_len, out, out_off, out_len, status, n, level, stream);
 }

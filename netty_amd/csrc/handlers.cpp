@@ -942,10 +942,36 @@ size_t nx::zl::write_header(const nx_zlib_encoder* e, uint8_t* out) {
         const int32_t l = e->level;
         out[0] = 0x78;
         out[1] = l == 0 || l == 1 ? 0x01 : l >= 2 && l <= 5 ? 0x5E : l == 6 || l == -1 ? 0x9C : 0xDA;
-        return 2;
+        if (!e->has_dict || e->dict.empty()) return 2;
+        // after deflateSetDictionary with a non-empty dictionary (zlib deflate.c, INIT_STATE): PRESET_DICT,
+        // the check bits again, then DICTID most significant byte first
+        const uint32_t flg = (out[1] & 0xC0u) | 0x20u;
+        out[1] = (uint8_t)(flg + 31u - ((0x7800u | flg) % 31u));
+        for (int k = 0; k < 4; ++k) out[2 + k] = (uint8_t)(e->dictid >> (8 * (3 - k)));
+        return 6;
     }
     return 0;
 }
+
+namespace {
+// java.util.zip.Adler32 over a dictionary on the host (once per handle)
+uint32_t adler32_host(const uint8_t* p, size_t n) {
+    uint32_t a = 1, b = 0;
+    while (n) {
+        const size_t k = n < 5552 ? n : 5552;  // zlib's NMAX: the sums stay below 2^32
+        for (size_t i = 0; i < k; ++i) {
+            a += p[i];
+            b += a;
+        }
+        a %= 65521u;
+        b %= 65521u;
+        p += k;
+        n -= k;
+    }
+    return (b << 16) | a;
+}
+constexpr size_t kZlibDictMax = 32768;  // what of a dictionary the window can hold
+}  // namespace
 
 extern "C" nx_zlib_encoder* nx_zlib_encoder_new(int32_t wrapper, int32_t level) {
     if (level < -1 || level > 9) return nullptr;     // checkInRange (:124-125)
@@ -957,6 +983,22 @@ extern "C" nx_zlib_encoder* nx_zlib_encoder_new(int32_t wrapper, int32_t level) 
     }
     e->wrapper = wrapper;
     e->level = level;
+    return e;
+}
+// JdkZlibEncoder(compressionLevel, dictionary) (:149-177): always ZlibWrapper.ZLIB (:173)
+extern "C" nx_zlib_encoder* nx_zlib_encoder_new_dict(int32_t level, const uint8_t* dict, size_t dict_len) {
+    if (!dict) return nullptr;  // checkNotNull(dictionary, "dictionary") (:172)
+    nx_zlib_encoder* e = nx_zlib_encoder_new(0, level);
+    if (!e) return nullptr;
+    const size_t tail = dict_len < kZlibDictMax ? dict_len : kZlibDictMax;
+    e->has_dict = true;
+    e->dict_armed = tail != 0;
+    e->dictid = adler32_host(dict, dict_len);
+    e->dict.assign(dict + (dict_len - tail), dict + dict_len);
+    if (tail && (!e->ddict.ensure(tail) || !e->g.h2d(e->ddict.p, e->dict.data(), tail) || !e->g.sync())) {
+        delete e;
+        return nullptr;
+    }
     return e;
 }
 extern "C" void nx_zlib_encoder_free(nx_zlib_encoder* e) { nx_zlib_encoder_unref(e); }
@@ -973,22 +1015,29 @@ extern "C" int64_t nx_zlib_encoder_encode(nx_zlib_encoder* e, const uint8_t* in,
     }
     if (n == 0) return 0;  // :220-223
     if (out_cap < nx_zlib_max_encoded_length(n)) return NX_ERR_INVALID_ARG;
-    const uint32_t ns = (uint32_t)((n + kZlibSlice - 1) / kZlibSlice);
-    std::vector<uint64_t> ioff(ns), ooff(ns);
-    std::vector<uint32_t> ilen(ns);
+    // the stream's first slice lies behind the dictionary's tail (its history prefix) in din
+    const uint32_t tail = e->dict_armed ? (uint32_t)e->dict.size() : 0u;
+    std::vector<uint64_t> ioff, ooff;
+    std::vector<uint32_t> ilen, plen;
     uint64_t oc = 0;
-    for (uint32_t i = 0; i < ns; ++i) {
-        ioff[i] = (uint64_t)i * kZlibSlice;
-        ilen[i] = (uint32_t)(n - ioff[i] < kZlibSlice ? n - ioff[i] : kZlibSlice);
-        ooff[i] = oc;
-        oc += (nx_deflate_max_compressed_length(ilen[i]) + 127) & ~(size_t)127;
-    }
+    nx::zl::for_slices(n, tail, [&](size_t q, uint32_t len, uint32_t pre) {
+        ioff.push_back(tail + q);
+        ilen.push_back(len);
+        plen.push_back(pre);
+        ooff.push_back(oc);
+        oc += (nx_deflate_max_compressed_length(len) + 127) & ~(size_t)127;
+    });
+    const uint32_t ns = (uint32_t)ilen.size();
     Gpu& g = e->g;
-    if (!g.din.ensure(n) || !g.dout.ensure(oc) || !g.a0.ensure(8ull * ns) || !g.a1.ensure(8ull * ns) || !g.a2.ensure(4ull * ns) ||
-        !g.a3.ensure(4ull * ns) || !g.a4.ensure(4ull * ns) || !g.a5.ensure(4ull * ns))
+    if (!g.din.ensure(tail + n) || !g.dout.ensure(oc) || !g.a0.ensure(8ull * ns) || !g.a1.ensure(8ull * ns) ||
+        !g.a2.ensure(4ull * ns) || !g.a3.ensure(4ull * ns) || !g.a4.ensure(4ull * ns) || !g.a5.ensure(4ull * ns) ||
+        (tail && !g.a6.ensure(4ull * ns)))
         return NX_ERR_HIP;
-    bool ok = g.h2d(g.din.p, in, n) && g.h2d(g.a0.p, ioff.data(), 8ull * ns) && g.h2d(g.a1.p, ooff.data(), 8ull * ns) &&
-              g.h2d(g.a2.p, ilen.data(), 4ull * ns);
+    bool ok = g.h2d(g.din.as<uint8_t>() + tail, in, n) && g.h2d(g.a0.p, ioff.data(), 8ull * ns) &&
+              g.h2d(g.a1.p, ooff.data(), 8ull * ns) && g.h2d(g.a2.p, ilen.data(), 4ull * ns);
+    if (tail)
+        ok = ok && g.h2d(g.a6.p, plen.data(), 4ull * ns) &&
+             hipMemcpyAsync(g.din.p, e->ddict.p, tail, hipMemcpyDeviceToDevice, g.s) == hipSuccess;
     if (!ok) return NX_ERR_HIP;
     int32_t r = NX_OK;
     if (e->wrapper == 1)
@@ -996,8 +1045,13 @@ extern "C" int64_t nx_zlib_encoder_encode(nx_zlib_encoder* e, const uint8_t* in,
     else if (e->wrapper == 0)
         r = nx_adler32_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.a5.as<uint32_t>(), ns, g.s);
     if (r != NX_OK) return r;
-    r = nx_deflate_encode_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.dout.as<uint8_t>(),
-                                g.a1.as<uint64_t>(), g.a3.as<uint32_t>(), g.a4.as<int32_t>(), ns, e->level, g.s);
+    if (tail)
+        r = nx_deflate_encode_batch_ex(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.a6.as<uint32_t>(),
+                                       g.dout.as<uint8_t>(), g.a1.as<uint64_t>(), g.a3.as<uint32_t>(), g.a4.as<int32_t>(), ns,
+                                       e->level, g.s);
+    else
+        r = nx_deflate_encode_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.dout.as<uint8_t>(),
+                                    g.a1.as<uint64_t>(), g.a3.as<uint32_t>(), g.a4.as<int32_t>(), ns, e->level, g.s);
     if (r != NX_OK) return r;
     std::vector<uint32_t> olen(ns), sum(ns, 0u);
     std::vector<int32_t> st(ns);
@@ -1021,6 +1075,7 @@ extern "C" int64_t nx_zlib_encoder_encode(nx_zlib_encoder* e, const uint8_t* in,
         else if (e->wrapper == 0) e->adler = nx_adler32_combine(e->adler, sum[i], ilen[i]);
     }
     e->total_in += n;
+    e->dict_armed = false;
     return (int64_t)op;
 }
 
@@ -1210,6 +1265,21 @@ extern "C" nx_zlib_decoder* nx_zlib_decoder_new(int32_t wrapper, int32_t decompr
     d->decide = wrapper == 3;
     return d;
 }
+// JdkZlibDecoder(dictionary, maxAllocation) (:96-111): ZlibWrapper.ZLIB, decompressConcatenated false
+extern "C" nx_zlib_decoder* nx_zlib_decoder_new_dict(const uint8_t* dict, size_t dict_len, int32_t max_allocation) {
+    if (!dict) return nullptr;
+    nx_zlib_decoder* d = nx_zlib_decoder_new(0, 0, max_allocation);
+    if (!d) return nullptr;
+    const size_t tail = dict_len < kZlibDictMax ? dict_len : kZlibDictMax;
+    d->has_dict = true;
+    d->dictid = adler32_host(dict, dict_len);
+    d->dict_n = (uint32_t)tail;
+    if (tail && (!d->ddict.ensure(tail) || !d->g.h2d(d->ddict.p, dict + (dict_len - tail), tail) || !d->g.sync())) {
+        delete d;
+        return nullptr;
+    }
+    return d;
+}
 extern "C" void nx_zlib_decoder_free(nx_zlib_decoder* d) { nx_zlib_decoder_unref(d); }
 extern "C" int32_t nx_zlib_decoder_is_closed(const nx_zlib_decoder* d) { return d && d->finished ? 1 : 0; }
 
@@ -1272,8 +1342,29 @@ int wrapper_step(nx_zlib_decoder* d, Call& c) {
                 else if ((cmf >> 4) + 8u > 15u) code = NX_ERR_ZLIB_WINDOW;
                 if (code == NX_OK && (flg & 0x20u)) {  // FDICT: zlib reads the dictionary id, then asks for it (:276-280)
                     if (n - rd < 6) return kStop;
-                    c.err = "decompression failure, unable to set dictionary as non was specified";
-                    return fail(d, c, NX_ERR_ZLIB_NEED_DICT);
+                    if (!d->has_dict) {
+                        c.err = "decompression failure, unable to set dictionary as non was specified";
+                        return fail(d, c, NX_ERR_ZLIB_NEED_DICT);
+                    }
+                    // inflater.setDictionary (:281): zlib's inflateSetDictionary refuses a dictionary whose
+                    // Adler32 is not DICTID, and Inflater throws IllegalArgumentException (zlib sets no text;
+                    // the message is not pinned by a JVM run)
+                    if (be32(in + rd + 2) != d->dictid) {
+                        c.err = "java.lang.IllegalArgumentException";
+                        return fail(d, c, NX_ERR_ZLIB_DICT_MISMATCH);
+                    }
+                    // the dictionary's tail is the window's content before the first output byte; the running
+                    // Adler32 starts at 1 after it (inflate.c, DICT -> TYPE)
+                    if (d->dict_n && (hipMemcpyAsync(d->win[d->cur].as<uint8_t>() + kZlibHist - d->dict_n, d->ddict.p, d->dict_n,
+                                                     hipMemcpyDeviceToDevice, d->g.s) != hipSuccess ||
+                                      !d->g.sync())) {
+                        c.err = "GPU copy failed";
+                        return fail(d, c, NX_ERR_HIP);
+                    }
+                    d->hist = d->dict_n;
+                    rd += 6;
+                    d->zs = Z::Z_BODY;
+                    continue;
                 }
                 if (code != NX_OK) {
                     c.err = "decompression failure";

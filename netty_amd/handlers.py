@@ -309,11 +309,13 @@ class JdkZlibEncoder(_Encoder):
     and the wrapper's trailer, after which encode() passes its input through (:215-218).  Levels 1-9
     and -1 run one matcher (sizes near zlib level 1), level 0 writes stored blocks; the bytes differ
     from the JDK's and inflate to the same data.  ZLIB_OR_NONE and levels outside -1..9 are refused
-    as the reference's constructor refuses them (:124-132)."""
+    as the reference's constructor refuses them (:124-132).  dictionary: JdkZlibEncoder(level, dictionary)
+    (:149-177), ZLIB only: the header carries FDICT and the dictionary's Adler32, and the stream's first
+    slice may match into the dictionary's last 32 KiB."""
 
     _free = "nx_zlib_encoder_free"
 
-    def __init__(self, wrapper: ZlibWrapper = ZlibWrapper.ZLIB, compression_level: int = 6):
+    def __init__(self, wrapper: ZlibWrapper = ZlibWrapper.ZLIB, compression_level: int = 6, dictionary: bytes | None = None):
         wrapper = ZlibWrapper(wrapper)
         if not -1 <= compression_level <= 9:
             raise ValueError(f"compressionLevel: {compression_level} (expected: -1-9)")
@@ -321,7 +323,13 @@ class JdkZlibEncoder(_Encoder):
             raise ValueError(f"wrapper '{wrapper.name}' is not allowed for compression.")
         self.wrapper = wrapper
         self.compression_level = int(compression_level)
-        self._h = _new(_lib.load().nx_zlib_encoder_new(int(wrapper), self.compression_level), "JdkZlibEncoder")
+        if dictionary is None:
+            self._h = _new(_lib.load().nx_zlib_encoder_new(int(wrapper), self.compression_level), "JdkZlibEncoder")
+            return
+        if wrapper != ZlibWrapper.ZLIB:  # the dictionary constructors take no wrapper (:173)
+            raise ValueError(f"a preset dictionary needs ZlibWrapper.ZLIB, not '{wrapper.name}'")
+        dictionary = bytes(dictionary)
+        self._h = _new(_lib.load().nx_zlib_encoder_new_dict(self.compression_level, dictionary, len(dictionary)), "JdkZlibEncoder")
 
     @staticmethod
     def _ret(r, out) -> bytes:
@@ -347,16 +355,24 @@ class JdkZlibDecoder(_Decoder):
     received so far (the boundaries are this decoder's own); with max_allocation > 0 a read delivers
     one message of at most that many bytes or fails with "Decompression buffer has reached maximum
     size".  A data error raises DecompressionException("decompression failure") with the inflater's
-    code as .status; the preset-dictionary constructors are not offered."""
+    code as .status.  dictionary: JdkZlibDecoder(dictionary, maxAllocation) (:96-111), ZLIB and not
+    concatenated; a stream whose DICTID is not the dictionary's raises DecoderException."""
 
     _free = "nx_zlib_decoder_free"
     _decode_fn = "nx_zlib_decoder_decode"
 
-    def __init__(self, wrapper: ZlibWrapper = ZlibWrapper.ZLIB, decompress_concatenated: bool = False, max_allocation: int = 0):
+    def __init__(self, wrapper: ZlibWrapper = ZlibWrapper.ZLIB, decompress_concatenated: bool = False, max_allocation: int = 0,
+                 dictionary: bytes | None = None):
         super().__init__()
         if max_allocation < 0:  # ObjectUtil.checkPositiveOrZero (ZlibDecoder.java:49)
             raise ValueError(f"maxAllocation : {max_allocation} (expected: >= 0)")
         self.wrapper = ZlibWrapper(wrapper)
+        if dictionary is not None:
+            if self.wrapper != ZlibWrapper.ZLIB or decompress_concatenated:  # the dictionary constructors take neither (:97,110)
+                raise ValueError("a preset dictionary needs ZlibWrapper.ZLIB and decompress_concatenated = False")
+            dictionary = bytes(dictionary)
+            self._h = _new(_lib.load().nx_zlib_decoder_new_dict(dictionary, len(dictionary), int(max_allocation)), "JdkZlibDecoder")
+            return
         self._h = _new(_lib.load().nx_zlib_decoder_new(int(self.wrapper), int(bool(decompress_concatenated)), int(max_allocation)),
                        "JdkZlibDecoder")
 

@@ -3,7 +3,8 @@
 // (Snappy frames, FastLZ frames at both levels with and without checksums, LZF, LZ4 frames fast and
 // high) over text, random and empty messages fed to the decoders in random slices (cumulation), the
 // same jobs through one batcher (outputs compared with the synchronous ones), corrupted streams
-// (any status, never a memory error), and handles freed while their jobs are in flight.
+// (any status, never a memory error), handles freed while their jobs are in flight, and the
+// preset-dictionary zlib handles (a round trip, the DICTID mismatch, a free with jobs in flight).
 // Prints one JSON line; exit 0 when every round trip matched.
 #include <stdint.h>
 #include <stdio.h>
@@ -370,11 +371,114 @@ int main(int argc, char** argv) {
         if (nx_snappy_encoder_reserve_ex(40000, 1000ull * 131072ull, nullptr, nullptr, nullptr) == NX_OK) fail("r6: cap below a live workspace");
         r6_checks += 3;
     }
+    // Preset-dictionary handles: a round trip (synchronous encode, synchronous and batched decode, fed in
+    // random slices), the DICTID mismatch, and handles freed while their jobs are in flight.
+    size_t dict_checks = 0;
+    {
+        nx_batcher* b = nx_batcher_new();
+        const size_t dict_lens[] = {0, 1, 100, 32768, 40000};
+        for (size_t dl : dict_lens) {
+            if (!b) break;
+            const Bytes dict = make_msg(&tg, 0, dl, 11), other = make_msg(&tg, 1, dl + 1, 12);
+            const uint8_t nothing = 0;
+            const uint8_t* dp = dl ? dict.data() : &nothing;
+            nx_zlib_encoder* e = nx_zlib_encoder_new_dict(6, dp, dl);
+            nx_zlib_decoder* d = nx_zlib_decoder_new_dict(dp, dl, 0);
+            if (!e || !d) {
+                fail("dict: handle creation");
+                break;
+            }
+            Bytes data, wire;
+            for (size_t n : {(size_t)1, (size_t)70000, (size_t)300}) {
+                Bytes m = make_msg(&tg, 0, n, 13 + n);
+                if (dl >= n) memcpy(m.data(), dict.data() + (dl - n), n);  // drawn from the dictionary's end
+                Bytes out(nx_zlib_max_encoded_length(n));
+                const int64_t w = nx_zlib_encoder_encode(e, m.data(), n, out.data(), out.size());
+                if (w < 0) fail("dict: encode");
+                else wire.insert(wire.end(), out.begin(), out.begin() + w);
+                data.insert(data.end(), m.begin(), m.end());
+            }
+            uint8_t fin[32];
+            const int64_t w = nx_zlib_encoder_close(e, fin, sizeof fin);
+            if (w < 0) fail("dict: close");
+            else wire.insert(wire.end(), fin, fin + w);
+            if (wire.size() < 2 || ((wire[1] & 0x20) != 0) != (dl != 0)) fail("dict: FDICT");
+            Bytes got, cum;
+            for (size_t at = 0; at < wire.size();) {  // the synchronous decoder, in slices
+                const size_t want = 1 + rnd() % 5000, n = want < wire.size() - at ? want : wire.size() - at;
+                cum.insert(cum.end(), wire.begin() + at, wire.begin() + at + n);
+                at += n;
+                size_t consumed = 0, nm = 0;
+                const nx_msg* ms = nullptr;
+                const char* err = nullptr;
+                if (nx_zlib_decoder_decode(d, cum.data(), cum.size(), &consumed, &ms, &nm, &err) != NX_OK) fail("dict: decode");
+                for (size_t k = 0; k < nm; ++k) got.insert(got.end(), ms[k].data, ms[k].data + ms[k].len);
+                cum.erase(cum.begin(), cum.begin() + consumed);
+            }
+            if (got != data || !nx_zlib_decoder_is_closed(d)) fail("dict: round trip");
+            // the same stream as two decoder jobs; then a decoder with another dictionary
+            nx_zlib_decoder* dj = nx_zlib_decoder_new_dict(dp, dl, 0);
+            nx_zlib_decoder* dw = nx_zlib_decoder_new_dict(other.data(), other.size(), 0);
+            size_t consumed = 0;
+            const size_t cut = wire.size() / 2;
+            const int64_t t0 = nx_zlib_decoder_submit(dj, b, wire.data(), cut, &consumed);
+            const int64_t t1 = nx_zlib_decoder_submit(dj, b, wire.data() + cut, wire.size() - cut, &consumed);
+            const int64_t tw = nx_zlib_decoder_submit(dw, b, wire.data(), wire.size(), &consumed);
+            nx_batcher_flush(b);
+            Bytes gotb;
+            for (int64_t t : {t0, t1, tw}) {
+                if (t <= 0) {
+                    fail("dict: submit");
+                    continue;
+                }
+                nx_batcher_wait(b, t);
+                const nx_msg* ms = nullptr;
+                size_t nm = 0;
+                const char* err = nullptr;
+                const int32_t r = nx_batcher_result(b, t, &ms, &nm, &err);
+                if (t == tw) {
+                    if (dl && r != NX_ERR_ZLIB_DICT_MISMATCH) fail("dict: mismatch status");
+                } else {
+                    if (r != NX_OK) fail("dict: decoder job");
+                    for (size_t k = 0; k < nm; ++k) gotb.insert(gotb.end(), ms[k].data, ms[k].data + ms[k].len);
+                }
+                nx_batcher_release(b, t);
+            }
+            if (gotb != data) fail("dict: batched decode differs");
+            // freed with jobs in flight: the jobs hold their handles
+            nx_zlib_encoder* ef = nx_zlib_encoder_new_dict(1, dp, dl);
+            nx_zlib_decoder* df = nx_zlib_decoder_new_dict(dp, dl, 0);
+            const int64_t te = ef ? nx_zlib_encoder_submit(ef, b, data.data(), data.size(), 2) : 0;
+            const int64_t td = df ? nx_zlib_decoder_submit(df, b, wire.data(), wire.size(), &consumed) : 0;
+            nx_zlib_encoder_free(ef);
+            nx_zlib_decoder_free(df);
+            nx_batcher_flush(b);
+            for (int64_t t : {te, td}) {
+                if (t <= 0) {
+                    fail("dict: submit before free");
+                    continue;
+                }
+                nx_batcher_wait(b, t);
+                const nx_msg* ms = nullptr;
+                size_t nm = 0;
+                const char* err = nullptr;
+                if (nx_batcher_result(b, t, &ms, &nm, &err) != NX_OK) fail("dict: job of a freed handle");
+                nx_batcher_release(b, t);
+            }
+            nx_zlib_encoder_free(e);
+            nx_zlib_decoder_free(d);
+            nx_zlib_decoder_free(dj);
+            nx_zlib_decoder_free(dw);
+            ++dict_checks;
+        }
+        if (nx_zlib_encoder_new_dict(6, nullptr, 0) || nx_zlib_decoder_new_dict(nullptr, 0, 0)) fail("dict: NULL dictionary");
+        if (b) nx_batcher_free(b);
+    }
     const int32_t trim = nx_workspaces_trim();
     if (trim != NX_OK) fail("nx_workspaces_trim");
-    printf("{\"codecs\": %zu, \"rounds\": %d, \"round_trips\": %zu, \"batch_jobs\": %zu, \"corrupt_runs\": %zu, \"round6_checks\": %zu, "
+    printf("{\"codecs\": %zu, \"rounds\": %d, \"round_trips\": %zu, \"batch_jobs\": %zu, \"corrupt_runs\": %zu, \"round6_checks\": %zu, \"dict_checks\": %zu, "
            "\"failures\": %d, \"failure_list\": \"%s\", \"verified\": %s}\n",
-           codecs.size(), rounds, round_trips, batch_jobs, corrupt_runs, r6_checks, g_fail, g_list.c_str(), g_fail ? "false" : "true");
+           codecs.size(), rounds, round_trips, batch_jobs, corrupt_runs, r6_checks, dict_checks, g_fail, g_list.c_str(), g_fail ? "false" : "true");
     fflush(stdout);
     return g_fail ? 1 : 0;
 }
