@@ -75,6 +75,7 @@ int32_t nx_snappy_encode_batch(const uint8_t* in, const uint64_t* in_off, const 
 #define NX_WS_DEC_RECORDS 4
 #define NX_WS_LZ4HC_ENC 5
 #define NX_WS_DEFLATE_ENC 6
+#define NX_WS_ZSTD_ENC 7
 int32_t nx_snappy_encoder_reserve(uint32_t max_chunks, void* stream);
 /* The same with a bound (round 6): max_bytes caps the Snappy table workspace for good (0: no cap; 128
  * KiB per lane, whole blocks of 256 lanes above 16 384): batches of any size then run on those lanes
@@ -242,6 +243,21 @@ int32_t nx_deflate_encode_batch(const uint8_t* in, const uint64_t* in_off, const
 int32_t nx_deflate_encode_batch_ex(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint32_t* prefix_len,
                                    uint8_t* out, const uint64_t* out_off, uint32_t* out_len, int32_t* status, uint32_t n,
                                    int32_t level, void* stream);
+
+/*
+ * Zstandard frames (ZstdEncoder.java:146-168: one Zstd.compress call per block buffer, one complete
+ * frame per block).  Chunk i, of at most 65536 bytes, becomes one frame in its slot of
+ * nx_zstd_max_compressed_length(in_len[i]) bytes (ZSTD_compressBound): a single-segment header with the
+ * exact content size and one last block, Raw, RLE or Compressed, whichever is smallest.  An empty chunk
+ * writes nothing; a chunk over 65536 bytes gets NX_ERR_INVALID_ARG and out_len 0, alone.  level as
+ * libzstd, -131072..22 (0: the default), every level the one matcher; a level outside that range makes
+ * the call return NX_ERR_INVALID_ARG.  The bytes are this encoder's own: libzstd decodes them to the
+ * input, zstd-jni would have written others.  512 KiB of NX_WS_ZSTD_ENC workspace per chunk in flight.
+ */
+size_t nx_zstd_max_compressed_length(size_t n);
+int32_t nx_zstd_encode_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                             const uint64_t* out_off, uint32_t* out_len, int32_t* status, uint32_t n, int32_t level,
+                             void* stream);
 
 /* Replaces Inflater.inflate(...) as JdkZlibDecoder.decode calls it (JdkZlibDecoder.java:254-296) for n
  * independent raw deflate (RFC 1951) streams, each resumable at symbol granularity: a call takes
@@ -469,6 +485,27 @@ size_t nx_lz4_frame_max_encoded_length(size_t n, int32_t block_size);
 int64_t nx_lz4_frame_encoder_encode(nx_lz4_frame_encoder* e, const uint8_t* in, size_t n, uint8_t* out, size_t out_cap);
 int64_t nx_lz4_frame_encoder_flush(nx_lz4_frame_encoder* e, uint8_t* out, size_t out_cap);
 int64_t nx_lz4_frame_encoder_close(nx_lz4_frame_encoder* e, uint8_t* out, size_t out_cap);
+
+/*
+ * ZstdEncoder.  nx_zstd_encoder_new(level, block_size, max_encode_size) restates the constructor's three
+ * checks (ZstdEncoder.java:90-96: level in -131072..22, block_size > 0, max_encode_size > 0) and returns
+ * NULL on a violation.  _encode appends to the block buffer and compresses every full block_size bytes
+ * (:134-143), all full blocks of one call in one batch launch; _flush compresses what is pending
+ * (:171-178) and writes nothing when nothing is.  Both run allocateBuffer's size check first (:105-122):
+ * the sum of compressBound(curSize) over the blocks of pending + n bytes against max_encode_size; on
+ * failure they return NX_ERR_ZSTD_ENCODE_SIZE, change nothing, and nx_zstd_encoder_error has the
+ * EncoderException's text.  There is no finish: the reference has none, and _free drops buffered bytes as
+ * handlerRemoved does (:187-193).  A block over 65536 bytes goes out as consecutive frames of 64 KiB
+ * slices (the reference writes one frame per block); their sum stays inside compressBound(block).
+ * nx_zstd_max_encoded_length(pending, block_size): the out_cap that always suffices for that many bytes.
+ */
+typedef struct nx_zstd_encoder nx_zstd_encoder;
+nx_zstd_encoder* nx_zstd_encoder_new(int32_t level, int32_t block_size, int32_t max_encode_size);
+void nx_zstd_encoder_free(nx_zstd_encoder* e);
+const char* nx_zstd_encoder_error(nx_zstd_encoder* e);
+size_t nx_zstd_max_encoded_length(size_t pending, int32_t block_size);
+int64_t nx_zstd_encoder_encode(nx_zstd_encoder* e, const uint8_t* in, size_t n, uint8_t* out, size_t out_cap);
+int64_t nx_zstd_encoder_flush(nx_zstd_encoder* e, uint8_t* out, size_t out_cap);
 
 /* JdkZlibEncoder(wrapper, compressionLevel)  JdkZlibEncoder.java:123-137,214-276,308-340.  wrapper is
  * ZlibWrapper's ordinal (0 ZLIB, 1 GZIP, 2 NONE); NULL for 3 (ZLIB_OR_NONE, :128-132) and for a level

@@ -77,6 +77,11 @@
  * EMPTY_BUFFER, i.e. the message's blocks need fewer than blockSize bytes (:216-218). */
 #define NX_ERR_LZ4_ENCODE_FINISHED        (-59)
 
+/* ZstdEncoder.allocateBuffer (ZstdEncoder.java:105-122): EncoderException "requested encode buffer size
+ * (%d bytes) exceeds the maximum allowable size (%d bytes)" or "too much data to allocate a buffer for
+ * compression" (nx_zstd_encoder_error has the message). */
+#define NX_ERR_ZSTD_ENCODE_SIZE           (-80)
+
 /* Device frame scan (nx_snappy_frame_scan_batch), one code per SnappyFrameDecoder throw site: */
 /* :116-118  "Unexpected length of stream identifier: %d" */
 #define NX_ERR_SNAPPY_STREAM_ID_LENGTH        (-41)

@@ -49,6 +49,8 @@ _SIGS = {
     "nx_deflate_max_compressed_length": (sz, [sz]),
     "nx_deflate_encode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, i32, vp]),
     "nx_deflate_encode_batch_ex": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, u32, i32, vp]),
+    "nx_zstd_max_compressed_length": (sz, [sz]),
+    "nx_zstd_encode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, i32, vp]),
     "nx_inflate_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]),
     "nx_lzf_encode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, vp]),
     "nx_lzf_decode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, vp]),
@@ -124,6 +126,12 @@ _SIGS = {
     "nx_lz4_frame_encoder_encode": (i64, [vp, C.c_char_p, sz, vp, sz]),
     "nx_lz4_frame_encoder_flush": (i64, [vp, vp, sz]),
     "nx_lz4_frame_encoder_close": (i64, [vp, vp, sz]),
+    "nx_zstd_encoder_new": (vp, [i32, i32, i32]),
+    "nx_zstd_encoder_free": (None, [vp]),
+    "nx_zstd_encoder_error": (C.c_char_p, [vp]),
+    "nx_zstd_max_encoded_length": (sz, [sz, i32]),
+    "nx_zstd_encoder_encode": (i64, [vp, C.c_char_p, sz, vp, sz]),
+    "nx_zstd_encoder_flush": (i64, [vp, vp, sz]),
     "nx_zlib_encoder_new": (vp, [i32, i32]),
     "nx_zlib_encoder_new_dict": (vp, [i32, C.c_char_p, sz]),
     "nx_zlib_encoder_free": (None, [vp]),

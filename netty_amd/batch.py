@@ -215,6 +215,23 @@ def deflate_encode(inp, in_off, in_len, out, out_off, level: int = 6, prefix_len
     return out_len, status
 
 
+def zstd_max_compressed_length(n: int) -> int:
+    return _lib.load().nx_zstd_max_compressed_length(n)
+
+
+def zstd_encode(inp, in_off, in_len, out, out_off, level: int = 3):
+    """One complete Zstandard frame per chunk of at most 65536 bytes (nx_zstd_encode_batch): slots of
+    zstd_max_compressed_length bytes; level as libzstd (-131072..22, every one the one matcher).
+    Returns (out_len, status)."""
+    n = in_len.numel()
+    dev = inp.device
+    out_len = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    _chk(_lib.load().nx_zstd_encode_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_len),
+                                          _ptr(status), n, int(level), _stream()), "nx_zstd_encode_batch")
+    return out_len, status
+
+
 INFLATE_STATE_BYTES = 512
 INFLATE_NEED_INPUT, INFLATE_OUTPUT_FULL = 2, 3
 

@@ -335,6 +335,15 @@ struct nx_lz4_frame_encoder {
     std::vector<uint8_t> buf;  // the block buffer (Lz4FrameEncoder.java:221-226)
 };
 
+struct nx_zstd_encoder {
+    nx::h::Gpu g;
+    int32_t level = 3;
+    uint32_t block_size = 65536;
+    int32_t max_encode_size = 1 << 25;  // maxEncodeSize (ZstdEncoder.java:48)
+    std::string err;                    // the last failure's message
+    std::vector<uint8_t> buf;           // the block buffer (:49,136-143), grown on demand
+};
+
 struct nx_zlib_encoder {
     nx::h::Gpu g;
     int32_t wrapper = 0;        // ZlibWrapper ordinal: 0 ZLIB, 1 GZIP, 2 NONE

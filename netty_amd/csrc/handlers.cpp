@@ -904,6 +904,144 @@ extern "C" int64_t nx_lz4_frame_encoder_close(nx_lz4_frame_encoder* e, uint8_t* 
     return w + kLz4Header;
 }
 
+// ------------------------------------------------------------------ ZstdEncoder
+namespace {
+constexpr size_t kZstdSlice = 65536;  // a frame of the batch encoder holds at most this much
+
+// flushBufferedData (ZstdEncoder.java:146-168) for the consecutive blocks of `src` (the last may be
+// short): one launch for all of them.  A block over 64 KiB is cut into 64 KiB slices, each its own frame.
+int64_t zstd_flush_blocks(nx_zstd_encoder* e, const uint8_t* src, size_t n, uint8_t* out, size_t out_cap) {
+    if (n == 0) return 0;
+    const size_t bs = e->block_size;
+    std::vector<uint64_t> ioff, ooff;
+    std::vector<uint32_t> ilen;
+    uint64_t oc = 0;
+    for (size_t b = 0; b < n; b += bs) {
+        const size_t blen = n - b < bs ? n - b : bs;
+        for (size_t q = 0; q < blen; q += kZstdSlice) {
+            const uint32_t len = (uint32_t)(blen - q < kZstdSlice ? blen - q : kZstdSlice);
+            ioff.push_back(b + q);
+            ilen.push_back(len);
+            ooff.push_back(oc);
+            oc += (nx_zstd_max_compressed_length(len) + 15) / 16 * 16;
+        }
+    }
+    const uint32_t nb = (uint32_t)ilen.size();
+    Gpu& g = e->g;
+    if (!g.din.ensure(n) || !g.dout.ensure(oc) || !g.a0.ensure(8ull * nb) || !g.a1.ensure(8ull * nb) || !g.a2.ensure(4ull * nb) ||
+        !g.a3.ensure(4ull * nb) || !g.a4.ensure(4ull * nb))
+        return NX_ERR_HIP;
+    bool ok = g.h2d(g.din.p, src, n) && g.h2d(g.a0.p, ioff.data(), 8ull * nb) && g.h2d(g.a1.p, ooff.data(), 8ull * nb) &&
+              g.h2d(g.a2.p, ilen.data(), 4ull * nb);
+    if (!ok) return NX_ERR_HIP;
+    const int32_t r = nx_zstd_encode_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.dout.as<uint8_t>(),
+                                           g.a1.as<uint64_t>(), g.a3.as<uint32_t>(), g.a4.as<int32_t>(), nb, e->level, g.s);
+    if (r != NX_OK) return r;
+    std::vector<uint32_t> olen(nb);
+    std::vector<int32_t> st(nb);
+    ok = g.d2h(olen.data(), g.a3.p, 4ull * nb) && g.d2h(st.data(), g.a4.p, 4ull * nb) && g.sync();
+    if (!ok) return NX_ERR_HIP;
+    size_t op = 0;
+    for (uint32_t i = 0; i < nb; ++i) {
+        if (st[i] != NX_OK) return st[i];
+        if (op + olen[i] > out_cap) return NX_ERR_INVALID_ARG;
+        op += olen[i];
+    }
+    // one copy of the slots up to the last frame's end, then the frames are packed on the host (a small
+    // block_size makes thousands of frames a call: a copy each would cost more than the bytes between them)
+    std::vector<uint8_t> slots((size_t)ooff[nb - 1] + olen[nb - 1]);
+    if (!g.d2h(slots.data(), g.dout.p, slots.size()) || !g.sync()) return NX_ERR_HIP;
+    op = 0;
+    for (uint32_t i = 0; i < nb; ++i) {
+        nx::copy_bytes(out + op, slots.data() + ooff[i], olen[i]);
+        op += olen[i];
+    }
+    return (int64_t)op;
+}
+
+// allocateBuffer's size check (:105-122): remaining as a Java int, the sum as a Java long.
+int32_t zstd_check_size(nx_zstd_encoder* e, uint64_t remaining) {
+    if (remaining > 0x7FFFFFFFull) {  // int remaining < 0 (:108-110)
+        e->err = "too much data to allocate a buffer for compression";
+        return NX_ERR_ZSTD_ENCODE_SIZE;
+    }
+    int64_t target = 0;
+    if (remaining >= e->block_size) {  // the full blocks all have one bound
+        const uint64_t full = remaining / e->block_size;
+        target += (int64_t)(full * nx_zstd_max_compressed_length(e->block_size));
+        remaining -= full * e->block_size;
+    }
+    if (remaining) target += (int64_t)nx_zstd_max_compressed_length(remaining);
+    if (target > e->max_encode_size || target < 0) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "requested encode buffer size (%lld bytes) exceeds the maximum allowable size (%d bytes)",
+                 (long long)target, e->max_encode_size);
+        e->err = buf;
+        return NX_ERR_ZSTD_ENCODE_SIZE;
+    }
+    return NX_OK;
+}
+}  // namespace
+
+extern "C" nx_zstd_encoder* nx_zstd_encoder_new(int32_t level, int32_t block_size, int32_t max_encode_size) {
+    // checkInRange(compressionLevel, MIN, MAX), checkPositive(blockSize), checkPositive(maxEncodeSize) :92-95
+    if (level < -131072 || level > 22 || block_size <= 0 || max_encode_size <= 0) return nullptr;
+    auto* e = new nx_zstd_encoder();
+    if (!e->g.hold(nx::WsKind::ZstdEnc)) {
+        delete e;
+        return nullptr;
+    }
+    e->level = level;
+    e->block_size = (uint32_t)block_size;
+    e->max_encode_size = max_encode_size;
+    return e;
+}
+extern "C" void nx_zstd_encoder_free(nx_zstd_encoder* e) { delete e; }
+extern "C" const char* nx_zstd_encoder_error(nx_zstd_encoder* e) { return e && !e->err.empty() ? e->err.c_str() : nullptr; }
+extern "C" size_t nx_zstd_max_encoded_length(size_t pending, int32_t block_size) {
+    const size_t bs = block_size > 0 ? (size_t)block_size : 65536;
+    return pending / bs * nx_zstd_max_compressed_length(bs) + nx_zstd_max_compressed_length(pending % bs);
+}
+
+extern "C" int64_t nx_zstd_encoder_encode(nx_zstd_encoder* e, const uint8_t* in, size_t n, uint8_t* out, size_t out_cap) {
+    const nx::NoGrowScope no_grow;
+    if (!e || (!in && n)) return NX_ERR_INVALID_ARG;
+    {   // MessageToByteEncoder.write: allocateBuffer before encode (:105-122)
+        const int32_t r = zstd_check_size(e, (uint64_t)n + e->buf.size());
+        if (r != NX_OK) return r;
+    }
+    // :136-143 — fill the block buffer; every full buffer is flushed
+    const size_t have = e->buf.size();
+    const size_t full = (have + n) / e->block_size * e->block_size;
+    if (full == 0) {
+        e->buf.insert(e->buf.end(), in, in + n);
+        return 0;
+    }
+    std::vector<uint8_t> joined;
+    const uint8_t* src = in;
+    if (have) {
+        joined.reserve(full);
+        joined.insert(joined.end(), e->buf.begin(), e->buf.end());
+        joined.insert(joined.end(), in, in + (full - have));
+        src = joined.data();
+    }
+    const int64_t w = zstd_flush_blocks(e, src, full, out, out_cap);
+    if (w < 0) return w;
+    e->buf.assign(in + (full - have), in + n);
+    return w;
+}
+
+extern "C" int64_t nx_zstd_encoder_flush(nx_zstd_encoder* e, uint8_t* out, size_t out_cap) {
+    const nx::NoGrowScope no_grow;
+    if (!e) return NX_ERR_INVALID_ARG;
+    if (e->buf.empty()) return 0;  // flush() :171-178: nothing readable, nothing allocated
+    const int32_t r = zstd_check_size(e, e->buf.size());
+    if (r != NX_OK) return r;
+    const int64_t w = zstd_flush_blocks(e, e->buf.data(), e->buf.size(), out, out_cap);
+    if (w >= 0) e->buf.clear();
+    return w;
+}
+
 extern "C" nx_lz4_frame_decoder* nx_lz4_frame_decoder_new(int32_t validate_checksums) {
     auto* d = new nx_lz4_frame_decoder();
     if (!d->g.hold(nx::WsKind::DecRecords)) {

@@ -20,7 +20,7 @@
 
 namespace nx {
 
-enum class WsKind : int { SnappyEnc = 0, Lz4Enc, FastLzEnc, LzfEnc, DecRecords, Lz4HcEnc, DeflateEnc, Count };
+enum class WsKind : int { SnappyEnc = 0, Lz4Enc, FastLzEnc, LzfEnc, DecRecords, Lz4HcEnc, DeflateEnc, ZstdEnc, Count };
 
 // Table geometry per encoder kind (entry bytes, log2 entries per table, waves per CU of its launch);
 // each codec static_asserts its own constants against this.
@@ -34,6 +34,8 @@ struct WsSpec {
 // 2 waves per CU, always one block per wave (kHcMaxSlots: at most cus * 2 tables, 128 MiB on 256 CUs).
 // DeflateEnc: 128 KiB per chunk (4096 hash entries, then 96 KiB of tokens; deflate.hip), one chunk per
 // slot and launch pair, 16 waves per CU of lanes in the dense form.
+// ZstdEnc: 512 KiB per chunk (32 768 hash entries, then the chunk's literals and sequences; zstd.hip), one
+// chunk per slot and launch pair as DeflateEnc, a workspace of its own.
 #ifndef NX_LZ4_WPCU  // build options for A/B runs of the alt encoders' occupancy (scripts/build_lib_variant.sh; LZ4 at 20: level)
 #define NX_LZ4_WPCU 16
 #endif
@@ -43,7 +45,7 @@ struct WsSpec {
 #ifndef NX_LZF_WPCU  // LZF: 16 waves per CU measured level with 8 (profiles/r06/s4), so the smaller workspace stays
 #define NX_LZF_WPCU 8
 #endif
-constexpr WsSpec kWsSpec[] = {{8, 14, 20}, {8, 13, NX_LZ4_WPCU}, {8, 13, NX_FLZ_WPCU}, {8, 14, NX_LZF_WPCU}, {0, 0, 0}, {8, 15, 2}, {8, 14, 16}};
+constexpr WsSpec kWsSpec[] = {{8, 14, 20}, {8, 13, NX_LZ4_WPCU}, {8, 13, NX_FLZ_WPCU}, {8, 14, NX_LZF_WPCU}, {0, 0, 0}, {8, 15, 2}, {8, 14, 16}, {8, 16, 16}};
 static_assert(sizeof(kWsSpec) / sizeof(kWsSpec[0]) == (size_t)WsKind::Count, "one spec per kind");
 constexpr size_t kDecSlotBytes = 16384u * 4u + 8u;  // records of one frame + its count and length
 #ifndef NX_DEC_MAX_FRAMES  // build option for A/B runs (scripts/build_lib_variant.sh)

@@ -294,6 +294,52 @@ class Lz4FrameEncoder(_Encoder):
         return self._ret(_lib.load().nx_lz4_frame_encoder_close(self._h, out, cap), out)
 
 
+class ZstdEncoder(_Encoder):
+    """ZstdEncoder.java:90-193 over the GPU Zstandard frame encoder.  encode() returns the frames of the
+    blocks it filled (a partial block stays buffered, :134-143), flush() the frame of the pending bytes
+    (:171-178; nothing when nothing is pending).  Each block of block_size bytes is one complete frame
+    (a block over 64 KiB: consecutive frames of 64 KiB slices), which any Zstandard decoder reads as one
+    stream; the bytes differ from zstd-jni's.  Every level runs the one matcher.  encode() and flush()
+    raise EncoderException when the pending bytes' compressBound sum exceeds max_encode_size
+    (allocateBuffer, :105-122), leaving the encoder unchanged.  There is no finish: close() drops
+    buffered bytes as handlerRemoved does (:187-193)."""
+
+    _free = "nx_zstd_encoder_free"
+    MIN_COMPRESSION_LEVEL, MAX_COMPRESSION_LEVEL = -131072, 22  # Zstd.minCompressionLevel() / maxCompressionLevel()
+    MAX_BLOCK_SIZE = 1 << 25  # ZstdConstants.java:40: 1 << (3 + 7) + 0x0F, 32 MiB by operator precedence
+
+    def __init__(self, compression_level: int = 3, block_size: int = 1 << 16, max_encode_size: int = MAX_BLOCK_SIZE):
+        if not self.MIN_COMPRESSION_LEVEL <= compression_level <= self.MAX_COMPRESSION_LEVEL:  # ObjectUtil.checkInRange (:92-93)
+            raise ValueError(f"compressionLevel: {compression_level} (expected: {self.MIN_COMPRESSION_LEVEL}-{self.MAX_COMPRESSION_LEVEL})")
+        if block_size <= 0:  # ObjectUtil.checkPositive (:94)
+            raise ValueError(f"blockSize : {block_size} (expected: > 0)")
+        if max_encode_size <= 0:  # (:95)
+            raise ValueError(f"maxEncodeSize : {max_encode_size} (expected: > 0)")
+        self.compression_level = int(compression_level)
+        self.block_size = int(block_size)
+        self.max_encode_size = int(max_encode_size)
+        self._h = _new(_lib.load().nx_zstd_encoder_new(self.compression_level, self.block_size, self.max_encode_size), "ZstdEncoder")
+
+    def _out(self, n: int):
+        cap = _lib.load().nx_zstd_max_encoded_length(n, self.block_size)
+        return (C.c_uint8 * cap)(), cap
+
+    def _ret(self, r, out) -> bytes:
+        if r == -80:  # NX_ERR_ZSTD_ENCODE_SIZE: allocateBuffer's EncoderException
+            raise EncoderException(_lib.load().nx_zstd_encoder_error(self._h).decode())
+        if r < 0:
+            raise CompressionException(_lib.status_string(r))
+        return bytes(out[:r])
+
+    def encode(self, data: bytes) -> bytes:
+        out, cap = self._out(len(data) + self.block_size)
+        return self._ret(_lib.load().nx_zstd_encoder_encode(self._h, data, len(data), out, cap), out)
+
+    def flush(self) -> bytes:
+        out, cap = self._out(self.block_size)
+        return self._ret(_lib.load().nx_zstd_encoder_flush(self._h, out, cap), out)
+
+
 class ZlibWrapper(enum.IntEnum):
     """ZlibWrapper.java:21-40 (the ordinals the C-ABI takes)"""
     ZLIB = 0
