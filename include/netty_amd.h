@@ -76,6 +76,7 @@ int32_t nx_snappy_encode_batch(const uint8_t* in, const uint64_t* in_off, const 
 #define NX_WS_LZ4HC_ENC 5
 #define NX_WS_DEFLATE_ENC 6
 #define NX_WS_ZSTD_ENC 7
+#define NX_WS_ZSTD_DEC 8
 int32_t nx_snappy_encoder_reserve(uint32_t max_chunks, void* stream);
 /* The same with a bound (round 6): max_bytes caps the Snappy table workspace for good (0: no cap; 128
  * KiB per lane, whole blocks of 256 lanes above 16 384): batches of any size then run on those lanes
@@ -258,6 +259,54 @@ size_t nx_zstd_max_compressed_length(size_t n);
 int32_t nx_zstd_encode_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
                              const uint64_t* out_off, uint32_t* out_len, int32_t* status, uint32_t n, int32_t level,
                              void* stream);
+
+/*
+ * Replaces Zstd.decompress as ZstdDecoder.java calls it through zstd-jni (ZSTD_decompress on one frame),
+ * for n independent frames.  Item i is exactly one complete frame that starts at in[in_off[i]]; bytes
+ * after it inside in_len[i] are allowed and untouched, so a caller can hand in a cumulation.  The frame's
+ * regenerated bytes go to out[out_off[i] .. + out_cap[i]) and nothing is ever written outside that range.
+ *   consumed[i] = the frame's compressed size (0 on an error);
+ *   out_len[i]  = the regenerated size; on an error, what was written before it;
+ *   status[i]   = NX_OK or one code:
+ *     NX_ERR_ZSTD_MAGIC                 skippable or unknown magic
+ *     NX_ERR_ZSTD_TRUNCATED             the input ends inside the frame
+ *     NX_ERR_ZSTD_WINDOW                Window_Size or content size above 128 MiB (positions stay in 32 bits)
+ *     NX_ERR_ZSTD_DICTIONARY            Dictionary_ID != 0
+ *     NX_ERR_ZSTD_CHECKSUM_UNSUPPORTED  Content_Checksum flag set (Netty's ZstdEncoder never sets it; XXH64
+ *                                       is not verified here, so such a frame is refused, not trusted)
+ *     NX_ERR_ZSTD_OUTPUT_FULL           the regenerated bytes do not fit out_cap[i]
+ *     NX_ERR_ZSTD_CORRUPT               everything libzstd calls corruption_detected, a content size that
+ *                                       differs from the regenerated total included
+ * All block types, all four literals types, 1 and 4 Huffman streams, direct and FSE-coded weights, all four
+ * sequence modes, repeat offsets, multi-block frames.  One wave per frame; 128 KiB of NX_WS_ZSTD_DEC
+ * workspace per frame in flight (at most 8 per CU), larger batches run on those slots in turn.
+ * nx_zstd_decoder_reserve(max_frames) sizes that workspace at start-up and caps it at max_frames slots
+ * until nx_workspaces_trim.
+ */
+int32_t nx_zstd_decode_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                             const uint64_t* out_off, const uint32_t* out_cap, uint32_t* consumed, uint32_t* out_len,
+                             int32_t* status, uint32_t n, void* stream);
+int32_t nx_zstd_decoder_reserve(uint32_t max_frames, void* stream);
+/*
+ * The frame walker (host only; what ZSTD_findFrameCompressedSize and ZSTD_getFrameContentSize tell
+ * ZstdDecoder's caller): walks the frame header and the block headers of the frame at in[0..n), no
+ * entropy work.  NX_OK: *frame_bytes = the frame's compressed size, *content_size = its Frame_Content_Size
+ * or UINT64_MAX when absent, *flags = NX_ZSTD_FRAME_SINGLE_SEGMENT | NX_ZSTD_FRAME_CHECKSUM | the
+ * Window_Descriptor byte << 8 (NX_ZSTD_FRAME_WINDOW_DESCRIPTOR; 0 when single-segment).
+ * NX_ERR_ZSTD_TRUNCATED: n ends inside the frame, more input is needed.  Otherwise the header's error
+ * (MAGIC, CORRUPT for the reserved bit, block type 3 or a block above min(window, 128 KiB), DICTIONARY,
+ * WINDOW).  A frame with a checksum is walked (its 4 bytes counted); the decoders refuse it.
+ */
+#define NX_ZSTD_FRAME_SINGLE_SEGMENT 1u
+#define NX_ZSTD_FRAME_CHECKSUM 2u
+#define NX_ZSTD_FRAME_WINDOW_DESCRIPTOR(flags) (((flags) >> 8) & 0xffu)
+int32_t nx_zstd_frame_info(const uint8_t* in, size_t n, uint64_t* frame_bytes, uint64_t* content_size, uint32_t* flags);
+/*
+ * One frame decoded on the host, single-threaded, by the same format functions the kernel runs
+ * (csrc/zstd_decode_core.hpp) and the same contract and codes as an item of nx_zstd_decode_batch.  NOT a
+ * product path: it is the CPU check of the format logic and the GPU tests' second opinion.
+ */
+int32_t nx_zstd_decode_host(const uint8_t* in, size_t n, uint8_t* out, size_t out_cap, size_t* out_len, size_t* consumed);
 
 /* Replaces Inflater.inflate(...) as JdkZlibDecoder.decode calls it (JdkZlibDecoder.java:254-296) for n
  * independent raw deflate (RFC 1951) streams, each resumable at symbol granularity: a call takes

@@ -51,6 +51,10 @@ _SIGS = {
     "nx_deflate_encode_batch_ex": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, u32, i32, vp]),
     "nx_zstd_max_compressed_length": (sz, [sz]),
     "nx_zstd_encode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, i32, vp]),
+    "nx_zstd_decode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]),
+    "nx_zstd_decoder_reserve": (i32, [u32, vp]),
+    "nx_zstd_frame_info": (i32, [C.c_char_p, sz, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]),
+    "nx_zstd_decode_host": (i32, [C.c_char_p, sz, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
     "nx_inflate_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]),
     "nx_lzf_encode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, vp]),
     "nx_lzf_decode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, vp]),

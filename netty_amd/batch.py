@@ -25,7 +25,7 @@ def _chk(rc, what):
 
 
 # Shared device workspaces (include/netty_amd.h NX_WS_*; csrc/workspace.hpp)
-WS_SNAPPY_ENC, WS_LZ4_ENC, WS_FASTLZ_ENC, WS_LZF_ENC, WS_DEC_RECORDS, WS_LZ4HC_ENC, WS_DEFLATE_ENC = range(7)
+WS_SNAPPY_ENC, WS_LZ4_ENC, WS_FASTLZ_ENC, WS_LZF_ENC, WS_DEC_RECORDS, WS_LZ4HC_ENC, WS_DEFLATE_ENC, WS_ZSTD_ENC, WS_ZSTD_DEC = range(9)
 
 
 def workspace_info(kind: int) -> tuple[int, int]:
@@ -230,6 +230,44 @@ def zstd_encode(inp, in_off, in_len, out, out_off, level: int = 3):
     _chk(_lib.load().nx_zstd_encode_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_len),
                                           _ptr(status), n, int(level), _stream()), "nx_zstd_encode_batch")
     return out_len, status
+
+
+ZSTD_FRAME_SINGLE_SEGMENT, ZSTD_FRAME_CHECKSUM = 1, 2
+ZSTD_CONTENT_SIZE_UNKNOWN = 2 ** 64 - 1
+
+
+def zstd_decode(inp, in_off, in_len, out, out_off, out_cap):
+    """One complete Zstandard frame per item (nx_zstd_decode_batch): item i starts at inp[in_off[i]], bytes
+    after its frame inside in_len[i] are left alone; it regenerates into out[out_off[i] : + out_cap[i]].
+    Returns (consumed, out_len, status): the frame's compressed size, the regenerated size (on an error,
+    what was written before it) and 0 or one NX_ERR_ZSTD_* code per item."""
+    n = in_len.numel()
+    dev = inp.device
+    consumed = torch.empty(n, dtype=torch.int32, device=dev)
+    out_len = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    _chk(_lib.load().nx_zstd_decode_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_cap),
+                                          _ptr(consumed), _ptr(out_len), _ptr(status), n, _stream()), "nx_zstd_decode_batch")
+    return consumed, out_len, status
+
+
+def zstd_decoder_reserve(max_frames: int):
+    """nx_zstd_decoder_reserve: size the decoder's literals workspace for max_frames frames in flight now and
+    cap it there until workspaces_trim()."""
+    _chk(_lib.load().nx_zstd_decoder_reserve(int(max_frames), _stream()), "nx_zstd_decoder_reserve")
+
+
+def zstd_frame_info(data: bytes):
+    """nx_zstd_frame_info on host bytes: (status, frame_bytes, content_size, flags) of the first frame of
+    `data`; content_size is None when the frame does not carry it; status NX_ERR_ZSTD_TRUNCATED (-85) when
+    `data` ends inside the frame.  flags: ZSTD_FRAME_SINGLE_SEGMENT | ZSTD_FRAME_CHECKSUM | Window_Descriptor << 8."""
+    import ctypes as C
+    fb, cs, fl = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+    data = bytes(data)
+    st = _lib.load().nx_zstd_frame_info(data, len(data), C.byref(fb), C.byref(cs), C.byref(fl))
+    if st != 0:
+        return st, 0, None, 0
+    return 0, fb.value, None if cs.value == ZSTD_CONTENT_SIZE_UNKNOWN else cs.value, fl.value
 
 
 INFLATE_STATE_BYTES = 512

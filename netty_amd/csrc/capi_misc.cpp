@@ -16,6 +16,13 @@ extern "C" const char* nx_status_string(int32_t s) {
         case NX_ERR_LZ4_END_CHECKSUM: return "stream corrupted: checksum error";
         case NX_ERR_LZ4_ENCODE_SIZE: return "requested encode buffer size exceeds the maximum allowable size";
         case NX_ERR_ZSTD_ENCODE_SIZE: return "requested encode buffer size exceeds the maximum allowable size";
+        case NX_ERR_ZSTD_WINDOW: return "Frame requires too much memory for decoding";
+        case NX_ERR_ZSTD_DICTIONARY: return "Dictionary mismatch";
+        case NX_ERR_ZSTD_CHECKSUM_UNSUPPORTED: return "frames with a content checksum are not supported";
+        case NX_ERR_ZSTD_MAGIC: return "Unknown frame descriptor";
+        case NX_ERR_ZSTD_TRUNCATED: return "Src size is incorrect";
+        case NX_ERR_ZSTD_CORRUPT: return "Data corruption detected";
+        case NX_ERR_ZSTD_OUTPUT_FULL: return "Destination buffer is too small";
         case NX_ERR_LZ4_ENCODE_FINISHED: return "encode finished and not enough space to write remaining data";
         case NX_ERR_SNAPPY_PREAMBLE_TOO_LONG: return "Preamble is greater than 4 bytes";
         case NX_ERR_SNAPPY_OFFSET_ZERO: return "Offset is less than minimum permissible value";

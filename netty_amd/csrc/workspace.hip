@@ -53,8 +53,8 @@ hipError_t ws_grow(WsKind k, SharedWs& W, size_t slots, hipStream_t st) {
     hipError_t e = ws_drop(W);
     if (e != hipSuccess) return e;
     void* p = nullptr;
-    if (k == WsKind::DecRecords) {
-        e = hipMalloc(&p, slots * kDecSlotBytes);  // records are written before they are read: no zeroing
+    if (ws_plain_slot_bytes(k)) {
+        e = hipMalloc(&p, slots * ws_plain_slot_bytes(k));  // records and literals are written before they are read: no zeroing
     } else {
         const WsSpec& s = kWsSpec[(int)k];
         if (s.entry_bytes == 8) {
@@ -85,6 +85,7 @@ size_t hc_slots(uint32_t n, int cus) { return std::min<size_t>(n, (size_t)cus * 
 size_t ws_want(WsKind k, uint32_t n, int cus) {
     if (k == WsKind::DecRecords) return std::min<uint32_t>(n, kDecMaxFrames);
     if (k == WsKind::Lz4HcEnc) return hc_slots(n, cus);
+    if (k == WsKind::ZstdDec) return std::min<size_t>(n, (size_t)cus * kZstdDecWavesPerCu);
     return lane_grid(n, cus, kWsSpec[(int)k].waves_per_cu).slots;
 }
 
@@ -271,7 +272,8 @@ extern "C" int32_t nx_workspace_info(int32_t kind, uint64_t* bytes, int32_t* own
     nx::SharedWs& W = nx::shared_ws((nx::WsKind)kind, dev);
     std::lock_guard<std::mutex> lk(W.mu);
     const nx::WsSpec& s = nx::kWsSpec[kind];
-    *bytes = kind == (int32_t)nx::WsKind::DecRecords ? W.slots * nx::kDecSlotBytes : W.slots * ((size_t)s.entry_bytes << s.lg);
+    const size_t plain = nx::ws_plain_slot_bytes((nx::WsKind)kind);
+    *bytes = plain ? W.slots * plain : W.slots * ((size_t)s.entry_bytes << s.lg);
     *owners = W.owners;
     return NX_OK;
 }

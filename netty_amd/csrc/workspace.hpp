@@ -20,7 +20,7 @@
 
 namespace nx {
 
-enum class WsKind : int { SnappyEnc = 0, Lz4Enc, FastLzEnc, LzfEnc, DecRecords, Lz4HcEnc, DeflateEnc, ZstdEnc, Count };
+enum class WsKind : int { SnappyEnc = 0, Lz4Enc, FastLzEnc, LzfEnc, DecRecords, Lz4HcEnc, DeflateEnc, ZstdEnc, ZstdDec, Count };
 
 // Table geometry per encoder kind (entry bytes, log2 entries per table, waves per CU of its launch);
 // each codec static_asserts its own constants against this.
@@ -36,6 +36,8 @@ struct WsSpec {
 // slot and launch pair, 16 waves per CU of lanes in the dense form.
 // ZstdEnc: 512 KiB per chunk (32 768 hash entries, then the chunk's literals and sequences; zstd.hip), one
 // chunk per slot and launch pair as DeflateEnc, a workspace of its own.
+// ZstdDec: no tables: 128 KiB per frame in flight (the literals of the block being decoded; zstd_decode.hip),
+// leased by part as DecRecords is, one slot per wave of the launch on at most kZstdDecWavesPerCu waves per CU.
 #ifndef NX_LZ4_WPCU  // build options for A/B runs of the alt encoders' occupancy (scripts/build_lib_variant.sh; LZ4 at 20: level)
 #define NX_LZ4_WPCU 16
 #endif
@@ -45,13 +47,17 @@ struct WsSpec {
 #ifndef NX_LZF_WPCU  // LZF: 16 waves per CU measured level with 8 (profiles/r06/s4), so the smaller workspace stays
 #define NX_LZF_WPCU 8
 #endif
-constexpr WsSpec kWsSpec[] = {{8, 14, 20}, {8, 13, NX_LZ4_WPCU}, {8, 13, NX_FLZ_WPCU}, {8, 14, NX_LZF_WPCU}, {0, 0, 0}, {8, 15, 2}, {8, 14, 16}, {8, 16, 16}};
+constexpr WsSpec kWsSpec[] = {{8, 14, 20}, {8, 13, NX_LZ4_WPCU}, {8, 13, NX_FLZ_WPCU}, {8, 14, NX_LZF_WPCU}, {0, 0, 0}, {8, 15, 2}, {8, 14, 16}, {8, 16, 16}, {0, 0, 0}};
 static_assert(sizeof(kWsSpec) / sizeof(kWsSpec[0]) == (size_t)WsKind::Count, "one spec per kind");
 constexpr size_t kDecSlotBytes = 16384u * 4u + 8u;  // records of one frame + its count and length
 #ifndef NX_DEC_MAX_FRAMES  // build option for A/B runs (scripts/build_lib_variant.sh)
 #define NX_DEC_MAX_FRAMES 262144
 #endif
 constexpr uint32_t kDecMaxFrames = NX_DEC_MAX_FRAMES;  // frames per parse/expand launch pair
+constexpr size_t kZstdDecSlotBytes = 128u << 10;  // Block_Maximum_Size: the most literals one block regenerates
+constexpr unsigned kZstdDecWavesPerCu = 8;        // 2 048 frames in flight, 256 MiB, on 256 CUs
+// bytes per slot of a kind without tables (0 for the table kinds)
+constexpr size_t ws_plain_slot_bytes(WsKind k) { return k == WsKind::DecRecords ? kDecSlotBytes : k == WsKind::ZstdDec ? kZstdDecSlotBytes : 0; }
 
 struct WsUse {  // an in-flight part lease: slots [a, b), done when ev completes
     size_t a, b;
