@@ -272,8 +272,8 @@ int32_t nx_zstd_encode_batch(const uint8_t* in, const uint64_t* in_off, const ui
  *     NX_ERR_ZSTD_TRUNCATED             the input ends inside the frame
  *     NX_ERR_ZSTD_WINDOW                Window_Size or content size above 128 MiB (positions stay in 32 bits)
  *     NX_ERR_ZSTD_DICTIONARY            Dictionary_ID != 0
- *     NX_ERR_ZSTD_CHECKSUM_UNSUPPORTED  Content_Checksum flag set (Netty's ZstdEncoder never sets it; XXH64
- *                                       is not verified here, so such a frame is refused, not trusted)
+ *     NX_ERR_ZSTD_CHECKSUM_UNSUPPORTED  Content_Checksum flag set: refused by the entry points without
+ *                                       VERIFY_CHECKSUM (the frame is not trusted unverified)
  *     NX_ERR_ZSTD_OUTPUT_FULL           the regenerated bytes do not fit out_cap[i]
  *     NX_ERR_ZSTD_CORRUPT               everything libzstd calls corruption_detected, a content size that
  *                                       differs from the regenerated total included
@@ -286,6 +286,17 @@ int32_t nx_zstd_encode_batch(const uint8_t* in, const uint64_t* in_off, const ui
 int32_t nx_zstd_decode_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
                              const uint64_t* out_off, const uint32_t* out_cap, uint32_t* consumed, uint32_t* out_len,
                              int32_t* status, uint32_t n, void* stream);
+/* nx_zstd_decode_batch with flags; flags == 0 is nx_zstd_decode_batch itself, any bit other than those
+ * below makes the call return NX_ERR_INVALID_ARG.
+ *   NX_ZSTD_DECODE_VERIFY_CHECKSUM: a frame with Content_Checksum is decoded, and after its last block the
+ *   wave hashes the regenerated bytes (XXH64, seed 0) and compares the low 32 bits with the four bytes
+ *   that follow, little-endian (what ZstdInputStream does for ZstdDecoder).  consumed[i] includes the four
+ *   bytes; fewer than four left is NX_ERR_ZSTD_TRUNCATED; a mismatch is NX_ERR_ZSTD_CHECKSUM with out_len[i]
+ *   what was regenerated.  A frame without the flag is decoded as before.  Same launch, no second kernel. */
+#define NX_ZSTD_DECODE_VERIFY_CHECKSUM 1u
+int32_t nx_zstd_decode_batch_ex(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                                const uint64_t* out_off, const uint32_t* out_cap, uint32_t* consumed, uint32_t* out_len,
+                                int32_t* status, uint32_t n, uint32_t flags, void* stream);
 int32_t nx_zstd_decoder_reserve(uint32_t max_frames, void* stream);
 /*
  * The frame walker (host only; what ZSTD_findFrameCompressedSize and ZSTD_getFrameContentSize tell
@@ -295,18 +306,35 @@ int32_t nx_zstd_decoder_reserve(uint32_t max_frames, void* stream);
  * Window_Descriptor byte << 8 (NX_ZSTD_FRAME_WINDOW_DESCRIPTOR; 0 when single-segment).
  * NX_ERR_ZSTD_TRUNCATED: n ends inside the frame, more input is needed.  Otherwise the header's error
  * (MAGIC, CORRUPT for the reserved bit, block type 3 or a block above min(window, 128 KiB), DICTIONARY,
- * WINDOW).  A frame with a checksum is walked (its 4 bytes counted); the decoders refuse it.
+ * WINDOW).  A frame with a checksum is walked (its 4 bytes counted); the decoders verify it when asked
+ * to (NX_ZSTD_DECODE_VERIFY_CHECKSUM) and refuse the frame otherwise.
  */
 #define NX_ZSTD_FRAME_SINGLE_SEGMENT 1u
 #define NX_ZSTD_FRAME_CHECKSUM 2u
 #define NX_ZSTD_FRAME_WINDOW_DESCRIPTOR(flags) (((flags) >> 8) & 0xffu)
 int32_t nx_zstd_frame_info(const uint8_t* in, size_t n, uint64_t* frame_bytes, uint64_t* content_size, uint32_t* flags);
 /*
+ * The walker a decoder handle runs on its cumulation (host only): the next frame of in[0..n), of either
+ * kind.  *kind = NX_ZSTD_KIND_SKIPPABLE for magic 0x184D2A50..5F: *frame_bytes = 8 + the 4-byte length,
+ * *out_bound = 0, *flags = 0; NX_ERR_ZSTD_TRUNCATED while fewer than 8, or fewer than 8 + length, bytes are
+ * there.  *kind = NX_ZSTD_KIND_FRAME for a Zstandard frame: *frame_bytes and *flags as nx_zstd_frame_info,
+ * whose errors are this call's; *out_bound = a size the frame's output always fits: its Frame_Content_Size
+ * when the header carries it, else the sum over its blocks of Block_Size for Raw and RLE blocks and of
+ * Block_Maximum_Size (min(Window_Size, 128 KiB)) for Compressed ones.  No entropy work.
+ */
+#define NX_ZSTD_KIND_FRAME 0u
+#define NX_ZSTD_KIND_SKIPPABLE 1u
+int32_t nx_zstd_next_frame(const uint8_t* in, size_t n, uint32_t* kind, uint64_t* frame_bytes, uint64_t* out_bound,
+                           uint32_t* flags);
+/*
  * One frame decoded on the host, single-threaded, by the same format functions the kernel runs
  * (csrc/zstd_decode_core.hpp) and the same contract and codes as an item of nx_zstd_decode_batch.  NOT a
  * product path: it is the CPU check of the format logic and the GPU tests' second opinion.
+ * nx_zstd_decode_host_ex: the same for an item of nx_zstd_decode_batch_ex with `flags`.
  */
 int32_t nx_zstd_decode_host(const uint8_t* in, size_t n, uint8_t* out, size_t out_cap, size_t* out_len, size_t* consumed);
+int32_t nx_zstd_decode_host_ex(const uint8_t* in, size_t n, uint8_t* out, size_t out_cap, size_t* out_len, size_t* consumed,
+                               uint32_t flags);
 
 /* Replaces Inflater.inflate(...) as JdkZlibDecoder.decode calls it (JdkZlibDecoder.java:254-296) for n
  * independent raw deflate (RFC 1951) streams, each resumable at symbol granularity: a call takes
@@ -555,6 +583,35 @@ const char* nx_zstd_encoder_error(nx_zstd_encoder* e);
 size_t nx_zstd_max_encoded_length(size_t pending, int32_t block_size);
 int64_t nx_zstd_encoder_encode(nx_zstd_encoder* e, const uint8_t* in, size_t n, uint8_t* out, size_t out_cap);
 int64_t nx_zstd_encoder_flush(nx_zstd_encoder* e, uint8_t* out, size_t out_cap);
+
+/* ZstdDecoder(maximumAllocationSize)  ZstdDecoder.java:59-122.  NULL for a negative size
+ * (checkPositiveOrZero, :64).  _decode as nx_lzf_decoder_decode: in[0..n) is the cumulation, *consumed the
+ * bytes read.  The cumulation is walked with nx_zstd_next_frame: skippable frames are consumed and
+ * produce nothing (libzstd's streaming decoder, continuous as :139 sets it, steps over them), and every
+ * complete Zstandard frame of the call goes into ONE nx_zstd_decode_batch_ex launch with
+ * NX_ZSTD_DECODE_VERIFY_CHECKSUM, each in a slot of its out_bound: one copy of the bytes to the device,
+ * one launch, one copy of results and output back.  A frame the input ends inside is left unconsumed
+ * (*consumed stops at its first byte) and the call returns NX_OK with what came before it.
+ * Differs from the reference: it hands partial frames to libzstd's streaming state and may fire a frame's
+ * first blocks before the rest has arrived; this handle emits a frame when it is whole (resuming inside a
+ * frame is not built), so the cumulation can grow to a whole frame.  What is the same: the concatenation
+ * of all messages is libzstd's output for the complete frames received so far; with
+ * maximum_allocation_size > 0 no message is longer than that and a longer frame is cut into several
+ * (:99-110), with 0 a non-empty frame is one message; an empty frame fires nothing (:105).
+ * On the first frame whose status is not NX_OK, from the walker or the kernel, the messages of the frames
+ * before it in the call are delivered and the call returns that status with err_msg its status string
+ * (zstd-jni's ZstdException text for the libzstd error of the same name); the handle is then CORRUPTED
+ * (:71-75,117): every later call consumes all of its input and delivers nothing.  The decoder's limits
+ * are failures of this kind: a window, content size or out_bound above 128 MiB (NX_ERR_ZSTD_WINDOW; the
+ * bound of a frame without Frame_Content_Size can exceed what it regenerates), a frame of 2 GiB or more
+ * of compressed bytes (the same code), a Dictionary_ID.
+ * nx_zstd_decoder_stats: the batch launches the handle has made and the frames they held (tests). */
+typedef struct nx_zstd_decoder nx_zstd_decoder;
+nx_zstd_decoder* nx_zstd_decoder_new(int32_t maximum_allocation_size);
+void nx_zstd_decoder_free(nx_zstd_decoder* d);
+int32_t nx_zstd_decoder_decode(nx_zstd_decoder* d, const uint8_t* in, size_t n, size_t* consumed,
+                               const nx_msg** msgs, size_t* n_msgs, const char** err_msg);
+int32_t nx_zstd_decoder_stats(const nx_zstd_decoder* d, uint64_t* launches, uint64_t* frames);
 
 /* JdkZlibEncoder(wrapper, compressionLevel)  JdkZlibEncoder.java:123-137,214-276,308-340.  wrapper is
  * ZlibWrapper's ordinal (0 ZLIB, 1 GZIP, 2 NONE); NULL for 3 (ZLIB_OR_NONE, :128-132) and for a level

@@ -81,16 +81,17 @@
  * (%d bytes) exceeds the maximum allowable size (%d bytes)" or "too much data to allocate a buffer for
  * compression" (nx_zstd_encoder_error has the message). */
 #define NX_ERR_ZSTD_ENCODE_SIZE           (-80)
-/* Zstandard frame decoding (nx_zstd_decode_batch, nx_zstd_frame_info, nx_zstd_decode_host).  zstd-jni turns
- * every libzstd error into a ZstdException that ZstdDecoder.java wraps in DecompressionException; the codes
- * follow libzstd's error names. */
+/* Zstandard frame decoding (nx_zstd_decode_batch[_ex], nx_zstd_frame_info, nx_zstd_next_frame,
+ * nx_zstd_decode_host[_ex], nx_zstd_decoder_decode).  zstd-jni turns every libzstd error into a ZstdException
+ * that ZstdDecoder.java wraps in DecompressionException; the codes follow libzstd's error names. */
 #define NX_ERR_ZSTD_WINDOW                (-81)  /* frameParameter_windowTooLarge: Window_Size or content size above 128 MiB */
 #define NX_ERR_ZSTD_DICTIONARY            (-82)  /* dictionary_wrong: the frame names a dictionary (Dictionary_ID != 0) */
-#define NX_ERR_ZSTD_CHECKSUM_UNSUPPORTED  (-83)  /* Content_Checksum flag set: XXH64 is not verified here, so the frame is refused */
+#define NX_ERR_ZSTD_CHECKSUM_UNSUPPORTED  (-83)  /* Content_Checksum flag set: refused by the entry points without VERIFY_CHECKSUM */
 #define NX_ERR_ZSTD_MAGIC                 (-84)  /* prefix_unknown: not a Zstandard frame (skippable frames included) */
 #define NX_ERR_ZSTD_TRUNCATED             (-85)  /* srcSize_wrong: the input ends inside the frame (frame_info: more input needed) */
 #define NX_ERR_ZSTD_CORRUPT               (-86)  /* corruption_detected */
 #define NX_ERR_ZSTD_OUTPUT_FULL           (-87)  /* dstSize_tooSmall: the regenerated bytes do not fit out_cap */
+#define NX_ERR_ZSTD_CHECKSUM              (-88)  /* checksum_wrong: XXH64 of the regenerated bytes is not the frame's Content_Checksum */
 
 /* Device frame scan (nx_snappy_frame_scan_batch), one code per SnappyFrameDecoder throw site: */
 /* :116-118  "Unexpected length of stream identifier: %d" */

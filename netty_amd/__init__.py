@@ -27,6 +27,7 @@ from .handlers import (  # noqa: F401
     SnappyFramedDecoder,
     SnappyFramedEncoder,
     ZlibWrapper,
+    ZstdDecoder,
     ZstdEncoder,
 )
 

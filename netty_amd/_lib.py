@@ -52,9 +52,12 @@ _SIGS = {
     "nx_zstd_max_compressed_length": (sz, [sz]),
     "nx_zstd_encode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, i32, vp]),
     "nx_zstd_decode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]),
+    "nx_zstd_decode_batch_ex": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, vp]),
     "nx_zstd_decoder_reserve": (i32, [u32, vp]),
     "nx_zstd_frame_info": (i32, [C.c_char_p, sz, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]),
+    "nx_zstd_next_frame": (i32, [C.c_char_p, sz, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]),
     "nx_zstd_decode_host": (i32, [C.c_char_p, sz, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
+    "nx_zstd_decode_host_ex": (i32, [C.c_char_p, sz, vp, sz, C.POINTER(sz), C.POINTER(sz), u32]),
     "nx_inflate_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]),
     "nx_lzf_encode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, vp]),
     "nx_lzf_decode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, vp]),
@@ -136,6 +139,11 @@ _SIGS = {
     "nx_zstd_max_encoded_length": (sz, [sz, i32]),
     "nx_zstd_encoder_encode": (i64, [vp, C.c_char_p, sz, vp, sz]),
     "nx_zstd_encoder_flush": (i64, [vp, vp, sz]),
+    "nx_zstd_decoder_new": (vp, [i32]),
+    "nx_zstd_decoder_free": (None, [vp]),
+    "nx_zstd_decoder_decode": (i32, [vp, C.c_char_p, sz, C.POINTER(sz), C.POINTER(C.POINTER(NxMsg)),
+                                     C.POINTER(sz), C.POINTER(C.c_char_p)]),
+    "nx_zstd_decoder_stats": (i32, [vp, C.POINTER(u64), C.POINTER(u64)]),
     "nx_zlib_encoder_new": (vp, [i32, i32]),
     "nx_zlib_encoder_new_dict": (vp, [i32, C.c_char_p, sz]),
     "nx_zlib_encoder_free": (None, [vp]),

@@ -236,18 +236,29 @@ ZSTD_FRAME_SINGLE_SEGMENT, ZSTD_FRAME_CHECKSUM = 1, 2
 ZSTD_CONTENT_SIZE_UNKNOWN = 2 ** 64 - 1
 
 
-def zstd_decode(inp, in_off, in_len, out, out_off, out_cap):
+ZSTD_DECODE_VERIFY_CHECKSUM = 1
+ZSTD_KIND_FRAME, ZSTD_KIND_SKIPPABLE = 0, 1
+
+
+def zstd_decode(inp, in_off, in_len, out, out_off, out_cap, verify_checksum: bool = False):
     """One complete Zstandard frame per item (nx_zstd_decode_batch): item i starts at inp[in_off[i]], bytes
     after its frame inside in_len[i] are left alone; it regenerates into out[out_off[i] : + out_cap[i]].
     Returns (consumed, out_len, status): the frame's compressed size, the regenerated size (on an error,
-    what was written before it) and 0 or one NX_ERR_ZSTD_* code per item."""
+    what was written before it) and 0 or one NX_ERR_ZSTD_* code per item.  verify_checksum
+    (nx_zstd_decode_batch_ex, NX_ZSTD_DECODE_VERIFY_CHECKSUM): a frame with a content checksum is decoded
+    and its XXH64 verified in the same launch (a mismatch is NX_ERR_ZSTD_CHECKSUM, -88) instead of refused."""
     n = in_len.numel()
     dev = inp.device
     consumed = torch.empty(n, dtype=torch.int32, device=dev)
     out_len = torch.empty(n, dtype=torch.int32, device=dev)
     status = torch.empty(n, dtype=torch.int32, device=dev)
-    _chk(_lib.load().nx_zstd_decode_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_cap),
-                                          _ptr(consumed), _ptr(out_len), _ptr(status), n, _stream()), "nx_zstd_decode_batch")
+    if not verify_checksum:
+        _chk(_lib.load().nx_zstd_decode_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_cap),
+                                              _ptr(consumed), _ptr(out_len), _ptr(status), n, _stream()), "nx_zstd_decode_batch")
+    else:
+        _chk(_lib.load().nx_zstd_decode_batch_ex(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_cap),
+                                                 _ptr(consumed), _ptr(out_len), _ptr(status), n, ZSTD_DECODE_VERIFY_CHECKSUM,
+                                                 _stream()), "nx_zstd_decode_batch_ex")
     return consumed, out_len, status
 
 
@@ -268,6 +279,20 @@ def zstd_frame_info(data: bytes):
     if st != 0:
         return st, 0, None, 0
     return 0, fb.value, None if cs.value == ZSTD_CONTENT_SIZE_UNKNOWN else cs.value, fl.value
+
+
+def zstd_next_frame(data: bytes):
+    """nx_zstd_next_frame on host bytes: (status, kind, frame_bytes, out_bound, flags) of the first frame of
+    `data`, a Zstandard frame (ZSTD_KIND_FRAME; out_bound: a size its output always fits, the content size
+    when the header has it) or a skippable one (ZSTD_KIND_SKIPPABLE; out_bound 0); status
+    NX_ERR_ZSTD_TRUNCATED (-85) when `data` ends inside it."""
+    import ctypes as C
+    kind, fb, ob, fl = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+    data = bytes(data)
+    st = _lib.load().nx_zstd_next_frame(data, len(data), C.byref(kind), C.byref(fb), C.byref(ob), C.byref(fl))
+    if st != 0:
+        return st, 0, 0, 0, 0
+    return 0, kind.value, fb.value, ob.value, fl.value
 
 
 INFLATE_STATE_BYTES = 512

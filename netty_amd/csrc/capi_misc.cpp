@@ -23,6 +23,7 @@ extern "C" const char* nx_status_string(int32_t s) {
         case NX_ERR_ZSTD_TRUNCATED: return "Src size is incorrect";
         case NX_ERR_ZSTD_CORRUPT: return "Data corruption detected";
         case NX_ERR_ZSTD_OUTPUT_FULL: return "Destination buffer is too small";
+        case NX_ERR_ZSTD_CHECKSUM: return "Restored data doesn't match checksum";
         case NX_ERR_LZ4_ENCODE_FINISHED: return "encode finished and not enough space to write remaining data";
         case NX_ERR_SNAPPY_PREAMBLE_TOO_LONG: return "Preamble is greater than 4 bytes";
         case NX_ERR_SNAPPY_OFFSET_ZERO: return "Offset is less than minimum permissible value";

@@ -1042,6 +1042,122 @@ extern "C" int64_t nx_zstd_encoder_flush(nx_zstd_encoder* e, uint8_t* out, size_
     return w;
 }
 
+// ------------------------------------------------------------------ ZstdDecoder
+// ZstdDecoder.java:59-122 over nx_zstd_decode_batch_ex: the cumulation is walked on the host
+// (nx_zstd_next_frame), every complete frame of the call is an item of one launch.  Where the handle
+// departs from the reference (whole frames only) is said at its declaration in netty_amd.h.
+extern "C" nx_zstd_decoder* nx_zstd_decoder_new(int32_t maximum_allocation_size) {
+    if (maximum_allocation_size < 0) return nullptr;  // checkPositiveOrZero (:64)
+    auto* d = new nx_zstd_decoder();
+    if (!d->g.hold(nx::WsKind::ZstdDec)) {
+        delete d;
+        return nullptr;
+    }
+    d->max_alloc = maximum_allocation_size;
+    return d;
+}
+extern "C" void nx_zstd_decoder_free(nx_zstd_decoder* d) { delete d; }
+extern "C" int32_t nx_zstd_decoder_stats(const nx_zstd_decoder* d, uint64_t* launches, uint64_t* frames) {
+    if (!d || !launches || !frames) return NX_ERR_INVALID_ARG;
+    *launches = d->launches;
+    *frames = d->frames;
+    return NX_OK;
+}
+
+extern "C" int32_t nx_zstd_decoder_decode(nx_zstd_decoder* d, const uint8_t* in, size_t n, size_t* consumed, const nx_msg** msgs,
+                                          size_t* n_msgs, const char** err_msg) {
+    const nx::NoGrowScope no_grow;
+    if (!d || (!in && n) || !consumed || !msgs || !n_msgs) return NX_ERR_INVALID_ARG;
+    MsgList& ml = d->ml;
+    ml.clear();
+    *consumed = 0;
+    *msgs = nullptr;
+    *n_msgs = 0;
+    if (err_msg) *err_msg = nullptr;
+    if (d->corrupted) {  // :71-75: in.skipBytes(in.readableBytes())
+        *consumed = n;
+        return NX_OK;
+    }
+    // the walk: skippable frames are stepped over, complete frames become items, a frame the input ends
+    // inside stops it; `fail` is the status of the first frame the walker refuses
+    constexpr uint64_t kMaxBound = 128ull << 20, kMaxFrameBytes = 0x7FFFFFFFull;  // the kernel's positions and lengths
+    struct Item {
+        uint64_t in_off, out_off;
+        uint32_t in_len, out_cap;
+    };
+    std::vector<Item> items;
+    size_t pos = 0;
+    uint64_t oc = 0;
+    int32_t fail = NX_OK;
+    while (pos < n) {
+        uint32_t kind = 0, flags = 0;
+        uint64_t fb = 0, bound = 0;
+        const int32_t st = nx_zstd_next_frame(in + pos, n - pos, &kind, &fb, &bound, &flags);
+        if (st == NX_ERR_ZSTD_TRUNCATED) break;
+        if (st == NX_OK && kind == NX_ZSTD_KIND_FRAME && (bound > kMaxBound || fb > kMaxFrameBytes)) fail = NX_ERR_ZSTD_WINDOW;
+        if (st != NX_OK) fail = st;
+        if (fail != NX_OK) break;
+        if (kind == NX_ZSTD_KIND_FRAME) {
+            items.push_back({pos, oc, (uint32_t)fb, (uint32_t)bound});
+            oc += (bound + 15) / 16 * 16;
+        }
+        pos += (size_t)fb;
+    }
+    if (!items.empty()) {
+        // one copy of the bytes and one of the items' geometry in, one launch, one copy back: the device
+        // output starts with the three result arrays, the slots follow
+        Gpu& g = d->g;
+        const uint32_t nb = (uint32_t)items.size();
+        const size_t res = ((size_t)12 * nb + 15) / 16 * 16;
+        const size_t bytes = (size_t)items.back().in_off + items.back().in_len;
+        std::vector<uint64_t> par(3ull * nb);  // in_off, out_off, then in_len and out_cap (32 bits each)
+        uint32_t* par32 = reinterpret_cast<uint32_t*>(par.data() + 2ull * nb);
+        for (uint32_t i = 0; i < nb; ++i) {
+            par[i] = items[i].in_off;
+            par[nb + i] = res + items[i].out_off;
+            par32[i] = items[i].in_len;
+            par32[nb + i] = items[i].out_cap;
+        }
+        if (!g.din.ensure(bytes) || !g.a0.ensure(24ull * nb) || !g.dout.ensure(res + oc)) return NX_ERR_HIP;
+        if (!g.h2d(g.din.p, in, bytes) || !g.h2d(g.a0.p, par.data(), 24ull * nb)) return NX_ERR_HIP;
+        const uint64_t* dpar = g.a0.as<uint64_t>();
+        const uint32_t* dpar32 = reinterpret_cast<const uint32_t*>(dpar + 2ull * nb);
+        uint32_t* dres = g.dout.as<uint32_t>();
+        const int32_t r = nx_zstd_decode_batch_ex(g.din.as<uint8_t>(), dpar, dpar32, g.dout.as<uint8_t>(), dpar + nb, dpar32 + nb, dres,
+                                                  dres + nb, reinterpret_cast<int32_t*>(dres + 2ull * nb), nb,
+                                                  NX_ZSTD_DECODE_VERIFY_CHECKSUM, g.s);
+        if (r != NX_OK) return r;
+        d->back.resize(res + oc);
+        if (!g.d2h(d->back.data(), g.dout.p, res + oc) || !g.sync()) return NX_ERR_HIP;
+        d->launches += 1;
+        d->frames += nb;
+        const uint32_t* out_len = reinterpret_cast<const uint32_t*>(d->back.data()) + nb;
+        const int32_t* status = reinterpret_cast<const int32_t*>(d->back.data()) + 2ull * nb;
+        for (uint32_t i = 0; i < nb; ++i) {
+            if (status[i] != NX_OK) {  // the first failing frame: what the walker found later comes after it
+                fail = status[i];
+                break;
+            }
+            // :99-110: buffers of min(maximumAllocationSize, uncompressedLength), fired while readable
+            const uint8_t* o = d->back.data() + res + items[i].out_off;
+            const size_t len = out_len[i] <= items[i].out_cap ? out_len[i] : items[i].out_cap;
+            const size_t piece = d->max_alloc > 0 ? (size_t)d->max_alloc : len;
+            for (size_t at = 0; at < len; at += piece) ml.msgs.push_back({o + at, len - at < piece ? len - at : piece});
+        }
+    }
+    *msgs = ml.msgs.data();
+    *n_msgs = ml.msgs.size();
+    if (fail != NX_OK) {  // :116-118: CORRUPTED, the exception's text is libzstd's for the error
+        d->corrupted = true;
+        ml.err = nx_status_string(fail);
+        if (err_msg) *err_msg = ml.err.c_str();
+        *consumed = n;
+        return fail;
+    }
+    *consumed = pos;
+    return NX_OK;
+}
+
 extern "C" nx_lz4_frame_decoder* nx_lz4_frame_decoder_new(int32_t validate_checksums) {
     auto* d = new nx_lz4_frame_decoder();
     if (!d->g.hold(nx::WsKind::DecRecords)) {

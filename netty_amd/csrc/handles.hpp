@@ -199,3 +199,14 @@ struct nx_snappy_frame_decoder {
 inline void nx_decoder_unref(nx_snappy_frame_decoder* d) {
     if (d && d->refs.fetch_sub(1) == 1) delete d;
 }
+
+// ZstdDecoder (handlers.cpp): stateless between frames, so the handle is its options, the CORRUPTED
+// state and the messages of the last call.
+struct nx_zstd_decoder {
+    nx::h::Gpu g;
+    nx::h::MsgList ml;
+    int32_t max_alloc = 0;       // maximumAllocationSize (ZstdDecoder.java:44), 0: no limit
+    bool corrupted = false;      // State.CORRUPTED (:54-57)
+    std::vector<uint8_t> back;   // the last launch's results and output slots, as copied back
+    uint64_t launches = 0, frames = 0;  // nx_zstd_decoder_stats
+};

@@ -1,5 +1,6 @@
-// zstd_decode.hip — Zstandard frame decoder over a batch of complete frames (nx_zstd_decode_batch; what
-// Zstd.decompress does for ZstdDecoder.java, one frame per item).
+// zstd_decode.hip — Zstandard frame decoder over a batch of complete frames (nx_zstd_decode_batch and
+// nx_zstd_decode_batch_ex, which also verifies a frame's content checksum; what Zstd.decompress does for
+// ZstdDecoder.java, one frame per item).
 //
 // One wave per frame (a block is one wave), as k_inflate: the lanes of a wave share every branch and
 // the tables fit its LDS.  The format logic is zstd_decode_core.hpp, the same functions the host decoder
@@ -12,7 +13,8 @@
 //   - sequences decode in tiles of 64 on lane 0 (the core's step: three interleaved FSE states, the
 //     repeat offsets, every bound checked) into LDS as (literal length, match length, resolved offset);
 //     the whole wave then runs the tile: literal runs and matches 64 bytes per step, an overlapping
-//     match reading source byte k mod offset, so every source byte lies before the match.
+//     match reading source byte k mod offset, so every source byte lies before the match;
+//   - the content checksum (content_checksum): XXH64 of the frame's output, read back once.
 // The wave reads back its own output (matches) and its own literals from HBM under inflate.hip's
 // discipline: wait for the wave's own stores (s_waitcnt vmcnt(0)), then load with agent scope, past
 // the vector L1.
@@ -34,10 +36,14 @@ struct WaveLds {
     Tables T;
     Entropy E;
     SeqCursor C;
-    Seq tile[kTile];
+    union {
+        Seq tile[kTile];
+        uint64_t stage[64];  // the checksum's staging, after the last block: 16 stripes, 8 bytes a lane
+    };
     HufStreams S;
     uint32_t mail[8];
 };
+constexpr uint32_t kVerifyMail = 7;  // mail[7]: NX_ZSTD_DECODE_VERIFY_CHECKSUM of the launch (the blocks use mail[0..5])
 
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ void wave_sync() {
@@ -159,11 +165,45 @@ __device__ int32_t decode_block(WaveLds& L, const uint8_t* in, uint32_t n, uint3
     return NX_OK;
 }
 
+// The low 32 bits of XXH64 (seed 0) of out[0, len), a frame's whole regenerated content, which the wave
+// reads back as its own stores.  A pass stages 16 stripes (512 bytes) in LDS, every lane fetching 8 of
+// their bytes one by one (out has any alignment); XXH64's four accumulators are serial chains over the
+// stripes, so lanes 0..3 then carry one each through the 16 in order.  Lane 0 merges the four and runs
+// the tail and the avalanche.  The same value on every lane.
+__device__ uint32_t content_checksum(WaveLds& L, const uint8_t* out, uint32_t len, int lane) {
+    own_stores_done();
+    const uint32_t stripes = len >> 5;
+    uint64_t acc = xxh64_acc_init((uint32_t)lane & 3u, 0);
+    for (uint32_t s0 = 0; s0 < stripes; s0 += 16u) {
+        const uint32_t m = stripes - s0 < 16u ? stripes - s0 : 16u;
+        wave_sync();  // the stage (and before the first pass the tile it shares memory with) has been read
+        if ((uint32_t)lane < 4u * m) {
+            const uint8_t* p = out + ((size_t)s0 << 5) + 8u * (uint32_t)lane;
+            uint64_t v = 0;
+            for (uint32_t b = 0; b < 8u; ++b) v |= (uint64_t)load_own(p + b) << (8u * b);
+            L.stage[lane] = v;
+        }
+        wave_sync();
+        if (lane < 4)
+            for (uint32_t s = 0; s < m; ++s) acc = xxh64_round(acc, L.stage[4u * s + (uint32_t)lane]);
+    }
+    wave_sync();
+    if (lane < 4) L.stage[lane] = acc;
+    wave_sync();
+    if (lane == 0) {
+        const uint8_t* t = out + ((size_t)stripes << 5);
+        L.mail[0] = (uint32_t)xxh64_finish(L.stage, len, 0, [t](uint32_t i) -> uint32_t { return load_own(t + i); });
+    }
+    wave_sync();
+    return uni(L.mail[0]);
+}
+
 __device__ void decode_frame(WaveLds& L, const uint8_t* in, uint32_t n, uint8_t* out, uint32_t cap, uint8_t* ws, uint32_t* consumed,
                              uint32_t* out_len, int32_t* status, int lane) {
     FrameHeader H;
     int32_t st = (int32_t)uni((uint32_t)parse_frame_header(in, n, &H));  // the same on every lane
-    if (st == NX_OK && H.checksum) st = NX_ERR_ZSTD_CHECKSUM_UNSUPPORTED;
+    // the launch's flags wait in the mailbox (kVerifyMail), read here only: nothing of them stays live in the blocks
+    if (st == NX_OK && H.checksum && !uni(L.mail[kVerifyMail])) st = NX_ERR_ZSTD_CHECKSUM_UNSUPPORTED;
     uint32_t pos = 0, q = 0;
     if (st == NX_OK) {
         const uint32_t block_max = uni(H.block_max);
@@ -191,6 +231,15 @@ __device__ void decode_frame(WaveLds& L, const uint8_t* in, uint32_t n, uint8_t*
         }
         const uint64_t fcs = H.content_size;
         if (st == NX_OK && fcs != UINT64_MAX && fcs != (uint64_t)pos) st = NX_ERR_ZSTD_CORRUPT;
+        if (st == NX_OK && (uni(in[4]) & 4u)) {  // Content_Checksum, and the frame passed every other check: its four bytes
+            if (n - q < 4u) {
+                st = NX_ERR_ZSTD_TRUNCATED;
+            } else if (content_checksum(L, out, pos, lane) != uni(le_bytes(in + q, 4))) {
+                st = NX_ERR_ZSTD_CHECKSUM;
+            } else {
+                q += 4u;
+            }
+        }
     }
     if (lane == 0) {
         *consumed = st == NX_OK ? q : 0u;
@@ -202,10 +251,13 @@ __device__ void decode_frame(WaveLds& L, const uint8_t* in, uint32_t n, uint8_t*
 __global__ void __launch_bounds__(64) k_zstd_decode(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                     const uint32_t* __restrict__ in_len, uint8_t* out,
                                                     const uint64_t* __restrict__ out_off, const uint32_t* __restrict__ out_cap,
-                                                    uint8_t* ws, uint32_t* consumed, uint32_t* out_len, int32_t* status, uint32_t n) {
+                                                    uint8_t* ws, uint32_t verify, uint32_t* consumed, uint32_t* out_len,
+                                                    int32_t* status, uint32_t n) {
     __shared__ WaveLds L;
     const int lane = (int)threadIdx.x;
     uint8_t* slot = ws + (size_t)blockIdx.x * kZstdDecSlotBytes;
+    if (lane == 0) L.mail[kVerifyMail] = verify;
+    wave_sync();
     for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
         decode_frame(L, in + in_off[i], uni(in_len[i]), out + out_off[i], uni(out_cap[i]), slot, consumed + i, out_len + i, status + i,
                      lane);
@@ -216,9 +268,10 @@ __global__ void __launch_bounds__(64) k_zstd_decode(const uint8_t* __restrict__ 
 }  // namespace zstdd
 }  // namespace nx
 
-extern "C" int32_t nx_zstd_decode_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
-                                        const uint64_t* out_off, const uint32_t* out_cap, uint32_t* consumed, uint32_t* out_len,
-                                        int32_t* status, uint32_t n, void* stream) {
+extern "C" int32_t nx_zstd_decode_batch_ex(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                                           const uint64_t* out_off, const uint32_t* out_cap, uint32_t* consumed, uint32_t* out_len,
+                                           int32_t* status, uint32_t n, uint32_t flags, void* stream) {
+    if (flags & ~NX_ZSTD_DECODE_VERIFY_CHECKSUM) return NX_ERR_INVALID_ARG;
     if (n == 0) return NX_OK;
     if (!in || !in_off || !in_len || !out || !out_off || !out_cap || !consumed || !out_len || !status) return NX_ERR_INVALID_ARG;
     NX_CLEAR_STALE_ERROR();
@@ -231,9 +284,15 @@ extern "C" int32_t nx_zstd_decode_batch(const uint8_t* in, const uint64_t* in_of
     NX_HIP_CHECK(lease.acquire_part(nx::ws_want(nx::WsKind::ZstdDec, n, cus), &first, &count));
     uint8_t* ws = static_cast<uint8_t*>(lease.ws().p) + first * nx::kZstdDecSlotBytes;
     hipLaunchKernelGGL(nx::zstdd::k_zstd_decode, dim3((unsigned)count), dim3(64), 0, st, in, in_off, in_len, out, out_off, out_cap, ws,
-                       consumed, out_len, status, n);
+                       flags & NX_ZSTD_DECODE_VERIFY_CHECKSUM, consumed, out_len, status, n);
     NX_HIP_CHECK(hipGetLastError());
     return NX_OK;
+}
+
+extern "C" int32_t nx_zstd_decode_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                                        const uint64_t* out_off, const uint32_t* out_cap, uint32_t* consumed, uint32_t* out_len,
+                                        int32_t* status, uint32_t n, void* stream) {
+    return nx_zstd_decode_batch_ex(in, in_off, in_len, out, out_off, out_cap, consumed, out_len, status, n, 0, stream);
 }
 
 // Size the literals workspace now: slots for max_frames frames in flight (at most 8 waves per CU), and

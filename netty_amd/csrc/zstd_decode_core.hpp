@@ -1,7 +1,8 @@
 // zstd_decode_core.hpp — the format logic of the Zstandard decoder (RFC 8878), written once for the
 // host and the device: frame, block and literals headers, the FSE distribution reader and table
-// build, the Huffman tree description, the backward bit reader and the sequence step.  Plain serial
-// functions: no wave intrinsics, no LDS keywords; tables come in as pointers (the kernel hands in LDS,
+// build, the Huffman tree description, the backward bit reader, the sequence step and XXH64 (the
+// content checksum).  Plain serial functions (XXH64 in pieces, for the kernel to spread over lanes):
+// no wave intrinsics, no LDS keywords; tables come in as pointers (the kernel hands in LDS,
 // the host decoder a heap block).  zstd_decode.hip runs them on one lane of a frame's wave and adds the
 // wave-wide copies; zstd_decode_host.cpp runs them on the CPU, where the tests hold them against libzstd.
 //
@@ -73,6 +74,61 @@ NX_HD uint32_t le_bytes(const uint8_t* p, uint32_t n) {
     return v;
 }
 
+// ---- XXH64 (the content checksum: its low 32 bits, seed 0, little-endian after the last block) ----
+// Four accumulators run over the 32-byte stripes, accumulator k over bytes [8k, 8k + 8) of each; they are
+// merged, the length is added, the last len % 32 bytes go in by 8-, 4- and 1-byte steps, then the
+// avalanche.  In pieces, so that the kernel can keep one accumulator per lane and read its own output
+// through its own loads; xxh64() below is the whole of it over plain memory.
+constexpr uint64_t kXxP1 = 0x9E3779B185EBCA87ull, kXxP2 = 0xC2B2AE3D27D4EB4Full, kXxP3 = 0x165667B19E3779F9ull,
+                   kXxP4 = 0x85EBCA77C2B2AE63ull, kXxP5 = 0x27D4EB2F165667C5ull;
+NX_HD uint64_t xx_rotl(uint64_t v, uint32_t r) { return (v << r) | (v >> (64u - r)); }
+NX_HD uint64_t xxh64_acc_init(uint32_t k, uint64_t seed) {  // accumulator k of 4
+    return k == 0u ? seed + kXxP1 + kXxP2 : k == 1u ? seed + kXxP2 : k == 2u ? seed : seed - kXxP1;
+}
+NX_HD uint64_t xxh64_round(uint64_t acc, uint64_t v) { return xx_rotl(acc + v * kXxP2, 31) * kXxP1; }
+// acc[4] after the len / 32 stripes (unused when len < 32); tail(i) = byte i of the last len % 32 bytes
+template <class Tail>
+NX_HD uint64_t xxh64_finish(const uint64_t* acc, uint64_t len, uint64_t seed, Tail tail) {
+    uint64_t h;
+    if (len >= 32u) {
+        h = xx_rotl(acc[0], 1) + xx_rotl(acc[1], 7) + xx_rotl(acc[2], 12) + xx_rotl(acc[3], 18);
+        for (uint32_t k = 0; k < 4u; ++k) h = (h ^ xxh64_round(0, acc[k])) * kXxP1 + kXxP4;
+    } else {
+        h = seed + kXxP5;
+    }
+    h += len;
+    const uint32_t rest = (uint32_t)(len & 31u);
+    uint32_t i = 0;
+    for (; i + 8u <= rest; i += 8u) {
+        uint64_t v = 0;
+        for (uint32_t b = 0; b < 8u; ++b) v |= (uint64_t)tail(i + b) << (8u * b);
+        h = xx_rotl(h ^ xxh64_round(0, v), 27) * kXxP1 + kXxP4;
+    }
+    if (i + 4u <= rest) {
+        uint64_t v = 0;
+        for (uint32_t b = 0; b < 4u; ++b) v |= (uint64_t)tail(i + b) << (8u * b);
+        h = xx_rotl(h ^ v * kXxP1, 23) * kXxP2 + kXxP3;
+        i += 4u;
+    }
+    for (; i < rest; ++i) h = xx_rotl(h ^ (uint64_t)tail(i) * kXxP5, 11) * kXxP1;
+    h = (h ^ (h >> 33)) * kXxP2;
+    h = (h ^ (h >> 29)) * kXxP3;
+    return h ^ (h >> 32);
+}
+NX_HD uint64_t xxh64(const uint8_t* p, size_t n, uint64_t seed) {
+    uint64_t acc[4];
+    for (uint32_t k = 0; k < 4u; ++k) acc[k] = xxh64_acc_init(k, seed);
+    const size_t stripes = n >> 5;
+    for (size_t s = 0; s < stripes; ++s)
+        for (uint32_t k = 0; k < 4u; ++k) {
+            uint64_t v = 0;
+            for (uint32_t b = 0; b < 8u; ++b) v |= (uint64_t)p[32u * s + 8u * k + b] << (8u * b);
+            acc[k] = xxh64_round(acc[k], v);
+        }
+    const uint8_t* t = p + 32u * stripes;
+    return xxh64_finish(acc, n, seed, [t](uint32_t i) -> uint32_t { return t[i]; });
+}
+
 // ---- frame header ----
 struct FrameHeader {
     uint32_t header_bytes;
@@ -83,7 +139,8 @@ struct FrameHeader {
     uint32_t block_max;
 };
 // NX_OK, NX_ERR_ZSTD_TRUNCATED when [in, in + n) ends inside the header, or the header's error.  The
-// Content_Checksum flag is reported, not refused: the walker counts its four bytes, the decoders refuse it.
+// Content_Checksum flag is reported, not refused: the walkers count its four bytes, the decoders verify
+// it or, through the entry points without NX_ZSTD_DECODE_VERIFY_CHECKSUM, refuse the frame.
 NX_HD int32_t parse_frame_header(const uint8_t* in, size_t n, FrameHeader* H) {
     for (uint32_t i = 0; i < 4u && i < n; ++i)
         if (in[i] != (uint8_t)(kMagic >> (8u * i))) return NX_ERR_ZSTD_MAGIC;

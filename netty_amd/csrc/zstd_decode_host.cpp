@@ -1,6 +1,7 @@
-// zstd_decode_host.cpp — the host entries of the Zstandard decoder: nx_zstd_frame_info, the frame
-// walker a handle runs on its cumulation, and nx_zstd_decode_host, a single-threaded decode of one
-// frame from the functions of zstd_decode_core.hpp plus plain copy loops.  The host decoder is the CPU
+// zstd_decode_host.cpp — the host entries of the Zstandard decoder: nx_zstd_frame_info and
+// nx_zstd_next_frame, the frame walkers (the second is what the nx_zstd_decoder handle runs on its
+// cumulation: skippable frames and an output bound too), and nx_zstd_decode_host[_ex], a single-threaded
+// decode of one frame from the functions of zstd_decode_core.hpp plus plain copy loops.  The host decoder is the CPU
 // check of the format core and the GPU tests' second opinion; it is not a product path.
 #include <string.h>
 #include <memory>
@@ -110,14 +111,60 @@ extern "C" int32_t nx_zstd_frame_info(const uint8_t* in, size_t n, uint64_t* fra
     return NX_OK;
 }
 
+extern "C" int32_t nx_zstd_next_frame(const uint8_t* in, size_t n, uint32_t* kind, uint64_t* frame_bytes, uint64_t* out_bound,
+                                      uint32_t* flags) {
+    if ((!in && n) || !kind || !frame_bytes || !out_bound || !flags) return NX_ERR_INVALID_ARG;
+    if (n == 0) return NX_ERR_ZSTD_TRUNCATED;
+    static constexpr uint8_t kSkip[4] = {0x50, 0x2A, 0x4D, 0x18};  // 0x184D2A50..5F: the low nibble is free
+    bool skippable = (in[0] & 0xF0u) == kSkip[0];
+    for (size_t i = 1; i < 4 && i < n && skippable; ++i) skippable = in[i] == kSkip[i];
+    if (skippable) {
+        if (n < 8) return NX_ERR_ZSTD_TRUNCATED;
+        const uint64_t len = le_bytes(in + 4, 4);
+        if (n - 8 < len) return NX_ERR_ZSTD_TRUNCATED;
+        *kind = NX_ZSTD_KIND_SKIPPABLE;
+        *frame_bytes = 8 + len;
+        *out_bound = 0;
+        *flags = 0;
+        return NX_OK;
+    }
+    uint64_t fb = 0, cs = 0;
+    uint32_t fl = 0;
+    const int32_t st = nx_zstd_frame_info(in, n, &fb, &cs, &fl);
+    if (st != NX_OK) return st;
+    if (cs == UINT64_MAX) {  // no Frame_Content_Size: what the blocks can regenerate at most
+        FrameHeader H;
+        (void)parse_frame_header(in, n, &H);  // walked by nx_zstd_frame_info just now, blocks included
+        cs = 0;
+        for (size_t q = H.header_bytes;;) {
+            BlockHeader B;
+            (void)parse_block_header(in + q, n - q, H.block_max, &B);
+            cs += B.type == 2u ? H.block_max : B.size;
+            q += 3u + B.content;
+            if (B.last) break;
+        }
+    }
+    *kind = NX_ZSTD_KIND_FRAME;
+    *frame_bytes = fb;
+    *out_bound = cs;
+    *flags = fl;
+    return NX_OK;
+}
+
 extern "C" int32_t nx_zstd_decode_host(const uint8_t* in, size_t n, uint8_t* out, size_t out_cap, size_t* out_len, size_t* consumed) {
+    return nx_zstd_decode_host_ex(in, n, out, out_cap, out_len, consumed, 0);
+}
+
+extern "C" int32_t nx_zstd_decode_host_ex(const uint8_t* in, size_t n, uint8_t* out, size_t out_cap, size_t* out_len, size_t* consumed,
+                                          uint32_t flags) {
     if ((!in && n) || (!out && out_cap) || !out_len || !consumed) return NX_ERR_INVALID_ARG;
+    if (flags & ~NX_ZSTD_DECODE_VERIFY_CHECKSUM) return NX_ERR_INVALID_ARG;
     *out_len = 0;
     *consumed = 0;
     FrameHeader H;
     int32_t st = parse_frame_header(in, n, &H);
     if (st != NX_OK) return st;
-    if (H.checksum) return NX_ERR_ZSTD_CHECKSUM_UNSUPPORTED;
+    if (H.checksum && !(flags & NX_ZSTD_DECODE_VERIFY_CHECKSUM)) return NX_ERR_ZSTD_CHECKSUM_UNSUPPORTED;
     std::unique_ptr<Tables> T(new Tables);
     std::vector<uint8_t> lits(kBlockMax);
     Entropy E;
@@ -145,6 +192,11 @@ extern "C" int32_t nx_zstd_decode_host(const uint8_t* in, size_t n, uint8_t* out
     *out_len = O.pos;
     if (st != NX_OK) return st;
     if (H.content_size != UINT64_MAX && H.content_size != O.pos) return NX_ERR_ZSTD_CORRUPT;
+    if (H.checksum) {  // the low 32 bits of XXH64 of the whole content, little-endian after the last block
+        if (n - q < 4) return NX_ERR_ZSTD_TRUNCATED;
+        if ((uint32_t)xxh64(O.p, O.pos, 0) != le_bytes(in + q, 4)) return NX_ERR_ZSTD_CHECKSUM;
+        q += 4;
+    }
     *consumed = q;
     return NX_OK;
 }

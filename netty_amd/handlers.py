@@ -340,6 +340,33 @@ class ZstdEncoder(_Encoder):
         return self._ret(_lib.load().nx_zstd_encoder_flush(self._h, out, cap), out)
 
 
+class ZstdDecoder(_Decoder):
+    """ZstdDecoder.java:59-122 over the GPU Zstandard frame decoder (nx_zstd_decoder_*).  Every complete
+    frame of a read is decoded in one launch, content checksums verified (XXH64) and skippable frames
+    stepped over; the concatenation of the messages is libzstd's output for the complete frames received
+    so far.  With maximum_allocation_size > 0 no message is longer than that (a longer frame is cut into
+    several, :99-110), with 0 a frame is one message; an empty frame fires none.  Unlike the reference,
+    a frame is emitted when it is whole: a partial frame waits in the cumulation (readable_bytes()).
+    The first bad frame raises DecompressionException with libzstd's text (its code as .status, the
+    messages of the frames before it as .decoded); afterwards input is swallowed (State.CORRUPTED)."""
+
+    _free = "nx_zstd_decoder_free"
+    _decode_fn = "nx_zstd_decoder_decode"
+
+    def __init__(self, maximum_allocation_size: int = 4 * 1024 * 1024):
+        super().__init__()
+        if maximum_allocation_size < 0:  # ObjectUtil.checkPositiveOrZero (:64)
+            raise ValueError(f"maximumAllocationSize : {maximum_allocation_size} (expected: >= 0)")
+        self.maximum_allocation_size = int(maximum_allocation_size)
+        self._h = _new(_lib.load().nx_zstd_decoder_new(self.maximum_allocation_size), "ZstdDecoder")
+
+    def stats(self) -> dict:
+        """batch launches made so far and the frames they held (one launch per read that completes a frame)"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        _lib.load().nx_zstd_decoder_stats(self._h, C.byref(a), C.byref(b))
+        return {"launches": a.value, "frames": b.value}
+
+
 class ZlibWrapper(enum.IntEnum):
     """ZlibWrapper.java:21-40 (the ordinals the C-ABI takes)"""
     ZLIB = 0

@@ -5,6 +5,9 @@ Steps, each a fresh child process under its own `timeout` (the parent never touc
 first failing step ends the run):
   gpu_encoder  n x 64 KiB k_textgen chunks as the project's encoder wrote them, then decoded: HIP events
                around batch.zstd_decode, 2 warm-up calls and 5 timed, output checked against the source.
+  gpu_encoder_checksum
+               the same frames with a content checksum each (the Content_Checksum flag set, the low 32 bits of
+               XXH64 of the chunk appended), decoded with verify_checksum=True: what verification costs.
   gpu_libzstd3 the first `sample` chunks compressed by libzstd level 3 on the host, decoded the same way.
   host         libzstd's own decode of the same `sample` level-3 frames on 16 threads.
 Prints one JSON line per step.  DESIGN.md section 4 "Zstandard decode" records the figures.
@@ -20,10 +23,10 @@ from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 L = 65536
-STEP_LIMIT_S = {"gpu_encoder": 240, "gpu_libzstd3": 180, "host": 180}
+STEP_LIMIT_S = {"gpu_encoder": 240, "gpu_encoder_checksum": 300, "gpu_libzstd3": 180, "host": 180}
 
 
-def _time_decode(B, torch, enc, eoff, elen, n, dev, src):
+def _time_decode(B, torch, enc, eoff, elen, n, dev, src, verify=False):
     off = torch.arange(n, dtype=torch.int64, device=dev) * L
     dec = torch.empty(n * L, dtype=torch.uint8, device=dev)
     cap = torch.full((n,), L, dtype=torch.int32, device=dev)
@@ -31,7 +34,8 @@ def _time_decode(B, torch, enc, eoff, elen, n, dev, src):
     for it in range(7):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        cons, olen, st = B.zstd_decode(enc, eoff, elen, dec, off, cap)
+        cons, olen, st = B.zstd_decode(enc, eoff, elen, dec, off, cap, verify_checksum=True) if verify else \
+            B.zstd_decode(enc, eoff, elen, dec, off, cap)
         b.record()
         torch.cuda.synchronize()
         if it >= 2:
@@ -49,14 +53,27 @@ def _level3(chunks):
         return list(ex.map(lambda c: codec.compress(c).to_pybytes(), chunks))
 
 
+def _add_checksums(torch, enc, eoff, elen, slot, src, n):
+    """make every frame of enc a checksummed one, in place; returns the new lengths"""
+    import numpy as np
+    import xxhash
+    host = src.cpu().numpy()
+    sums = np.array([xxhash.xxh64_intdigest(host[k * L:(k + 1) * L]) & 0xFFFFFFFF for k in range(n)], dtype="<u4")
+    assert int(elen.max()) + 4 <= slot
+    enc[eoff + 4] |= 4  # Frame_Header_Descriptor bit 2
+    at = (eoff + elen.to(torch.int64))[:, None] + torch.arange(4, device=enc.device)[None, :]
+    enc[at] = torch.from_numpy(sums.view(np.uint8).reshape(n, 4)).to(enc.device)
+    return elen + 4
+
+
 def step_gpu(n, sample, which):
     import torch
     from netty_amd import batch as B
     dev = torch.device("cuda:0")
-    n = n if which == "gpu_encoder" else sample
+    n = sample if which == "gpu_libzstd3" else n
     src = torch.empty(n * L, dtype=torch.uint8, device=dev)
     B.textgen(src, 0, n, L)
-    if which == "gpu_encoder":
+    if which != "gpu_libzstd3":
         off = torch.arange(n, dtype=torch.int64, device=dev) * L
         ln = torch.full((n,), L, dtype=torch.int32, device=dev)
         slot = (B.zstd_max_compressed_length(L) + 127) // 128 * 128
@@ -65,11 +82,13 @@ def step_gpu(n, sample, which):
         elen, est = B.zstd_encode(src, off, ln, enc, eoff)
         torch.cuda.synchronize()
         assert int((est != 0).sum()) == 0
+        if which == "gpu_encoder_checksum":
+            elen = _add_checksums(torch, enc, eoff, elen, slot, src, n)
     else:
         host = src.cpu().numpy().tobytes()
         enc, eoff, elen = B.pack(_level3([host[k * L:(k + 1) * L] for k in range(n)]), dev)
     comp = int(elen.sum())
-    ms = _time_decode(B, torch, enc, eoff, elen, n, dev, src)
+    ms = _time_decode(B, torch, enc, eoff, elen, n, dev, src, verify=which == "gpu_encoder_checksum")
     best = min(ms)
     print(json.dumps({"step": which, "chunks": n, "compressed_bytes": comp, "ms": [round(x, 3) for x in ms],
                       "out_gib_s": round(n * L / 2**30 / (best / 1e3), 3)}))
