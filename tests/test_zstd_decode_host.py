@@ -123,3 +123,7 @@ def test_corpus_census(oracle):
     for which in range(3):
         assert {("mode", which, Z.SEQ_PREDEFINED), ("mode", which, Z.SEQ_FSE), ("mode", which, Z.SEQ_REPEAT)} <= fl, which
     assert {"nseq0", "nseq_1b", "nseq_2b"} <= fl
+    ent = I.entropy_census([c.frame for c in I.libzstd_frames(oracle)])   # printed only: what libzstd chose to emit
+    for key in ("ll_log", "of_log", "ml_log", "hw_log", "ll_minus", "of_minus", "ml_minus", "tree_weights", "lit_format"):
+        print(key, sorted(x[1] for x in ent if isinstance(x, tuple) and x[0] == key))
+    print("zero-run flag chains", sorted({x[1] for x in ent if isinstance(x, tuple) and x[0].endswith("_flags")}))

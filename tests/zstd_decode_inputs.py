@@ -120,3 +120,65 @@ def _census_of(frames):
 def census(frames):
     """what the frames exercise, from their headers (tests/zstd_frames.py)"""
     return _census_of(tuple(frames))
+
+
+def entropy_census(frames):
+    """what the frames' entropy tables exercise, read from their bytes (tests/zstd_frames.py, entropy=True):
+    a set of flags such as ("ll_log", 9), ("of_minus", 3), ("ml_flags", (3, 1)), ("tree_weights", 128),
+    ("repeat_after", which, mode), ("live_nseq", 65)"""
+    flags = set()
+    names = ("ll", "of", "ml")
+    for fr in frames:
+        f = Z.parse_frame(fr, entropy=True)
+        assert f.end == len(fr)
+        held = [None, None, None]   # the mode that built the table a Repeat_Mode block would reuse
+        since_tree = None           # what came since the last tree description
+        tree_streams = None
+        for b in f.blocks:
+            if b.type != Z.COMPRESSED:
+                if since_tree is not None:
+                    since_tree.add(("block", b.type))
+                continue
+            if b.lit_type >= Z.LIT_COMPRESSED:
+                flags.add(("lit_format", b.lit_format))
+                flags.add(("lit_regen", b.lit_streams, b.lit_regen))
+                if 1 in b.stream_ends:
+                    flags.add(("stream_end_01", b.lit_streams))
+            if b.lit_type == Z.LIT_COMPRESSED:
+                flags.add(("tree", b.tree))
+                if b.tree == "direct":
+                    flags.add(("tree_weights", b.tree_weights))
+                else:
+                    d = b.tree_dist
+                    flags.update({("hw_log", d.log), ("hw_minus", d.minus)})
+                    if b.weights_end == 1:
+                        flags.add("weights_end_01")
+                since_tree, tree_streams = set(), b.lit_streams
+            elif b.lit_type == Z.LIT_TREELESS:
+                flags.add(("treeless_after", frozenset(since_tree)))
+                flags.add(("treeless_streams", tree_streams, b.lit_streams))
+            elif since_tree is not None:
+                since_tree.add(("lit", b.lit_type))
+            if not b.nseq:
+                if any(held):
+                    flags.add("tables_across_nseq0")
+                continue
+            for which, mode in enumerate(b.modes):
+                if mode == Z.SEQ_REPEAT:
+                    flags.add(("repeat_after", which, held[which]))
+                else:
+                    held[which] = mode
+            for which, sym in b.rle_syms.items():
+                flags.add(("rle_sym", which, sym))
+            for which, d in b.dists.items():
+                n = names[which]
+                flags.update({(n + "_log", d.log), (n + "_minus", d.minus), (n + "_top", d.top), (n + "_symbols", sum(p != 0 for p in d.probs))})
+                flags.update((n + "_flags", c) for c in d.flags)
+                if (1 << d.log) - 1 in d.probs:
+                    flags.add((n + "_size_minus_1", d.minus))
+            if len(b.dists) == 3 and min(d.log for d in b.dists.values()) >= 6:
+                flags.add(("live_nseq", b.nseq))
+            flags.add(("modes", b.modes))
+            if b.seq_end == 1:
+                flags.add("seq_end_01")
+    return flags

@@ -1,6 +1,8 @@
 """A reader of Zstandard frame structure for the tests: frame header, block headers, the literals-section
-header, the first byte of a Huffman tree description and the sequences header.  It decodes no entropy;
-sizes it parses must add up, and it raises ValueError where they cannot."""
+header, the first byte of a Huffman tree description and the sequences header.  With entropy=True also
+the FSE distributions (accuracy log, probabilities, zero-run flags), the form and size of a tree description
+and where each bitstream ends.  It decodes no bitstream; sizes it parses must add up, and it raises
+ValueError where they cannot."""
 from dataclasses import dataclass, field
 
 MAGIC = b"\x28\xb5\x2f\xfd"
@@ -26,6 +28,73 @@ class Block:
     nseq: int = None
     seq_header: int = None
     modes: tuple = None   # (literal lengths, offsets, match lengths)
+    # with entropy=True:
+    tree_weights: int = None   # direct weights: how many are sent
+    tree_dist: object = None   # FSE-compressed weights: their Dist
+    tree_bytes: int = None     # the whole description (0 for Treeless)
+    weights_end: int = None    # FSE-compressed weights: the last byte of their bitstream
+    stream_ends: list = None   # the last byte of each literals stream
+    dists: dict = None         # which -> Dist, for the codes in FSE mode
+    rle_syms: dict = None      # which -> symbol, for the codes in RLE mode
+    seq_end: int = None        # the last byte of the sequence bitstream
+    tables: list = None        # (start, end) in the input of the tree description, the jump table and every code's table
+
+
+@dataclass
+class Dist:
+    log: int
+    probs: list       # -1 = "less than 1"
+    flags: list       # one tuple of 2-bit repeat flags per probability 0 read
+    size: int         # bytes
+
+    @property
+    def minus(self):
+        return sum(p == -1 for p in self.probs)
+
+    @property
+    def top(self):
+        return len(self.probs) - 1
+
+
+def read_distribution(b, p, end, max_syms):
+    """the FSE distribution at b[p:end): RFC 8878 4.1.1"""
+    at = 0
+
+    def take(k):
+        nonlocal at
+        if p * 8 + at + k > end * 8:
+            raise ValueError("distribution runs past its section")
+        v = (int.from_bytes(b[p:end], "little") >> at) & ((1 << k) - 1)
+        at += k
+        return v
+
+    log = take(4) + 5
+    left, probs, flags = 1 << log, [], []
+    while left > 0:
+        if len(probs) >= max_syms:
+            raise ValueError("more symbols than the alphabet")
+        width = (left + 1).bit_length()          # left + 2 values in `width` bits, the lowest ones in one fewer
+        spare = (1 << width) - (left + 2)
+        v = take(width - 1)
+        if v >= spare:
+            v |= take(1) << (width - 1)
+            if v >= 1 << (width - 1):
+                v -= spare
+        left -= abs(v - 1)
+        if left < 0:
+            raise ValueError("probabilities above the table size")
+        probs.append(v - 1)
+        if v == 1:
+            chain = []
+            while True:
+                chain.append(take(2))
+                probs += [0] * chain[-1]
+                if chain[-1] != 3:
+                    break
+            flags.append(tuple(chain))
+    if len(probs) > max_syms:
+        raise ValueError("more symbols than the alphabet")
+    return Dist(log, probs, flags, (at + 7) // 8)
 
 
 @dataclass
@@ -48,7 +117,7 @@ def _le(b, p, n):
     return int.from_bytes(b[p:p + n], "little")
 
 
-def parse_compressed_block(b, p, size, blk):
+def parse_compressed_block(b, p, size, blk, entropy=False):
     end = p + size
     b0 = _le(b, p, 1)
     blk.lit_type, blk.lit_format = b0 & 3, (b0 >> 2) & 3
@@ -71,6 +140,32 @@ def parse_compressed_block(b, p, size, blk):
     q = p + h + blk.lit_comp
     if q > end:
         raise ValueError("literals section runs past its block")
+    if entropy and blk.lit_type >= LIT_COMPRESSED:
+        t = p + h
+        blk.tree_bytes, blk.tables = 0, []
+        if blk.tree == "direct":
+            blk.tree_weights = blk.tree_byte - 127
+            blk.tree_bytes = 1 + (blk.tree_weights + 1) // 2
+        elif blk.tree == "fse":
+            blk.tree_bytes = 1 + blk.tree_byte
+            blk.tree_dist = read_distribution(b, t + 1, t + blk.tree_bytes, 256)
+            blk.weights_end = b[t + blk.tree_bytes - 1]
+        if blk.tree_bytes:
+            blk.tables.append((t, t + blk.tree_bytes))
+        t += blk.tree_bytes
+        if blk.lit_streams == 4:
+            sizes = [_le(b, t + 2 * k, 2) for k in range(3)]
+            blk.tables.append((t, t + 6))
+            t += 6
+            sizes.append(q - t - sum(sizes))
+        else:
+            sizes = [q - t]
+        if min(sizes) < 1:
+            raise ValueError("an empty literals stream")
+        blk.stream_ends = []
+        for n in sizes:
+            t += n
+            blk.stream_ends.append(b[t - 1])
     if q == end:
         raise ValueError("no sequences section")
     s0 = _le(b, q, 1)
@@ -92,9 +187,25 @@ def parse_compressed_block(b, p, size, blk):
     blk.seq_header = n + 1
     if q + n + 1 > end:
         raise ValueError("sequences header runs past its block")
+    if entropy:
+        t = q + n + 1
+        blk.dists, blk.rle_syms, blk.tables = {}, {}, blk.tables or []
+        for which, mode in enumerate(blk.modes):
+            t0 = t
+            if mode == SEQ_RLE:
+                blk.rle_syms[which] = _le(b, t, 1)
+                t += 1
+            elif mode == SEQ_FSE:
+                blk.dists[which] = read_distribution(b, t, end, (36, 32, 53)[which])
+                t += blk.dists[which].size
+            if t > t0:
+                blk.tables.append((t0, t))
+        if t >= end:
+            raise ValueError("no sequence bitstream")
+        blk.seq_end = b[end - 1]
 
 
-def parse_frame(b, p=0):
+def parse_frame(b, p=0, entropy=False):
     if b[p:p + 4] != MAGIC:
         raise ValueError("bad magic")
     fhd = _le(b, p + 4, 1)
@@ -125,7 +236,7 @@ def parse_frame(b, p=0):
         if q + blk.content > len(b):
             raise ValueError("block runs past the input")
         if blk.type == COMPRESSED:
-            parse_compressed_block(b, q, blk.size, blk)
+            parse_compressed_block(b, q, blk.size, blk, entropy)
         q += blk.content
         f.blocks.append(blk)
         if blk.last:

@@ -135,11 +135,18 @@ def run_sequences(out, lits, s, rep):
 
 
 def build(blocks, single=True, window_descriptor=None, with_size=True, **hdr):
-    """blocks: ('raw', bytes) | ('rle', byte, n) | ('seq', lits, Seqs or None).  Returns (frame, expected)."""
-    out, rep, body = bytearray(), [1, 4, 8], b""
+    """blocks: ('raw', bytes) | ('rle', byte, n) | ('seq', lits, Seqs or None) | ('ent', lits, sequences, coding):
+    a block of tests/zstd_entropy.py's encoder, Huffman and FSE coded as `coding` says.  Returns (frame, expected)."""
+    out, rep, body, enc = bytearray(), [1, 4, 8], b"", None
     for i, b in enumerate(blocks):
         last = i == len(blocks) - 1
-        if b[0] == "raw":
+        if b[0] == "ent":
+            if enc is None:
+                import zstd_entropy
+                enc = zstd_entropy.BlockEncoder()  # one per frame: it holds the tables Repeat_Mode and Treeless reuse
+            run_sequences(out, b[1], b[2], rep)
+            body += enc.block(b[1], b[2], b[3], last)
+        elif b[0] == "raw":
             out += b[1]
             body += raw_block(b[1], last)
         elif b[0] == "rle":
