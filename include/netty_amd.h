@@ -77,6 +77,7 @@ int32_t nx_snappy_encode_batch(const uint8_t* in, const uint64_t* in_off, const 
 #define NX_WS_DEFLATE_ENC 6
 #define NX_WS_ZSTD_ENC 7
 #define NX_WS_ZSTD_DEC 8
+#define NX_WS_BZIP2_DEC 9
 int32_t nx_snappy_encoder_reserve(uint32_t max_chunks, void* stream);
 /* The same with a bound (round 6): max_bytes caps the Snappy table workspace for good (0: no cap; 128
  * KiB per lane, whole blocks of 256 lanes above 16 384): batches of any size then run on those lanes
@@ -335,6 +336,50 @@ int32_t nx_zstd_next_frame(const uint8_t* in, size_t n, uint32_t* kind, uint64_t
 int32_t nx_zstd_decode_host(const uint8_t* in, size_t n, uint8_t* out, size_t out_cap, size_t* out_len, size_t* consumed);
 int32_t nx_zstd_decode_host_ex(const uint8_t* in, size_t n, uint8_t* out, size_t out_cap, size_t* out_len, size_t* consumed,
                                uint32_t flags);
+
+/*
+ * Replaces Bzip2Decoder.java (with Bzip2BlockDecompressor, Bzip2HuffmanStageDecoder, Bzip2MoveToFrontTable,
+ * Bzip2BitReader and Crc32) for n independent, complete bzip2 streams.  Item i is the stream that starts at
+ * in[in_off[i]]; only that first stream is decoded and bytes after it inside in_len[i] are left alone
+ * (Bzip2Decoder goes to its EOF state and skips them).  Its bytes go to out[out_off[i] .. + out_cap[i]) and
+ * nothing is ever written outside that range.
+ *   out_len[i]  = the decoded size; on an error, the bytes of the blocks completed before it;
+ *   consumed[i] = the stream's size, up to the byte after the padded combined CRC (0 on an error);
+ *   status[i]   = NX_OK or one NX_ERR_BZIP2_* code (netty_amd_status.h), one per throw site of the reference:
+ *     STREAM_ID, BLOCK_SIZE, BLOCK_HEADER, STREAM_CRC, HUFFMAN_GROUPS, ALPHABET, SELECTORS, DECODING_BLOCK,
+ *     CODE, BLOCK_EXCEEDS, START_POINTER, BLOCK_CRC, and this library's own TRUNCATED (the input ends inside
+ *     the stream; the reference waits for more), OUTPUT_FULL and RANDOMISED.
+ * Differences from the reference: a block with the randomised bit set is refused with
+ * NX_ERR_BZIP2_RANDOMISED (Bzip2BlockDecompressor decodes such blocks through Bzip2Rand's 512-entry table,
+ * which this library does not carry; no encoder has written one since bzip2 0.9.5).  Where the Java throws an
+ * unchecked array-index exception libbz2 decides: a selector index at or above the table count is
+ * DECODING_BLOCK, a code length outside 1..23 or a code index outside the alphabet is CODE.  A block that ends
+ * right after four equal bytes is a run of four.  "block length exceeds max block length"
+ * (Bzip2BlockDecompressor.java:234) cannot be reached under the declared-size check and has no code.
+ * One wave per stream, a stream's blocks one after another; the inverse BWT walk of a block is split into
+ * nx_bzip2_decode_chains() sublists over the wave's lanes.  One slot of NX_WS_BZIP2_DEC workspace per stream
+ * in flight (5.4 MB: a 900 000-byte block's bytes, merged pointers and pre-RLE bytes; at most 4 per CU),
+ * larger batches run on those slots in turn.  nx_bzip2_decoder_reserve(max_streams) sizes that workspace
+ * at start-up and caps it at max_streams slots until nx_workspaces_trim.
+ */
+int32_t nx_bzip2_decode_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                              const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len, uint32_t* consumed,
+                              int32_t* status, uint32_t n, void* stream);
+int32_t nx_bzip2_decoder_reserve(uint32_t max_streams, void* stream);
+uint32_t nx_bzip2_decode_chains(void);
+/*
+ * The first stream of in[0..n) decoded on the host, single-threaded, by the same format functions the kernel
+ * runs (csrc/bzip2_decode_core.hpp), with the contract and codes of an item of nx_bzip2_decode_batch.  NOT a
+ * product path: it is the CPU check of the format logic and the GPU tests' second opinion.
+ */
+int32_t nx_bzip2_decode_host(const uint8_t* in, size_t n, uint8_t* out, size_t out_cap, size_t* out_len, size_t* consumed);
+/*
+ * What the first 14 bytes of a stream say (host only): *level = 1..9 (the declared block size is 100 000 x
+ * level), *is_empty = 1 when the end-of-stream magic follows the header (*first_block_crc = 0), else
+ * *first_block_crc = the first block's stored CRC.  NX_ERR_BZIP2_TRUNCATED while n < 14; otherwise
+ * STREAM_ID, BLOCK_SIZE or BLOCK_HEADER.
+ */
+int32_t nx_bzip2_stream_info(const uint8_t* in, size_t n, uint32_t* level, uint32_t* first_block_crc, uint32_t* is_empty);
 
 /* Replaces Inflater.inflate(...) as JdkZlibDecoder.decode calls it (JdkZlibDecoder.java:254-296) for n
  * independent raw deflate (RFC 1951) streams, each resumable at symbol granularity: a call takes

@@ -93,6 +93,45 @@
 #define NX_ERR_ZSTD_OUTPUT_FULL           (-87)  /* dstSize_tooSmall: the regenerated bytes do not fit out_cap */
 #define NX_ERR_ZSTD_CHECKSUM              (-88)  /* checksum_wrong: XXH64 of the regenerated bytes is not the frame's Content_Checksum */
 
+/* Bzip2 stream decoding (nx_bzip2_decode_batch, nx_bzip2_decode_host, nx_bzip2_stream_info), one code per
+ * throw site of Bzip2Decoder.java and its helpers, with the DecompressionException's message as the status
+ * string.  Bzip2BlockDecompressor.java:234-237 ("block length exceeds max block length") has no code: the
+ * declared-size checks at :206 and :223 keep a block at or below 900 000 bytes, so it cannot be reached. */
+/* Bzip2Decoder.java:108-111  "Unexpected stream identifier contents. Mismatched bzip2 protocol version?" */
+#define NX_ERR_BZIP2_STREAM_ID            (-110)
+/* Bzip2Decoder.java:113-115  "block size is invalid" */
+#define NX_ERR_BZIP2_BLOCK_SIZE           (-111)
+/* Bzip2Decoder.java:131-133  "stream CRC error" */
+#define NX_ERR_BZIP2_STREAM_CRC           (-112)
+/* Bzip2Decoder.java:137-139  "bad block header" */
+#define NX_ERR_BZIP2_BLOCK_HEADER         (-113)
+/* Bzip2Decoder.java:186-188  "incorrect huffman groups number" */
+#define NX_ERR_BZIP2_HUFFMAN_GROUPS       (-114)
+/* Bzip2Decoder.java:190-192  "incorrect alphabet size" */
+#define NX_ERR_BZIP2_ALPHABET             (-115)
+/* Bzip2Decoder.java:201-203  "incorrect selectors number" */
+#define NX_ERR_BZIP2_SELECTORS            (-116)
+/* Bzip2HuffmanStageDecoder.java:178  "error decoding block": the groups outrun the selectors; also a
+ * selector index at or above the table count (an array-index exception in the Java, a data error in libbz2) */
+#define NX_ERR_BZIP2_DECODING_BLOCK       (-117)
+/* Bzip2HuffmanStageDecoder.java:201  "a valid code was not recognised"; also a code length outside 1..23
+ * and a code index outside the alphabet (array-index exceptions in the Java, data errors in libbz2) */
+#define NX_ERR_BZIP2_CODE                 (-118)
+/* Bzip2BlockDecompressor.java:207,224  "block exceeds declared block size" */
+#define NX_ERR_BZIP2_BLOCK_EXCEEDS        (-119)
+/* Bzip2BlockDecompressor.java:254  "start pointer invalid" */
+#define NX_ERR_BZIP2_START_POINTER        (-120)
+/* Bzip2BlockDecompressor.java:346  "block CRC error"; also a block whose inverse BWT closes before its last
+ * byte (the reference walks the cycle again and then fails this check) */
+#define NX_ERR_BZIP2_BLOCK_CRC            (-121)
+/* This library's own: the input ends inside the stream (the reference waits for more input). */
+#define NX_ERR_BZIP2_TRUNCATED            (-122)
+/* This library's own: the decoded bytes do not fit out_cap. */
+#define NX_ERR_BZIP2_OUTPUT_FULL          (-123)
+/* This library's own: the block's randomised bit is set (the reference decodes such blocks; no encoder has
+ * written one since bzip2 0.9.5). */
+#define NX_ERR_BZIP2_RANDOMISED           (-124)
+
 /* Device frame scan (nx_snappy_frame_scan_batch), one code per SnappyFrameDecoder throw site: */
 /* :116-118  "Unexpected length of stream identifier: %d" */
 #define NX_ERR_SNAPPY_STREAM_ID_LENGTH        (-41)

@@ -58,6 +58,11 @@ _SIGS = {
     "nx_zstd_next_frame": (i32, [C.c_char_p, sz, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]),
     "nx_zstd_decode_host": (i32, [C.c_char_p, sz, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
     "nx_zstd_decode_host_ex": (i32, [C.c_char_p, sz, vp, sz, C.POINTER(sz), C.POINTER(sz), u32]),
+    "nx_bzip2_decode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]),
+    "nx_bzip2_decoder_reserve": (i32, [u32, vp]),
+    "nx_bzip2_decode_chains": (u32, []),
+    "nx_bzip2_decode_host": (i32, [C.c_char_p, sz, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
+    "nx_bzip2_stream_info": (i32, [C.c_char_p, sz, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]),
     "nx_inflate_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]),
     "nx_lzf_encode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, vp]),
     "nx_lzf_decode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, vp]),

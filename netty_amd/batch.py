@@ -25,7 +25,7 @@ def _chk(rc, what):
 
 
 # Shared device workspaces (include/netty_amd.h NX_WS_*; csrc/workspace.hpp)
-WS_SNAPPY_ENC, WS_LZ4_ENC, WS_FASTLZ_ENC, WS_LZF_ENC, WS_DEC_RECORDS, WS_LZ4HC_ENC, WS_DEFLATE_ENC, WS_ZSTD_ENC, WS_ZSTD_DEC = range(9)
+WS_SNAPPY_ENC, WS_LZ4_ENC, WS_FASTLZ_ENC, WS_LZF_ENC, WS_DEC_RECORDS, WS_LZ4HC_ENC, WS_DEFLATE_ENC, WS_ZSTD_ENC, WS_ZSTD_DEC, WS_BZIP2_DEC = range(10)
 
 
 def workspace_info(kind: int) -> tuple[int, int]:
@@ -293,6 +293,56 @@ def zstd_next_frame(data: bytes):
     if st != 0:
         return st, 0, 0, 0, 0
     return 0, kind.value, fb.value, ob.value, fl.value
+
+
+def bzip2_decode(inp, in_off, in_len, out, out_off, out_cap):
+    """One complete bzip2 stream per item (nx_bzip2_decode_batch): item i starts at inp[in_off[i]], only its
+    first stream is decoded and bytes after it inside in_len[i] are left alone; it decodes into
+    out[out_off[i] : + out_cap[i]].  Returns (out_len, consumed, status): the decoded size (on an error, the
+    bytes of the blocks completed before it), the stream's compressed size and 0 or one NX_ERR_BZIP2_* code
+    (-110 .. -124) per item.  A block with the randomised bit set is refused (NX_ERR_BZIP2_RANDOMISED, -124)."""
+    n = in_len.numel()
+    dev = inp.device
+    out_len = torch.empty(n, dtype=torch.int32, device=dev)
+    consumed = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    _chk(_lib.load().nx_bzip2_decode_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_cap),
+                                           _ptr(out_len), _ptr(consumed), _ptr(status), n, _stream()), "nx_bzip2_decode_batch")
+    return out_len, consumed, status
+
+
+def bzip2_decoder_reserve(max_streams: int):
+    """nx_bzip2_decoder_reserve: size the decoder's block workspace for max_streams streams in flight now and
+    cap it there until workspaces_trim()."""
+    _chk(_lib.load().nx_bzip2_decoder_reserve(int(max_streams), _stream()), "nx_bzip2_decoder_reserve")
+
+
+def bzip2_decode_chains() -> int:
+    """nx_bzip2_decode_chains: the sublists the kernel splits a block's inverse BWT walk into."""
+    return _lib.load().nx_bzip2_decode_chains()
+
+
+def bzip2_decode_host(data: bytes, out_cap: int):
+    """nx_bzip2_decode_host on host bytes: (status, decoded bytes, consumed) of the first stream of `data`, by
+    the kernel's format functions on the CPU (the tests' second opinion, not a product path)."""
+    import ctypes as C
+    data = bytes(data)
+    buf = C.create_string_buffer(max(int(out_cap), 1))
+    ol, cs = C.c_size_t(0), C.c_size_t(0)
+    st = _lib.load().nx_bzip2_decode_host(data, len(data), C.cast(buf, C.c_void_p), int(out_cap), C.byref(ol), C.byref(cs))
+    return st, buf.raw[:ol.value], cs.value
+
+
+def bzip2_stream_info(data: bytes):
+    """nx_bzip2_stream_info on host bytes: (status, level, first_block_crc, is_empty) from the first 14 bytes
+    of `data`; status NX_ERR_BZIP2_TRUNCATED (-122) while fewer are there."""
+    import ctypes as C
+    data = bytes(data)
+    lv, crc, em = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    st = _lib.load().nx_bzip2_stream_info(data, len(data), C.byref(lv), C.byref(crc), C.byref(em))
+    if st != 0:
+        return st, 0, 0, False
+    return 0, lv.value, crc.value, bool(em.value)
 
 
 INFLATE_STATE_BYTES = 512

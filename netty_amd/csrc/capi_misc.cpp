@@ -24,6 +24,21 @@ extern "C" const char* nx_status_string(int32_t s) {
         case NX_ERR_ZSTD_CORRUPT: return "Data corruption detected";
         case NX_ERR_ZSTD_OUTPUT_FULL: return "Destination buffer is too small";
         case NX_ERR_ZSTD_CHECKSUM: return "Restored data doesn't match checksum";
+        case NX_ERR_BZIP2_STREAM_ID: return "Unexpected stream identifier contents. Mismatched bzip2 protocol version?";
+        case NX_ERR_BZIP2_BLOCK_SIZE: return "block size is invalid";
+        case NX_ERR_BZIP2_STREAM_CRC: return "stream CRC error";
+        case NX_ERR_BZIP2_BLOCK_HEADER: return "bad block header";
+        case NX_ERR_BZIP2_HUFFMAN_GROUPS: return "incorrect huffman groups number";
+        case NX_ERR_BZIP2_ALPHABET: return "incorrect alphabet size";
+        case NX_ERR_BZIP2_SELECTORS: return "incorrect selectors number";
+        case NX_ERR_BZIP2_DECODING_BLOCK: return "error decoding block";
+        case NX_ERR_BZIP2_CODE: return "a valid code was not recognised";
+        case NX_ERR_BZIP2_BLOCK_EXCEEDS: return "block exceeds declared block size";
+        case NX_ERR_BZIP2_START_POINTER: return "start pointer invalid";
+        case NX_ERR_BZIP2_BLOCK_CRC: return "block CRC error";
+        case NX_ERR_BZIP2_TRUNCATED: return "the input ends inside the bzip2 stream";
+        case NX_ERR_BZIP2_OUTPUT_FULL: return "the decoded bytes do not fit the output";
+        case NX_ERR_BZIP2_RANDOMISED: return "randomised bzip2 blocks are not supported";
         case NX_ERR_LZ4_ENCODE_FINISHED: return "encode finished and not enough space to write remaining data";
         case NX_ERR_SNAPPY_PREAMBLE_TOO_LONG: return "Preamble is greater than 4 bytes";
         case NX_ERR_SNAPPY_OFFSET_ZERO: return "Offset is less than minimum permissible value";

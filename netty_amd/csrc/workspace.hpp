@@ -20,7 +20,7 @@
 
 namespace nx {
 
-enum class WsKind : int { SnappyEnc = 0, Lz4Enc, FastLzEnc, LzfEnc, DecRecords, Lz4HcEnc, DeflateEnc, ZstdEnc, ZstdDec, Count };
+enum class WsKind : int { SnappyEnc = 0, Lz4Enc, FastLzEnc, LzfEnc, DecRecords, Lz4HcEnc, DeflateEnc, ZstdEnc, ZstdDec, Bzip2Dec, Count };
 
 // Table geometry per encoder kind (entry bytes, log2 entries per table, waves per CU of its launch);
 // each codec static_asserts its own constants against this.
@@ -38,6 +38,9 @@ struct WsSpec {
 // chunk per slot and launch pair as DeflateEnc, a workspace of its own.
 // ZstdDec: no tables: 128 KiB per frame in flight (the literals of the block being decoded; zstd_decode.hip),
 // leased by part as DecRecords is, one slot per wave of the launch on at most kZstdDecWavesPerCu waves per CU.
+// Bzip2Dec: no tables: one slot per stream in flight holds a block's BWT bytes, merged pointers and pre-RLE
+// bytes (6 x 900 000 bytes and padding; bzip2_decode.hip), leased by part, one slot per wave of the launch on
+// at most kBzip2DecWavesPerCu waves per CU.
 #ifndef NX_LZ4_WPCU  // build options for A/B runs of the alt encoders' occupancy (scripts/build_lib_variant.sh; LZ4 at 20: level)
 #define NX_LZ4_WPCU 16
 #endif
@@ -47,7 +50,7 @@ struct WsSpec {
 #ifndef NX_LZF_WPCU  // LZF: 16 waves per CU measured level with 8 (profiles/r06/s4), so the smaller workspace stays
 #define NX_LZF_WPCU 8
 #endif
-constexpr WsSpec kWsSpec[] = {{8, 14, 20}, {8, 13, NX_LZ4_WPCU}, {8, 13, NX_FLZ_WPCU}, {8, 14, NX_LZF_WPCU}, {0, 0, 0}, {8, 15, 2}, {8, 14, 16}, {8, 16, 16}, {0, 0, 0}};
+constexpr WsSpec kWsSpec[] = {{8, 14, 20}, {8, 13, NX_LZ4_WPCU}, {8, 13, NX_FLZ_WPCU}, {8, 14, NX_LZF_WPCU}, {0, 0, 0}, {8, 15, 2}, {8, 14, 16}, {8, 16, 16}, {0, 0, 0}, {0, 0, 0}};
 static_assert(sizeof(kWsSpec) / sizeof(kWsSpec[0]) == (size_t)WsKind::Count, "one spec per kind");
 constexpr size_t kDecSlotBytes = 16384u * 4u + 8u;  // records of one frame + its count and length
 #ifndef NX_DEC_MAX_FRAMES  // build option for A/B runs (scripts/build_lib_variant.sh)
@@ -56,8 +59,14 @@ constexpr size_t kDecSlotBytes = 16384u * 4u + 8u;  // records of one frame + it
 constexpr uint32_t kDecMaxFrames = NX_DEC_MAX_FRAMES;  // frames per parse/expand launch pair
 constexpr size_t kZstdDecSlotBytes = 128u << 10;  // Block_Maximum_Size: the most literals one block regenerates
 constexpr unsigned kZstdDecWavesPerCu = 8;        // 2 048 frames in flight, 256 MiB, on 256 CUs
+constexpr size_t kBzip2DecSlotBytes = 6u * 900000u + 256u;  // a 900 000-byte block: bytes, 4-byte pointers, pre-RLE bytes
+// k_bzip2_decode keeps about 27 KiB of LDS per wave (tables, selectors, tiles): five waves fit a CU's 160 KiB;
+// four leave one wave per SIMD and 5.2 GiB of slots on 256 CUs
+constexpr unsigned kBzip2DecWavesPerCu = 4;
 // bytes per slot of a kind without tables (0 for the table kinds)
-constexpr size_t ws_plain_slot_bytes(WsKind k) { return k == WsKind::DecRecords ? kDecSlotBytes : k == WsKind::ZstdDec ? kZstdDecSlotBytes : 0; }
+constexpr size_t ws_plain_slot_bytes(WsKind k) {
+    return k == WsKind::DecRecords ? kDecSlotBytes : k == WsKind::ZstdDec ? kZstdDecSlotBytes : k == WsKind::Bzip2Dec ? kBzip2DecSlotBytes : 0;
+}
 
 struct WsUse {  // an in-flight part lease: slots [a, b), done when ev completes
     size_t a, b;
