@@ -78,6 +78,7 @@ int32_t nx_snappy_encode_batch(const uint8_t* in, const uint64_t* in_off, const 
 #define NX_WS_ZSTD_ENC 7
 #define NX_WS_ZSTD_DEC 8
 #define NX_WS_BZIP2_DEC 9
+#define NX_WS_BZIP2_ENC 10
 int32_t nx_snappy_encoder_reserve(uint32_t max_chunks, void* stream);
 /* The same with a bound (round 6): max_bytes caps the Snappy table workspace for good (0: no cap; 128
  * KiB per lane, whole blocks of 256 lanes above 16 384): batches of any size then run on those lanes
@@ -380,6 +381,53 @@ int32_t nx_bzip2_decode_host(const uint8_t* in, size_t n, uint8_t* out, size_t o
  * STREAM_ID, BLOCK_SIZE or BLOCK_HEADER.
  */
 int32_t nx_bzip2_stream_info(const uint8_t* in, size_t n, uint32_t* level, uint32_t* first_block_crc, uint32_t* is_empty);
+
+/*
+ * Replaces Bzip2Encoder.java (with Bzip2BlockCompressor, Bzip2MTFAndRLE2StageEncoder, Bzip2HuffmanStageEncoder,
+ * Bzip2HuffmanAllocator, Bzip2BitWriter and Bzip2MoveToFrontTable) for n independent items at block size
+ * `level` x 100 000.  Item i = in[in_off[i] .. + in_len[i]) becomes what one encode(in) followed by close()
+ * writes: "BZh" and the level digit, its blocks (filled by Bzip2BlockCompressor.write: a byte is accepted while
+ * the block holds at most blockSize - 6 bytes, so multi-block streams are cut where the reference cuts them,
+ * not where libbz2 does), the end magic, the combined CRC and zero padding, in out[out_off[i] .. + out_cap[i]);
+ * nothing is ever written outside that range and slots may start at any byte address.
+ *   out_len[i] = the stream's size (0 on an error);
+ *   status[i]  = NX_OK or NX_ERR_BZIP2_ENCODE_FULL (the stream does not fit out_cap[i];
+ *                nx_bzip2_max_compressed_length(in_len[i], level) always fits).
+ * A level outside 1..9 fails the call with NX_ERR_BZIP2_LEVEL before any launch (the constructor's
+ * IllegalArgumentException, Bzip2Encoder.java:98-101).
+ * Differences from the reference: the Burrows-Wheeler transform is a sort of the block's cyclic rotations
+ * written for the device, not Bzip2DivSufSort; equal rotations (periodic blocks) are ordered by index and the
+ * start pointer is the row of rotation 0.  The claim is a valid stream with the reference's block boundaries and
+ * coding decisions; byte identity with the Java is expected wherever a block's rotations are distinct but is
+ * not claimed (DESIGN.md "Bzip2 encode").
+ * One workgroup per stream, a stream's blocks one after another.  One slot of NX_WS_BZIP2_ENC workspace per
+ * stream in flight, nx_bzip2_encoder_slot_bytes(level) bytes (the block, the sort's two index and two rank
+ * arrays, the transformed bytes, the MTF symbols and the staged output), at most one per CU; larger batches run
+ * on those slots in turn.  nx_bzip2_encoder_reserve(max_streams, level) sizes that workspace at start-up and
+ * caps it there until nx_workspaces_trim; a later call at a higher level runs fewer streams at once on it, and
+ * grows it to one slot of that level if it holds less.
+ */
+int32_t nx_bzip2_encode_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                              const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len, int32_t* status,
+                              uint32_t n, int32_t level, void* stream);
+int32_t nx_bzip2_encoder_reserve(uint32_t max_streams, int32_t level, void* stream);
+uint64_t nx_bzip2_encoder_slot_bytes(int32_t level);
+/*
+ * An upper bound of the stream of an n-byte item at `level` (0 for a level outside 1..9), derived, not
+ * measured: the first stage grows n to at most r = n + n / 4; a block closed with input left holds more than
+ * S - 6 bytes (S = level x 100 000), so there are at most r / (S - 5) + 1 blocks; a block of m bytes takes at
+ * most 105 header bits, 16 + 256 map bits, 18 bits of counts, 6 bits for each of m / 50 + 1 selectors, six
+ * tables of 5 + 258 x (1 + 2 x 19) bits and 20 bits for each of m + 1 symbols; 32 bits of stream header, 80 of
+ * footer and 7 of padding (csrc/bzip2_encode_core.hpp stream_bytes_bound).
+ */
+size_t nx_bzip2_max_compressed_length(size_t n, int32_t level);
+/*
+ * One item encoded on the host, single-threaded, by the same format functions the kernel runs
+ * (csrc/bzip2_encode_core.hpp) and a serial form of its rotation sort, with the contract and codes of an item of
+ * nx_bzip2_encode_batch (NX_ERR_BZIP2_LEVEL for a level outside 1..9).  NOT a product path: it is the CPU check
+ * of the format logic and the GPU tests' second opinion.
+ */
+int32_t nx_bzip2_encode_host(const uint8_t* in, size_t n, int32_t level, uint8_t* out, size_t out_cap, size_t* out_len);
 
 /* Replaces Inflater.inflate(...) as JdkZlibDecoder.decode calls it (JdkZlibDecoder.java:254-296) for n
  * independent raw deflate (RFC 1951) streams, each resumable at symbol granularity: a call takes

@@ -131,6 +131,11 @@
 /* This library's own: the block's randomised bit is set (the reference decodes such blocks; no encoder has
  * written one since bzip2 0.9.5). */
 #define NX_ERR_BZIP2_RANDOMISED           (-124)
+/* Bzip2 stream encoding (nx_bzip2_encode_batch, nx_bzip2_encode_host). */
+/* Bzip2Encoder.java:98-101  "blockSizeMultiplier: %d (expected: 1-9)" (an IllegalArgumentException) */
+#define NX_ERR_BZIP2_LEVEL                (-125)
+/* This library's own: the stream does not fit the output slot. */
+#define NX_ERR_BZIP2_ENCODE_FULL          (-126)
 
 /* Device frame scan (nx_snappy_frame_scan_batch), one code per SnappyFrameDecoder throw site: */
 /* :116-118  "Unexpected length of stream identifier: %d" */

@@ -62,6 +62,11 @@ _SIGS = {
     "nx_bzip2_decoder_reserve": (i32, [u32, vp]),
     "nx_bzip2_decode_chains": (u32, []),
     "nx_bzip2_decode_host": (i32, [C.c_char_p, sz, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
+    "nx_bzip2_encode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, u32, i32, vp]),
+    "nx_bzip2_encoder_reserve": (i32, [u32, i32, vp]),
+    "nx_bzip2_encoder_slot_bytes": (C.c_uint64, [i32]),
+    "nx_bzip2_max_compressed_length": (sz, [sz, i32]),
+    "nx_bzip2_encode_host": (i32, [C.c_char_p, sz, i32, vp, sz, C.POINTER(sz)]),
     "nx_bzip2_stream_info": (i32, [C.c_char_p, sz, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]),
     "nx_inflate_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]),
     "nx_lzf_encode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, vp]),

@@ -25,7 +25,7 @@ def _chk(rc, what):
 
 
 # Shared device workspaces (include/netty_amd.h NX_WS_*; csrc/workspace.hpp)
-WS_SNAPPY_ENC, WS_LZ4_ENC, WS_FASTLZ_ENC, WS_LZF_ENC, WS_DEC_RECORDS, WS_LZ4HC_ENC, WS_DEFLATE_ENC, WS_ZSTD_ENC, WS_ZSTD_DEC, WS_BZIP2_DEC = range(10)
+WS_SNAPPY_ENC, WS_LZ4_ENC, WS_FASTLZ_ENC, WS_LZF_ENC, WS_DEC_RECORDS, WS_LZ4HC_ENC, WS_DEFLATE_ENC, WS_ZSTD_ENC, WS_ZSTD_DEC, WS_BZIP2_DEC, WS_BZIP2_ENC = range(11)
 
 
 def workspace_info(kind: int) -> tuple[int, int]:
@@ -343,6 +343,50 @@ def bzip2_stream_info(data: bytes):
     if st != 0:
         return st, 0, 0, False
     return 0, lv.value, crc.value, bool(em.value)
+
+
+def bzip2_max_compressed_length(n: int, level: int = 9) -> int:
+    """nx_bzip2_max_compressed_length: a derived upper bound of the stream of an n-byte item at `level` (0 for
+    a level outside 1..9)."""
+    return _lib.load().nx_bzip2_max_compressed_length(int(n), int(level))
+
+
+def bzip2_encode(inp, in_off, in_len, out, out_off, out_cap, level: int = 9):
+    """One bzip2 stream per item (nx_bzip2_encode_batch): item i = inp[in_off[i] : + in_len[i]] becomes what
+    Bzip2Encoder writes for one encode(in) and close() at block size level x 100 000, in
+    out[out_off[i] : + out_cap[i]] (slots may start at any byte; nothing is written outside them).  Returns
+    (out_len, status): the stream's size and 0 or NX_ERR_BZIP2_ENCODE_FULL (-126) per item.  A level outside
+    1..9 raises (NX_ERR_BZIP2_LEVEL, -125)."""
+    n = in_len.numel()
+    dev = inp.device
+    out_len = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    _chk(_lib.load().nx_bzip2_encode_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_cap),
+                                           _ptr(out_len), _ptr(status), n, int(level), _stream()), "nx_bzip2_encode_batch")
+    return out_len, status
+
+
+def bzip2_encoder_reserve(max_streams: int, level: int = 9):
+    """nx_bzip2_encoder_reserve: size the encoder's workspace for max_streams streams in flight at `level` now
+    and cap it there until workspaces_trim()."""
+    _chk(_lib.load().nx_bzip2_encoder_reserve(int(max_streams), int(level), _stream()), "nx_bzip2_encoder_reserve")
+
+
+def bzip2_encoder_slot_bytes(level: int = 9) -> int:
+    """nx_bzip2_encoder_slot_bytes: the workspace bytes of one stream in flight at `level`."""
+    return _lib.load().nx_bzip2_encoder_slot_bytes(int(level))
+
+
+def bzip2_encode_host(data: bytes, level: int = 9, out_cap=None):
+    """nx_bzip2_encode_host on host bytes: (status, stream) of one item, by the kernel's format functions on the
+    CPU (the tests' second opinion, not a product path); out_cap defaults to bzip2_max_compressed_length."""
+    import ctypes as C
+    data = bytes(data)
+    cap = bzip2_max_compressed_length(len(data), level) if out_cap is None else int(out_cap)
+    buf = C.create_string_buffer(max(cap, 1))
+    ol = C.c_size_t(0)
+    st = _lib.load().nx_bzip2_encode_host(data, len(data), int(level), C.cast(buf, C.c_void_p), cap, C.byref(ol))
+    return st, buf.raw[:ol.value]
 
 
 INFLATE_STATE_BYTES = 512

@@ -39,6 +39,8 @@ extern "C" const char* nx_status_string(int32_t s) {
         case NX_ERR_BZIP2_TRUNCATED: return "the input ends inside the bzip2 stream";
         case NX_ERR_BZIP2_OUTPUT_FULL: return "the decoded bytes do not fit the output";
         case NX_ERR_BZIP2_RANDOMISED: return "randomised bzip2 blocks are not supported";
+        case NX_ERR_BZIP2_LEVEL: return "blockSizeMultiplier (expected: 1-9)";
+        case NX_ERR_BZIP2_ENCODE_FULL: return "the bzip2 stream does not fit the output slot";
         case NX_ERR_LZ4_ENCODE_FINISHED: return "encode finished and not enough space to write remaining data";
         case NX_ERR_SNAPPY_PREAMBLE_TOO_LONG: return "Preamble is greater than 4 bytes";
         case NX_ERR_SNAPPY_OFFSET_ZERO: return "Offset is less than minimum permissible value";

@@ -20,7 +20,7 @@
 
 namespace nx {
 
-enum class WsKind : int { SnappyEnc = 0, Lz4Enc, FastLzEnc, LzfEnc, DecRecords, Lz4HcEnc, DeflateEnc, ZstdEnc, ZstdDec, Bzip2Dec, Count };
+enum class WsKind : int { SnappyEnc = 0, Lz4Enc, FastLzEnc, LzfEnc, DecRecords, Lz4HcEnc, DeflateEnc, ZstdEnc, ZstdDec, Bzip2Dec, Bzip2Enc, Count };
 
 // Table geometry per encoder kind (entry bytes, log2 entries per table, waves per CU of its launch);
 // each codec static_asserts its own constants against this.
@@ -41,6 +41,10 @@ struct WsSpec {
 // Bzip2Dec: no tables: one slot per stream in flight holds a block's BWT bytes, merged pointers and pre-RLE
 // bytes (6 x 900 000 bytes and padding; bzip2_decode.hip), leased by part, one slot per wave of the launch on
 // at most kBzip2DecWavesPerCu waves per CU.
+// Bzip2Enc: no tables: counted in units of one level's worth (a 100 000-byte block's bytes, transformed bytes, two
+// index and two rank arrays of the rotation sort, MTF symbols and staged output; bzip2_encode.hip); a stream at
+// level L takes L consecutive units, leased by part, one stream per workgroup of the launch on at most
+// kBzip2EncGroupsPerCu workgroups per CU.
 #ifndef NX_LZ4_WPCU  // build options for A/B runs of the alt encoders' occupancy (scripts/build_lib_variant.sh; LZ4 at 20: level)
 #define NX_LZ4_WPCU 16
 #endif
@@ -50,7 +54,7 @@ struct WsSpec {
 #ifndef NX_LZF_WPCU  // LZF: 16 waves per CU measured level with 8 (profiles/r06/s4), so the smaller workspace stays
 #define NX_LZF_WPCU 8
 #endif
-constexpr WsSpec kWsSpec[] = {{8, 14, 20}, {8, 13, NX_LZ4_WPCU}, {8, 13, NX_FLZ_WPCU}, {8, 14, NX_LZF_WPCU}, {0, 0, 0}, {8, 15, 2}, {8, 14, 16}, {8, 16, 16}, {0, 0, 0}, {0, 0, 0}};
+constexpr WsSpec kWsSpec[] = {{8, 14, 20}, {8, 13, NX_LZ4_WPCU}, {8, 13, NX_FLZ_WPCU}, {8, 14, NX_LZF_WPCU}, {0, 0, 0}, {8, 15, 2}, {8, 14, 16}, {8, 16, 16}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
 static_assert(sizeof(kWsSpec) / sizeof(kWsSpec[0]) == (size_t)WsKind::Count, "one spec per kind");
 constexpr size_t kDecSlotBytes = 16384u * 4u + 8u;  // records of one frame + its count and length
 #ifndef NX_DEC_MAX_FRAMES  // build option for A/B runs (scripts/build_lib_variant.sh)
@@ -63,9 +67,14 @@ constexpr size_t kBzip2DecSlotBytes = 6u * 900000u + 256u;  // a 900 000-byte bl
 // k_bzip2_decode keeps about 27 KiB of LDS per wave (tables, selectors, tiles): five waves fit a CU's 160 KiB;
 // four leave one wave per SIMD and 5.2 GiB of slots on 256 CUs
 constexpr unsigned kBzip2DecWavesPerCu = 4;
+// 24 bytes per block byte and padding: a slot is 2 404 096 bytes at level 1 and 21 636 864 at level 9
+constexpr size_t kBzip2EncUnitBytes = 24u * 100000u + 4096u;
+// k_bzip2_encode is one workgroup of 1 024 lanes with about 69 KiB of LDS: one per CU, 256 slots, 5.5 GB at level 9
+// (615 MB at level 1) on 256 CUs
+constexpr unsigned kBzip2EncGroupsPerCu = 1;
 // bytes per slot of a kind without tables (0 for the table kinds)
 constexpr size_t ws_plain_slot_bytes(WsKind k) {
-    return k == WsKind::DecRecords ? kDecSlotBytes : k == WsKind::ZstdDec ? kZstdDecSlotBytes : k == WsKind::Bzip2Dec ? kBzip2DecSlotBytes : 0;
+    return k == WsKind::DecRecords ? kDecSlotBytes : k == WsKind::ZstdDec ? kZstdDecSlotBytes : k == WsKind::Bzip2Dec ? kBzip2DecSlotBytes : k == WsKind::Bzip2Enc ? kBzip2EncUnitBytes : 0;
 }
 
 struct WsUse {  // an in-flight part lease: slots [a, b), done when ev completes
