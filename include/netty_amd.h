@@ -428,6 +428,60 @@ size_t nx_bzip2_max_compressed_length(size_t n, int32_t level);
  * of the format logic and the GPU tests' second opinion.
  */
 int32_t nx_bzip2_encode_host(const uint8_t* in, size_t n, int32_t level, uint8_t* out, size_t out_cap, size_t* out_len);
+/*
+ * The same streams with a stream's blocks on several workgroups (DESIGN.md "Bzip2 encode, split").  Three
+ * kinds of launch on the one stream, none of which waits for another workgroup: a planner that finds where
+ * every item's blocks are cut (the block-filling rule of Bzip2BlockCompressor.write without the block's bytes,
+ * one wave per item) and lists the blocks as jobs; then, in rounds of as many jobs as the workspace has
+ * slots, one workgroup per job that encodes its block from bit 0 of its slot's staging, and a splice that
+ * places the round's blocks at their bit offsets in the callers' slots, every output byte stored once.
+ *   max_blocks = the most jobs the call lists (in_len is a device array, so the caller counts:
+ *                the sum of nx_bzip2_blocks_bound(in_len[i], level) always suffices).  Items whose blocks fall
+ *                beyond it get NX_ERR_BZIP2_ENCODE_BLOCKS and out_len 0; the call launches
+ *                ceil(max_blocks / slots) rounds, so a generous value costs empty launches only.
+ *   seg == NULL: item i is a whole stream and out / out_len / status are byte for byte those of
+ *                nx_bzip2_encode_batch.
+ *   seg != NULL: a device array of n entries, read and written.  Item i is a run of whole blocks of a stream
+ *                that the caller writes in several calls.  NX_BZIP2_SEG_FIRST: "BZh" and the level digit come
+ *                first (carry_bits, carry_count and crc are not read).  Otherwise carry_count < 32 bits
+ *                precede the first block: the low carry_count bits of carry_bits, the first in the highest;
+ *                crc is the stream CRC of the blocks before.  NX_BZIP2_SEG_LAST: the footer and the padding
+ *                follow the last block and the carry comes back empty.  Without it the item's input must end
+ *                where a block closes (the planner closes the open block at the end of the input either way),
+ *                the item emits floor(bits / 32) * 4 bytes, what Bzip2BitWriter.writeBits has handed over by
+ *                then (Bzip2BitWriter.java:41-56), and the other bits come back as the carry.  crc comes back
+ *                folded over the item's blocks ((crc << 1 | crc >>> 31) ^ blockCrc in block order).  An item
+ *                with an error status leaves its entry unspecified.
+ * Workspace: NX_WS_BZIP2_ENC, the call's plan arrays in ceil((32 n + 32 max_blocks + 64) / unit) units ahead of
+ * its slots, where a unit is nx_bzip2_encoder_slot_bytes(1); at most 1 024 jobs a round.
+ * nx_bzip2_blocks_bound: 0 for n = 0 or a level outside 1..9, else (n + n / 4) / (S - 5) + 1.
+ * nx_bzip2_plan_batch is the planner's launch alone: counts[i] = the blocks of item i (a device array).
+ */
+typedef struct {
+    uint32_t flags, carry_bits, carry_count, crc;
+} nx_bzip2_seg;
+#define NX_BZIP2_SEG_FIRST 1u /* write "BZh" and the level digit */
+#define NX_BZIP2_SEG_LAST 2u  /* flush the open block, write the footer and the padding */
+size_t nx_bzip2_blocks_bound(size_t n, int32_t level);
+int32_t nx_bzip2_encode_batch_split(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                                    const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len, int32_t* status,
+                                    uint32_t n, int32_t level, uint32_t max_blocks, nx_bzip2_seg* seg, void* stream);
+int32_t nx_bzip2_plan_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t* counts, uint32_t n,
+                            int32_t level, void* stream);
+/*
+ * The host forms of the split path, by the same functions (csrc/bzip2_encode_core.hpp).  NOT product paths:
+ * the CPU check and the GPU tests' second opinion, like nx_bzip2_encode_host.
+ * nx_bzip2_plan_host: the input end of every block of in[0, n) in cuts[0 .. min(*count, cap)); *count is the
+ * number of blocks whatever cap is.  nx_bzip2_plan_resume_host is the planner one write at a time: state
+ * (block length, run count, run value; zeros at a stream's start) is read and written, cuts are relative to
+ * this call's `in`, a block closes as soon as it is full, and `close` closes the open block at n.
+ * nx_bzip2_encode_segment_host: one item of nx_bzip2_encode_batch_split with a segment, on host memory.
+ */
+int32_t nx_bzip2_plan_host(const uint8_t* in, size_t n, int32_t level, uint64_t* cuts, size_t cap, size_t* count);
+int32_t nx_bzip2_plan_resume_host(const uint8_t* in, size_t n, int32_t level, uint32_t state[3], int32_t close,
+                                  uint64_t* cuts, size_t cap, size_t* count);
+int32_t nx_bzip2_encode_segment_host(const uint8_t* in, size_t n, int32_t level, nx_bzip2_seg* seg, uint8_t* out,
+                                     size_t out_cap, size_t* out_len);
 
 /* Replaces Inflater.inflate(...) as JdkZlibDecoder.decode calls it (JdkZlibDecoder.java:254-296) for n
  * independent raw deflate (RFC 1951) streams, each resumable at symbol granularity: a call takes
@@ -676,6 +730,35 @@ const char* nx_zstd_encoder_error(nx_zstd_encoder* e);
 size_t nx_zstd_max_encoded_length(size_t pending, int32_t block_size);
 int64_t nx_zstd_encoder_encode(nx_zstd_encoder* e, const uint8_t* in, size_t n, uint8_t* out, size_t out_cap);
 int64_t nx_zstd_encoder_flush(nx_zstd_encoder* e, uint8_t* out, size_t out_cap);
+
+/*
+ * Bzip2Encoder(blockSizeMultiplier)  Bzip2Encoder.java:96-228, one stream over any number of writes.
+ * nx_bzip2_encoder_new returns NULL for a level outside 1..9 (:98-101).  The stream is a function of the
+ * concatenated input alone: however the writes slice it, the bytes of all calls together are those of
+ * nx_bzip2_encode_batch on the whole.  _encode: the first call writes "BZh" and the level digit, also for an
+ * empty write (State.INIT writes before it looks at `in`, :114-119); the planner then runs over the new bytes
+ * on the host, and when they close k >= 1 blocks (a block closes as soon as it is full, :132-143) those blocks'
+ * bytes are uploaded and encoded by ONE nx_bzip2_encode_batch_split call, k workgroups, whose whole 32-bit
+ * words are the call's output (what Bzip2BitWriter.writeBits has handed over by then); fewer than 32 bits and
+ * the stream CRC wait in the handle.  The input of the open block is kept in host memory until the block
+ * closes: at most 51 times the block size (255 equal bytes make 5 block bytes), the block size itself for input
+ * without long runs.  _close encodes the open block, if any, with the footer and the padding (finishEncode,
+ * :207-228); a second _close returns 0, and _encode after _close copies `in` to `out` (:107-110).  Difference
+ * from the reference: _close on a handle that was never written to writes the header as well, so that the
+ * stream is the 14 bytes of an empty bzip2 stream (the Java writes the 10 footer bytes alone).
+ * _max_encoded_length(e, n): the out_cap that always suffices for the next _encode of n bytes (n = 0: _close).
+ * _launches: the nx_bzip2_encode_batch_split calls made so far.  Errors are negative NX_ERR_* codes
+ * (_error has the text), after which the handle is to be freed.
+ */
+typedef struct nx_bzip2_encoder nx_bzip2_encoder;
+nx_bzip2_encoder* nx_bzip2_encoder_new(int32_t level);
+void nx_bzip2_encoder_free(nx_bzip2_encoder* e);
+const char* nx_bzip2_encoder_error(nx_bzip2_encoder* e);
+size_t nx_bzip2_encoder_max_encoded_length(const nx_bzip2_encoder* e, size_t n);
+int64_t nx_bzip2_encoder_encode(nx_bzip2_encoder* e, const uint8_t* in, size_t n, uint8_t* out, size_t out_cap);
+int64_t nx_bzip2_encoder_close(nx_bzip2_encoder* e, uint8_t* out, size_t out_cap);
+int32_t nx_bzip2_encoder_is_closed(const nx_bzip2_encoder* e);
+uint64_t nx_bzip2_encoder_launches(const nx_bzip2_encoder* e);
 
 /* ZstdDecoder(maximumAllocationSize)  ZstdDecoder.java:59-122.  NULL for a negative size
  * (checkPositiveOrZero, :64).  _decode as nx_lzf_decoder_decode: in[0..n) is the cumulation, *consumed the

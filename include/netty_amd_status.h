@@ -136,6 +136,8 @@
 #define NX_ERR_BZIP2_LEVEL                (-125)
 /* This library's own: the stream does not fit the output slot. */
 #define NX_ERR_BZIP2_ENCODE_FULL          (-126)
+/* This library's own (nx_bzip2_encode_batch_split): the item's blocks fall beyond the call's max_blocks. */
+#define NX_ERR_BZIP2_ENCODE_BLOCKS        (-127)
 
 /* Device frame scan (nx_snappy_frame_scan_batch), one code per SnappyFrameDecoder throw site: */
 /* :116-118  "Unexpected length of stream identifier: %d" */

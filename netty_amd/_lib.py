@@ -68,6 +68,20 @@ _SIGS = {
     "nx_bzip2_max_compressed_length": (sz, [sz, i32]),
     "nx_bzip2_encode_host": (i32, [C.c_char_p, sz, i32, vp, sz, C.POINTER(sz)]),
     "nx_bzip2_stream_info": (i32, [C.c_char_p, sz, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]),
+    "nx_bzip2_blocks_bound": (sz, [sz, i32]),
+    "nx_bzip2_encode_batch_split": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, u32, i32, u32, vp, vp]),
+    "nx_bzip2_plan_batch": (i32, [vp, vp, vp, vp, u32, i32, vp]),
+    "nx_bzip2_plan_host": (i32, [C.c_char_p, sz, i32, C.POINTER(u64), sz, C.POINTER(sz)]),
+    "nx_bzip2_plan_resume_host": (i32, [C.c_char_p, sz, i32, C.POINTER(u32), i32, C.POINTER(u64), sz, C.POINTER(sz)]),
+    "nx_bzip2_encode_segment_host": (i32, [C.c_char_p, sz, i32, C.POINTER(u32), vp, sz, C.POINTER(sz)]),
+    "nx_bzip2_encoder_new": (vp, [i32]),
+    "nx_bzip2_encoder_free": (None, [vp]),
+    "nx_bzip2_encoder_error": (C.c_char_p, [vp]),
+    "nx_bzip2_encoder_max_encoded_length": (sz, [vp, sz]),
+    "nx_bzip2_encoder_encode": (i64, [vp, C.c_char_p, sz, vp, sz]),
+    "nx_bzip2_encoder_close": (i64, [vp, vp, sz]),
+    "nx_bzip2_encoder_is_closed": (i32, [vp]),
+    "nx_bzip2_encoder_launches": (u64, [vp]),
     "nx_inflate_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]),
     "nx_lzf_encode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, vp]),
     "nx_lzf_decode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, vp]),

@@ -351,19 +351,84 @@ def bzip2_max_compressed_length(n: int, level: int = 9) -> int:
     return _lib.load().nx_bzip2_max_compressed_length(int(n), int(level))
 
 
-def bzip2_encode(inp, in_off, in_len, out, out_off, out_cap, level: int = 9):
+BZIP2_SEG_FIRST, BZIP2_SEG_LAST = 1, 2
+
+
+def bzip2_encode(inp, in_off, in_len, out, out_off, out_cap, level: int = 9, split: bool = False, max_blocks=None, seg=None):
     """One bzip2 stream per item (nx_bzip2_encode_batch): item i = inp[in_off[i] : + in_len[i]] becomes what
     Bzip2Encoder writes for one encode(in) and close() at block size level x 100 000, in
     out[out_off[i] : + out_cap[i]] (slots may start at any byte; nothing is written outside them).  Returns
     (out_len, status): the stream's size and 0 or NX_ERR_BZIP2_ENCODE_FULL (-126) per item.  A level outside
-    1..9 raises (NX_ERR_BZIP2_LEVEL, -125)."""
+    1..9 raises (NX_ERR_BZIP2_LEVEL, -125).
+    split=True takes nx_bzip2_encode_batch_split: the same bytes, a stream's blocks on several workgroups.
+    max_blocks is the most blocks the call lists (default: the sum of bzip2_blocks_bound over in_len, which
+    reads in_len back); items beyond it get NX_ERR_BZIP2_ENCODE_BLOCKS (-127).  seg, split only: an int32 or
+    uint32 device tensor of n x 4 (flags, carry_bits, carry_count, crc), read and written: the items are
+    segments of streams (include/netty_amd.h)."""
     n = in_len.numel()
     dev = inp.device
     out_len = torch.empty(n, dtype=torch.int32, device=dev)
     status = torch.empty(n, dtype=torch.int32, device=dev)
-    _chk(_lib.load().nx_bzip2_encode_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_cap),
-                                           _ptr(out_len), _ptr(status), n, int(level), _stream()), "nx_bzip2_encode_batch")
+    if not split:
+        if max_blocks is not None or seg is not None:
+            raise ValueError("max_blocks and seg belong to split=True")
+        _chk(_lib.load().nx_bzip2_encode_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_cap),
+                                               _ptr(out_len), _ptr(status), n, int(level), _stream()), "nx_bzip2_encode_batch")
+        return out_len, status
+    if max_blocks is None:
+        max_blocks = sum(bzip2_blocks_bound(v, level) for v in in_len.cpu().tolist()) if 1 <= level <= 9 else 0
+    if seg is not None and (seg.numel() != 4 * n or seg.element_size() != 4 or not seg.is_contiguous()):
+        raise ValueError("seg: n x 4 32-bit values")
+    _chk(_lib.load().nx_bzip2_encode_batch_split(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_cap),
+                                                 _ptr(out_len), _ptr(status), n, int(level), int(max_blocks), _ptr(seg), _stream()),
+         "nx_bzip2_encode_batch_split")
     return out_len, status
+
+
+def bzip2_blocks_bound(n: int, level: int = 9) -> int:
+    """nx_bzip2_blocks_bound: the blocks of an n-byte item at `level`, at most (0 for n = 0)."""
+    return _lib.load().nx_bzip2_blocks_bound(int(n), int(level))
+
+
+def bzip2_plan(inp, in_off, in_len, level: int = 9):
+    """nx_bzip2_plan_batch: the planner's launch alone; returns the int32 tensor of every item's block count."""
+    n = in_len.numel()
+    counts = torch.empty(n, dtype=torch.int32, device=inp.device)
+    _chk(_lib.load().nx_bzip2_plan_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(counts), n, int(level), _stream()),
+         "nx_bzip2_plan_batch")
+    return counts
+
+
+def bzip2_plan_host(data: bytes, level: int = 9, state=None, close: bool = True):
+    """nx_bzip2_plan_host on host bytes: (status, cuts), the input end of every block of `data`.  With `state`
+    (a list of three ints, updated in place; [0, 0, 0] at a stream's start) it is nx_bzip2_plan_resume_host: the
+    planner continues from that state, and close=False leaves the open block open."""
+    import ctypes as C
+    data = bytes(data)
+    L = _lib.load()
+    cap = L.nx_bzip2_blocks_bound(len(data), int(level)) + 2
+    cuts = (C.c_uint64 * cap)()
+    cnt = C.c_size_t(0)
+    if state is None:
+        st = L.nx_bzip2_plan_host(data, len(data), int(level), cuts, cap, C.byref(cnt))
+    else:
+        s = (C.c_uint32 * 3)(*state)
+        st = L.nx_bzip2_plan_resume_host(data, len(data), int(level), s, int(bool(close)), cuts, cap, C.byref(cnt))
+        state[:] = list(s)
+    return st, list(cuts[:min(cnt.value, cap)])
+
+
+def bzip2_encode_segment_host(data: bytes, level: int, seg, out_cap=None):
+    """nx_bzip2_encode_segment_host on host bytes: `data` is whole blocks of a stream, seg = (flags, carry_bits,
+    carry_count, crc).  Returns (status, bytes, seg after)."""
+    import ctypes as C
+    data = bytes(data)
+    cap = bzip2_max_compressed_length(len(data), level) + 8 if out_cap is None else int(out_cap)
+    buf = C.create_string_buffer(max(cap, 1))
+    ol = C.c_size_t(0)
+    s = (C.c_uint32 * 4)(*seg)
+    st = _lib.load().nx_bzip2_encode_segment_host(data, len(data), int(level), s, C.cast(buf, C.c_void_p), cap, C.byref(ol))
+    return st, buf.raw[:ol.value], tuple(s)
 
 
 def bzip2_encoder_reserve(max_streams: int, level: int = 9):

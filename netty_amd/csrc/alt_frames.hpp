@@ -344,6 +344,20 @@ struct nx_zstd_encoder {
     std::vector<uint8_t> buf;           // the block buffer (:49,136-143), grown on demand
 };
 
+// Bzip2Encoder (handlers.cpp): the planner's state and the raw bytes of the open block on the host, the bits
+// that do not fill a 32-bit word and the stream CRC between launches.
+struct nx_bzip2_encoder {
+    nx::h::Gpu g;
+    int32_t level = 9;
+    bool started = false;        // the stream header is out (State.INIT left, Bzip2Encoder.java:114-119)
+    bool finished = false;
+    uint32_t plan[3] = {0, 0, 0};  // nx_bzip2_plan_resume_host's state of the open block
+    std::vector<uint8_t> open;     // the open block's input: at most 51 x the block size (255 bytes make 5)
+    nx_bzip2_seg seg = {0, 0, 0, 0};  // carry_bits, carry_count and crc between launches
+    uint64_t launches = 0;         // nx_bzip2_encode_batch_split calls
+    std::string err;               // the last failure's message
+};
+
 struct nx_zlib_encoder {
     nx::h::Gpu g;
     int32_t wrapper = 0;        // ZlibWrapper ordinal: 0 ZLIB, 1 GZIP, 2 NONE

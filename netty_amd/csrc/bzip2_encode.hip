@@ -321,8 +321,9 @@ __device__ int32_t end_piece(EncLds& L, const uint32_t* stg, Out& O, uint64_t bi
     return NX_OK;
 }
 
-// Bzip2BlockCompressor.close for the block lane 0 has filled (L.R, blk).
-__device__ int32_t encode_block(EncLds& L, uint8_t* slot, const SlotLayout& S, uint32_t level, Out& O, uint32_t* crc_out) {
+// Bzip2BlockCompressor.close for the block lane 0 has filled (L.R, blk), up to its bits in the staging words
+// (behind the header or the carried bits that begin_piece finds in the mail); returns the staged bits.
+__device__ uint64_t stage_block(EncLds& L, uint8_t* slot, const SlotLayout& S, uint32_t level, uint32_t* crc_out) {
     const uint32_t tid = threadIdx.x;
     uint8_t* blk = slot + S.blk();
     uint8_t* bwt = slot + S.bwt();
@@ -335,7 +336,7 @@ __device__ int32_t encode_block(EncLds& L, uint8_t* slot, const SlotLayout& S, u
                                       reinterpret_cast<uint32_t*>(slot + S.ra()), reinterpret_cast<uint32_t*>(slot + S.rb()), n);
 #ifdef NX_BZIP2_ENC_SORT_ONLY  // build option (scripts/build_lib_variant.sh): stop after the sort, to time it alone
     *crc_out = crc + start;
-    return NX_OK;
+    return 0;
 #endif
     // 3: move-to-front and the run symbols
     if (tid == 0u) mtf2_init(L.M, L.R.present);
@@ -382,8 +383,14 @@ __device__ int32_t encode_block(EncLds& L, uint8_t* slot, const SlotLayout& S, u
         bw_flush(e);
     }
     *crc_out = crc;
-    const uint64_t bits = ((uint64_t)L.mail[13] << 32) | L.mail[12];
-    return end_piece(L, stg, O, bits, false);
+    return ((uint64_t)L.mail[13] << 32) | L.mail[12];
+}
+__device__ int32_t encode_block(EncLds& L, uint8_t* slot, const SlotLayout& S, uint32_t level, Out& O, uint32_t* crc_out) {
+    const uint64_t bits = stage_block(L, slot, S, level, crc_out);
+#ifdef NX_BZIP2_ENC_SORT_ONLY
+    return NX_OK;
+#endif
+    return end_piece(L, reinterpret_cast<const uint32_t*>(slot + S.stg()), O, bits, false);
 }
 
 __device__ void encode_stream(EncLds& L, const uint8_t* in, uint32_t len, uint8_t* slot, const SlotLayout& S, uint32_t level, Out& O,
@@ -461,8 +468,369 @@ __global__ void __launch_bounds__(kThreads) k_bzip2_encode(const uint8_t* __rest
     }
 }
 
+// ------------------------------------------------------------------ the split path (nx_bzip2_encode_batch_split)
+// A stream's blocks are independent once their cut points are known, apart from the bit offset where each one
+// lands.  k_bzip2_plan finds the cuts (twice: once to count every item's blocks, and after k_bzip2_plan_scan has
+// turned the counts into each item's first job, once more to write the job list); k_bzip2_encode_blocks encodes
+// a round of jobs, one workgroup and one workspace slot each, from bit 0 of the slot's staging;
+// k_bzip2_splice gathers the round's staged bits into the callers' slots and carries each stream's bit position,
+// sub-word carry, CRC and status to the next round in ItemSt.  The launches are ordered by the one stream; no
+// workgroup waits for another, and every loop is bounded by an item's length, a round's jobs or the item count.
+struct ItemSt {  // per item, in the call's plan arrays
+    uint32_t cnt, first;  // its blocks, and the job index of the first (saturated)
+    uint32_t pos;         // bytes of its output slot written so far
+    uint32_t carry, carry_n;  // the bits, fewer than 32, that follow them
+    uint32_t crc;             // the stream CRC over the blocks spliced so far
+    int32_t status;
+    uint32_t flags;  // NX_BZIP2_SEG_*
+};
+struct Job {
+    uint32_t item, begin, end;  // the block's input range in its item
+    uint32_t bits, crc;         // of the encoded block
+    int32_t status;
+    uint32_t pad[2];
+};
+static_assert(sizeof(ItemSt) == 32 && sizeof(Job) == 32, "the plan arrays' layout");
+constexpr uint32_t kMaxRound = 1024;  // jobs per round, at most: k_bzip2_splice's list of parts is in LDS
+constexpr uint32_t kPlanStep = 64;    // bytes the planner's wave takes at a time
+// A step of kPlanStep bytes grows the block by at most 5 (the pending run) + 5 for every 4 bytes: while the
+// block stays this far below its limit no byte of the step can fill it.
+constexpr uint32_t kPlanMargin = 5u + 5u * (kPlanStep / 4u) + 11u;
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+    for (uint32_t d = 32; d > 0u; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+// One wave per item.  The state (plan_byte's) is uniform.  Far from the block's limit a step is counted
+// wave-wide: a lane that starts a run adds the bytes of the run that ended before it (5 for every 255 of its
+// length and plan_run_bytes of the rest, the pending run included when it reaches back before the step), and
+// the step's last run stays pending modulo 255.  Near the limit the step's bytes go through plan_byte one at a
+// time, every lane alike, and a full block is closed where the reference closes it.
+template <bool kWrite>
+__global__ void __launch_bounds__(64) k_bzip2_plan(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
+                                                  const uint32_t* __restrict__ in_len, ItemSt* items, Job* jobs, uint32_t level,
+                                                  uint32_t max_blocks) {
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    const uint8_t* p = in + in_off[i];
+    const uint32_t len = in_len[i], limit = level * kBaseBlock - 6u;
+    const uint32_t first = kWrite ? items[i].first : 0u;
+    Plan P;
+    plan_init(P);
+    uint32_t count = 0, begin = 0;
+    auto cut = [&](uint32_t end) {
+        if (kWrite && lane == 0u && (uint64_t)first + count < max_blocks) {
+            Job& J = jobs[first + count];
+            J.item = i;
+            J.begin = begin;
+            J.end = end;
+            J.bits = 0;
+            J.crc = 0;
+            J.status = NX_OK;
+        }
+        count += 1u;
+        begin = end;
+        plan_init(P);
+    };
+    for (uint32_t pos = 0; pos < len; pos += kPlanStep) {
+        const uint32_t m = len - pos < kPlanStep ? len - pos : kPlanStep;
+        const bool on = lane < m;
+        const uint32_t v = on ? p[pos + lane] : 0u;
+        if (P.len + kPlanMargin <= limit) {
+            const uint32_t prev = __shfl_up(v, 1);
+            const bool head = on && (lane == 0u ? (P.run == 0u || v != P.cur) : v != prev);
+            const uint64_t H = __ballot(head);
+            const uint64_t below = H & ((1ull << lane) - 1ull);
+            const uint32_t r = below ? lane - (63u - (uint32_t)__clzll(below)) : P.run + lane;
+            const uint32_t add = wave_sum(head ? 5u * (r / 255u) + plan_run_bytes(r % 255u) : 0u);
+            const uint32_t tail = H ? m - (63u - (uint32_t)__clzll(H)) : P.run + m;
+            P.len += add + 5u * (tail / 255u);
+            P.run = tail % 255u;
+            P.cur = __shfl(v, m - 1u);
+        } else {
+            for (uint32_t k = 0; k < m; ++k) {
+                plan_byte(P, __shfl(v, k));
+                if (plan_full(P, limit)) cut(pos + k + 1u);
+            }
+        }
+    }
+    if (!plan_empty(P)) cut(len);
+    if (!kWrite && lane == 0u) items[i].cnt = count;
+}
+
+// One workgroup: every item's first job from the counts, its state from its segment, and the jobs listed.
+__global__ void __launch_bounds__(kThreads) k_bzip2_plan_scan(ItemSt* items, uint32_t* njobs, const nx_bzip2_seg* seg, uint32_t* out_len,
+                                                              int32_t* status, uint32_t n, uint32_t max_blocks) {
+    __shared__ uint64_t wsum[kWaves];
+    __shared__ uint64_t total;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    if (tid == 0u) total = 0;
+    __syncthreads();
+    for (uint32_t base = 0; base < n; base += kThreads) {
+        const uint32_t i = base + tid;
+        const uint32_t c = i < n ? items[i].cnt : 0u;
+        uint64_t x = c;  // inclusive over the wave
+#pragma unroll
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint32_t lo = __shfl_up((uint32_t)x, d), hi = __shfl_up((uint32_t)(x >> 32), d);
+            if (lane >= d) x += ((uint64_t)hi << 32) | lo;
+        }
+        if (lane == 63u) wsum[wave] = x;
+        __syncthreads();
+        uint64_t before = total;
+        for (uint32_t w = 0; w < wave; ++w) before += wsum[w];
+        if (i < n) {
+            const uint64_t f = before + x - c;
+            ItemSt& I = items[i];
+            const bool fits = c == 0u || f + c <= max_blocks;  // an item without blocks lists none
+            const uint32_t flags = seg ? seg[i].flags : (NX_BZIP2_SEG_FIRST | NX_BZIP2_SEG_LAST);
+            const bool cont = seg && !(flags & NX_BZIP2_SEG_FIRST);
+            I.first = f < 0xffffffffull ? (uint32_t)f : 0xffffffffu;
+            I.pos = 0;
+            I.carry = cont ? seg[i].carry_bits : 0u;
+            I.carry_n = cont ? seg[i].carry_count : 0u;
+            I.crc = cont ? seg[i].crc : 0u;
+            I.flags = flags;
+            I.status = !fits ? NX_ERR_BZIP2_ENCODE_BLOCKS : I.carry_n >= 32u ? NX_ERR_INVALID_ARG : NX_OK;
+            out_len[i] = 0;
+            status[i] = I.status;
+        }
+        __syncthreads();
+        if (tid == kThreads - 1u) total = before + x;
+        __syncthreads();
+    }
+    if (tid == 0u) *njobs = total < max_blocks ? (uint32_t)total : max_blocks;
+}
+
+// One workgroup per job of the round: block `base_job + blockIdx.x` of the list, in slot blockIdx.x.
+__global__ void __launch_bounds__(kThreads) k_bzip2_encode_blocks(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
+                                                                  const ItemSt* items, Job* jobs, const uint32_t* njobs, uint8_t* ws,
+                                                                  uint32_t base_job, uint32_t level) {
+    __shared__ EncLds L;
+    const uint32_t tid = threadIdx.x, job = base_job + blockIdx.x;
+    if (job >= *njobs) return;
+    Job& J = jobs[job];
+    if (items[J.item].status != NX_OK) return;  // the item has failed: the splice passes it over
+    const SlotLayout S(level);
+    uint8_t* slot = ws + (size_t)blockIdx.x * level * kBzip2EncUnitBytes;
+    uint8_t* blk = slot + S.blk();
+    const uint8_t* src = in + in_off[J.item];
+    const uint32_t begin = J.begin, end = J.end;
+    for (uint32_t k = tid; k < 256u; k += kThreads) L.crc_table[k] = bz2d::crc_table_entry(k);
+    if (tid == 0u) {
+        L.mail[0] = L.mail[1] = L.mail[2] = 0;  // no header, nothing carried: the block starts at bit 0
+        L.mail[6] = 0;
+        rle1_init(L.R, level * kBaseBlock);
+    }
+    // 1: the job's range goes in whole and closes as one block, or the plan and the block filler disagree
+    for (uint32_t pos = begin; pos < end; pos += kTile) {
+        const uint32_t m = end - pos < kTile ? end - pos : kTile;
+        __syncthreads();
+        for (uint32_t k = tid; k < m; k += kThreads) L.tile[k] = src[pos + k];
+        __syncthreads();
+        if (tid == 0u && L.mail[6] == 0u) {
+            uint32_t used = 0;
+            while (used < m && rle1_write(L.R, blk, L.crc_table, L.tile[used])) used += 1u;
+            if (used < m) L.mail[6] = 1;
+        }
+    }
+    __syncthreads();
+    if (L.mail[6] || rle1_empty(L.R)) {
+        if (tid == 0u) J.status = NX_ERR_INTERNAL;
+        return;
+    }
+    uint32_t crc = 0;
+    const uint64_t bits = stage_block(L, slot, S, level, &crc);
+    if (tid == 0u) {
+        J.bits = (uint32_t)bits;  // below 2^32: block_bits_bound of 900 000 bytes
+        J.crc = crc;
+    }
+}
+
+// One workgroup per item: the item's blocks of this round, behind the carried bits (or the stream header) and,
+// when the stream ends here, before the footer, gathered into the item's output slot.  Lane 0 lists the parts
+// and their destination bits in LDS; every lane then makes whole destination bytes from one or two parts
+// (splice_source) and stores each once.  Staged words are read with agent-scope loads, as end_piece reads them.
+__global__ void __launch_bounds__(kThreads) k_bzip2_splice(ItemSt* items, const Job* jobs, const uint32_t* njobs, const uint8_t* ws, uint8_t* out,
+                                                           const uint64_t* __restrict__ out_off, const uint32_t* __restrict__ out_cap,
+                                                           uint32_t* out_len, int32_t* status, nx_bzip2_seg* seg, uint32_t level,
+                                                           uint32_t base_job, uint32_t round_jobs) {
+    constexpr uint16_t kHead = 0xfffe, kFoot = 0xffff;
+    __shared__ uint64_t start[kMaxRound + 3];
+    __shared__ uint16_t kind[kMaxRound + 2];
+    __shared__ uint32_t head_bytes[2], foot_bytes[3];  // the bytes in order, as the staging words hold them
+    __shared__ uint32_t sh_parts, sh_bytes, sh_crc;
+    __shared__ int32_t sh_status;
+    const uint32_t i = blockIdx.x, tid = threadIdx.x;
+    ItemSt& I = items[i];
+    const uint64_t first = I.first, cnt = I.cnt, lo = base_job, hi = (uint64_t)base_job + round_jobs;
+    const uint64_t listed = *njobs;
+    const bool starts = cnt ? (first >= lo && first < hi) : base_job == 0u;
+    const bool finishes = cnt ? (first + cnt - 1u >= lo && first + cnt - 1u < hi) : base_job == 0u;
+    const uint64_t j0 = first > lo ? first : lo, j1e = first + cnt < hi ? first + cnt : hi, j1 = j1e < listed ? j1e : listed;
+    if (!starts && !finishes && j1 <= j0) return;
+    if (I.status != NX_OK) return;  // reported when it failed
+    const uint32_t pos = I.pos, flags = I.flags;
+    const bool fin = finishes && (flags & NX_BZIP2_SEG_LAST);
+    const SlotLayout S(level);
+    if (tid == 0u) {
+        const bool header = starts && (flags & NX_BZIP2_SEG_FIRST);
+        const uint32_t hn = header ? 32u : I.carry_n, hv = header ? (0x425a6800u | ('0' + level)) : I.carry;
+        uint32_t k = 0, crc = I.crc;
+        uint64_t bit = 0;
+        int32_t st = NX_OK;
+        if (hn) {
+            head_bytes[0] = __builtin_bswap32(hv << (32u - hn));
+            head_bytes[1] = 0;
+            kind[k] = kHead;
+            start[k++] = 0;
+            bit = hn;
+        }
+        for (uint64_t j = j0; j < j1; ++j) {  // at most round_jobs <= kMaxRound
+            const Job& J = jobs[j];
+            if (J.status != NX_OK && st == NX_OK) st = J.status;
+            kind[k] = (uint16_t)(j - lo);
+            start[k++] = bit;
+            bit += J.bits;
+            crc = bz2d::crc_combine_stream(crc, J.crc);
+        }
+        if (fin) {  // Bzip2Encoder.java:220-223
+            foot_bytes[0] = __builtin_bswap32((bz2d::kEndMagicHi << 8) | (bz2d::kEndMagicLo >> 16));
+            foot_bytes[1] = __builtin_bswap32((bz2d::kEndMagicLo << 16) | (crc >> 16));
+            foot_bytes[2] = __builtin_bswap32(crc << 16);
+            kind[k] = kFoot;
+            start[k++] = bit;
+            bit += 80u;
+        }
+        start[k] = bit;
+        const uint64_t bytes = fin ? (bit + 7u) / 8u : bit / 32u * 4u;
+        if (st == NX_OK && bytes > out_cap[i] - pos) st = NX_ERR_BZIP2_ENCODE_FULL;
+        sh_parts = k;
+        sh_bytes = st == NX_OK ? (uint32_t)bytes : 0u;
+        sh_crc = crc;
+        sh_status = st;
+    }
+    __syncthreads();
+    const uint32_t parts = sh_parts, bytes = sh_bytes;
+    if (sh_status != NX_OK) {
+        if (tid == 0u) {
+            I.status = sh_status;
+            out_len[i] = 0;
+            status[i] = sh_status;
+        }
+        return;
+    }
+    auto part_byte = [&](uint32_t part, uint64_t b) -> uint32_t {
+        const uint16_t kd = kind[part];
+        if (kd == kHead) return b < 8u ? (head_bytes[b >> 2] >> (8u * (b & 3u))) & 0xffu : 0u;
+        if (kd == kFoot) return b < 12u ? (foot_bytes[b >> 2] >> (8u * (b & 3u))) & 0xffu : 0u;
+        const uint32_t* stg = reinterpret_cast<const uint32_t*>(ws + (size_t)kd * level * kBzip2EncUnitBytes + S.stg());
+        return (load_l2(stg + (b >> 2)) >> (8u * (b & 3u))) & 0xffu;
+    };
+    auto gather = [&](uint64_t byte) -> uint32_t {
+        if (parts == 0u) return 0u;
+        const SpliceSrc s = splice_source(start, parts, byte);
+        if (s.part >= parts) return 0u;
+        uint32_t v = splice_read8([&](uint64_t b) { return part_byte(s.part, b); }, s.off);
+        if (s.have < 8u && s.part + 1u < parts) v |= splice_read8([&](uint64_t b) { return part_byte(s.part + 1u, b); }, 0) >> s.have;
+        return v;
+    };
+    uint8_t* dst = out + out_off[i] + pos;
+    for (uint32_t b = tid; b < bytes; b += kThreads) dst[b] = (uint8_t)gather(b);
+    if (tid == 0u) {
+        const uint32_t cn = fin ? 0u : (uint32_t)(start[parts] - (uint64_t)bytes * 8u);  // below 32
+        const uint32_t w = (gather(bytes) << 24) | (gather(bytes + 1ull) << 16) | (gather(bytes + 2ull) << 8) | gather(bytes + 3ull);
+        const uint32_t carry = cn ? w >> (32u - cn) : 0u;
+        I.pos = pos + bytes;
+        I.carry = carry;
+        I.carry_n = cn;
+        I.crc = sh_crc;
+        if (finishes) {
+            out_len[i] = pos + bytes;
+            status[i] = NX_OK;
+            if (seg) {
+                seg[i].carry_bits = carry;
+                seg[i].carry_count = cn;
+                seg[i].crc = sh_crc;
+            }
+        }
+    }
+}
+
 }  // namespace bz2e
 }  // namespace nx
+
+extern "C" int32_t nx_bzip2_encode_batch_split(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                                               const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len, int32_t* status,
+                                               uint32_t n, int32_t level, uint32_t max_blocks, nx_bzip2_seg* seg, void* stream) {
+    using namespace nx::bz2e;
+    if (level < 1 || level > 9) return NX_ERR_BZIP2_LEVEL;  // Bzip2Encoder.java:98-101
+    if (n == 0) return NX_OK;
+    if (!in || !in_off || !in_len || !out || !out_off || !out_cap || !out_len || !status) return NX_ERR_INVALID_ARG;
+    NX_CLEAR_STALE_ERROR();
+    int dev = 0, cus = 256;
+    NX_HIP_CHECK(hipGetDevice(&dev));
+    NX_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    hipStream_t st = (hipStream_t)stream;
+    nx::WsLease lease(nx::WsKind::Bzip2Enc, dev, st);
+    // the plan arrays (a job count, n ItemSt, max_blocks Job) in whole units ahead of the slots
+    const size_t unit = nx::kBzip2EncUnitBytes;
+    const size_t plan_units = (64u + sizeof(ItemSt) * (size_t)n + sizeof(Job) * (size_t)max_blocks + unit - 1u) / unit;
+    const size_t want_slots = std::min<size_t>({std::max<size_t>(max_blocks, 1u), (size_t)cus * nx::kBzip2EncGroupsPerCu, kMaxRound});
+    const size_t need = plan_units + (size_t)level;
+    nx::SharedWs& W = lease.ws();
+    if (W.cap && W.cap < need) W.cap = need;  // a reserve below one slot of this level and the plan arrays
+    size_t first = 0, count = 0;
+    NX_HIP_CHECK(lease.acquire_part(plan_units + want_slots * (size_t)level, &first, &count));
+    if (count < need) return NX_ERR_INVALID_ARG;  // a workspace its owner holds below that
+    uint8_t* base = static_cast<uint8_t*>(W.p) + first * unit;
+    uint32_t* njobs = reinterpret_cast<uint32_t*>(base);
+    ItemSt* items = reinterpret_cast<ItemSt*>(base + 64u);
+    Job* jobs = reinterpret_cast<Job*>(base + 64u + sizeof(ItemSt) * (size_t)n);
+    uint8_t* ws = base + plan_units * unit;
+    const uint32_t slots = (uint32_t)std::min<size_t>((count - plan_units) / (size_t)level, kMaxRound);
+    hipLaunchKernelGGL(k_bzip2_plan<false>, dim3(n), dim3(64), 0, st, in, in_off, in_len, items, jobs, (uint32_t)level, max_blocks);
+    hipLaunchKernelGGL(k_bzip2_plan_scan, dim3(1), dim3(kThreads), 0, st, items, njobs, seg, out_len, status, n, max_blocks);
+    hipLaunchKernelGGL(k_bzip2_plan<true>, dim3(n), dim3(64), 0, st, in, in_off, in_len, items, jobs, (uint32_t)level, max_blocks);
+    NX_HIP_CHECK(hipGetLastError());
+    // rounds of at most `slots` jobs; a round's staging lives until its splice, and the launches are in stream order
+    for (uint64_t b = 0; b == 0u || b < max_blocks; b += slots) {
+        const uint32_t round = (uint32_t)std::min<uint64_t>(slots, max_blocks - b);
+        if (round)
+            hipLaunchKernelGGL(k_bzip2_encode_blocks, dim3(round), dim3(kThreads), 0, st, in, in_off, items, jobs, njobs, ws, (uint32_t)b,
+                               (uint32_t)level);
+        hipLaunchKernelGGL(k_bzip2_splice, dim3(n), dim3(kThreads), 0, st, items, jobs, njobs, ws, out, out_off, out_cap, out_len, status, seg,
+                           (uint32_t)level, (uint32_t)b, slots);
+        NX_HIP_CHECK(hipGetLastError());
+    }
+    return NX_OK;
+}
+
+// the planner alone (scripts/measure_bzip2_split.py times it): counts[i] = the blocks of item i
+extern "C" int32_t nx_bzip2_plan_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t* counts, uint32_t n,
+                                       int32_t level, void* stream) {
+    using namespace nx::bz2e;
+    if (level < 1 || level > 9) return NX_ERR_BZIP2_LEVEL;
+    if (n == 0) return NX_OK;
+    if (!in || !in_off || !in_len || !counts) return NX_ERR_INVALID_ARG;
+    NX_CLEAR_STALE_ERROR();
+    int dev = 0;
+    NX_HIP_CHECK(hipGetDevice(&dev));
+    hipStream_t st = (hipStream_t)stream;
+    nx::WsLease lease(nx::WsKind::Bzip2Enc, dev, st);
+    const size_t unit = nx::kBzip2EncUnitBytes, plan_units = (sizeof(ItemSt) * (size_t)n + unit - 1u) / unit;
+    nx::SharedWs& W = lease.ws();
+    if (W.cap && W.cap < plan_units) W.cap = plan_units;
+    size_t first = 0, count = 0;
+    NX_HIP_CHECK(lease.acquire_part(plan_units, &first, &count));
+    if (count < plan_units) return NX_ERR_INVALID_ARG;
+    ItemSt* items = reinterpret_cast<ItemSt*>(static_cast<uint8_t*>(W.p) + first * unit);
+    hipLaunchKernelGGL(k_bzip2_plan<false>, dim3(n), dim3(64), 0, st, in, in_off, in_len, items, (Job*)nullptr, (uint32_t)level, 0u);
+    NX_HIP_CHECK(hipGetLastError());
+    NX_HIP_CHECK(hipMemcpy2DAsync(counts, 4, &items[0].cnt, sizeof(ItemSt), 4, n, hipMemcpyDeviceToDevice, st));
+    return NX_OK;
+}
 
 extern "C" uint64_t nx_bzip2_encoder_slot_bytes(int32_t level) { return level < 1 || level > 9 ? 0u : (uint64_t)level * nx::kBzip2EncUnitBytes; }
 

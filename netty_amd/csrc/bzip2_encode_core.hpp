@@ -147,6 +147,88 @@ NX_HD void rle1_close(Rle1& R, uint8_t* block, const uint32_t* T) {
 }
 NX_HD bool rle1_empty(const Rle1& R) { return R.len == 0u && R.run == 0u; }  // Bzip2BlockCompressor.java:287-289
 
+// ------------------------------------------------------------------ the planner: where a stream's blocks are cut
+// The block-filling rule above without the block's bytes (Bzip2BlockCompressor.java:141-207): the state is the
+// block length, the run value and the run count, so it can be saved after any byte and resumed.  A block is
+// closed as soon as it is full (blockLength > blockLengthLimit, Bzip2Encoder.java:132-143), which is where the
+// next byte would be refused; closing flushes the pending run, and the next block starts with none.
+struct Plan {
+    uint32_t len, run, cur;
+};
+NX_HD void plan_init(Plan& P) { P.len = P.run = P.cur = 0; }
+NX_HD uint32_t plan_run_bytes(uint32_t run) { return run < 4u ? run : 5u; }  // writeRun: a run of four or more is five bytes
+NX_HD void plan_byte(Plan& P, uint32_t value) {                              // write(), for a block that is not full
+    if (P.run == 0u) {
+        P.cur = value;
+        P.run = 1;
+    } else if (P.cur != value) {
+        P.len += plan_run_bytes(P.run);
+        P.cur = value;
+        P.run = 1;
+    } else if (P.run == 254u) {
+        P.len += 5u;
+        P.run = 0;
+    } else {
+        P.run += 1u;
+    }
+}
+NX_HD bool plan_full(const Plan& P, uint32_t limit) { return P.len > limit; }
+NX_HD bool plan_empty(const Plan& P) { return P.len == 0u && P.run == 0u; }
+// in[0, n) offered to P: the input end (base + index) of every block that closes goes to cuts[*count++] while
+// *count < cap and is counted beyond; with `close` the open block, if it holds anything, is closed at base + n.
+NX_HD void plan_range(Plan& P, uint32_t limit, const uint8_t* in, uint64_t n, bool close, uint64_t base, uint64_t* cuts, uint64_t cap,
+                      uint64_t* count) {
+    for (uint64_t i = 0; i < n; ++i) {
+        plan_byte(P, in[i]);
+        if (plan_full(P, limit)) {
+            if (*count < cap) cuts[*count] = base + i + 1u;
+            *count += 1u;
+            plan_init(P);
+        }
+    }
+    if (close && !plan_empty(P)) {
+        if (*count < cap) cuts[*count] = base + n;
+        *count += 1u;
+        plan_init(P);
+    }
+}
+// The blocks of n input bytes at `level`, at most: the derivation of stream_bytes_bound.
+constexpr uint64_t blocks_bound(uint64_t n, uint32_t level) {
+    return n ? (n + n / 4u) / ((uint64_t)level * kBaseBlock - 5u) + 1u : 0u;
+}
+
+// ------------------------------------------------------------------ the splice, as a gather
+// Consecutive parts of a stream, each a run of bits from bit 0 of its own zero-padded bytes (the carried bits,
+// blocks encoded from bit 0, the footer), land one behind another.  start[k] is the destination bit of part k,
+// start[parts] the total.  A destination byte takes its first bits from the part that holds its first bit and
+// the rest from the next part: a block is at least 105 bits and the footer 80, and only the carry (below 32
+// bits, always first) can be shorter than a byte, so a byte never spans three.
+struct SpliceSrc {
+    uint32_t part;  // the part of the byte's first bit; `parts` when the byte lies past the total
+    uint64_t off;   // that bit's offset in the part
+    uint32_t have;  // the bits the part still holds from there, 8 at most: the other 8 - have come from bit 0 of part + 1
+};
+NX_HD SpliceSrc splice_source(const uint64_t* start, uint32_t parts, uint64_t byte) {
+    const uint64_t bit = byte * 8u;
+    if (bit >= start[parts]) return {parts, 0, 8};
+    uint32_t lo = 0, hi = parts - 1u;  // the last part whose start is at or before `bit`; empty parts are passed over
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi + 1u) >> 1;
+        if (start[mid] <= bit) lo = mid;
+        else hi = mid - 1u;
+    }
+    const uint64_t left = start[lo + 1u] - bit;
+    return {lo, bit - start[lo], left < 8u ? (uint32_t)left : 8u};
+}
+// eight bits from bit `off` of bytes b (zeros behind the part's last bit), given a way to read byte i
+template <class ByteAt>
+NX_HD uint32_t splice_read8(ByteAt&& at, uint64_t off) {
+    const uint64_t i = off >> 3;
+    const uint32_t sh = (uint32_t)(off & 7u);
+    const uint32_t v = (at(i) << 8) | (sh ? at(i + 1u) : 0u);
+    return (v >> (8u - sh)) & 0xffu;
+}
+
 // ------------------------------------------------------------------ second stage (Bzip2MTFAndRLE2StageEncoder.java)
 struct Mtf2 {
     uint8_t list[256];  // Bzip2MoveToFrontTable

@@ -1,7 +1,10 @@
 // bzip2_encode_host.cpp — the host entries of the bzip2 encoder: nx_bzip2_max_compressed_length and
 // nx_bzip2_encode_host, a single-threaded encode of one item (one encode(in) followed by close() of
 // Bzip2Encoder.java) from the functions of bzip2_encode_core.hpp plus a serial rotation sort.  The host encoder
-// is the CPU check of the format core and the GPU tests' second opinion; it is not a product path.
+// is the CPU check of the format core and the GPU tests' second opinion; it is not a product path.  Beside it
+// the host forms of the split path (nx_bzip2_encode_batch_split): nx_bzip2_blocks_bound, the planner
+// (nx_bzip2_plan_host, nx_bzip2_plan_resume_host) and nx_bzip2_encode_segment_host, which encodes a segment's
+// blocks one after another behind the carried bits, the way the one-shot encoder does behind the header.
 //
 // The sort is the one the kernel runs, one element at a time: prefix doubling over the cyclic rotations, each
 // round a stable least-significant-digit radix sort by the rank of the first half over a list that is already
@@ -168,12 +171,12 @@ extern "C" size_t nx_bzip2_max_compressed_length(size_t n, int32_t level) {
     return (size_t)stream_bytes_bound(n, (uint32_t)level);
 }
 
-extern "C" int32_t nx_bzip2_encode_host(const uint8_t* in, size_t n, int32_t level, uint8_t* out, size_t out_cap, size_t* out_len) {
-    if ((!in && n) || (!out && out_cap) || !out_len) return NX_ERR_INVALID_ARG;
-    *out_len = 0;
-    if (level < 1 || level > 9) return NX_ERR_BZIP2_LEVEL;  // Bzip2Encoder.java:98-101
+namespace {
+// The blocks of in[0, n) behind what O carries (the stream header, or the bits of an earlier segment), then with
+// `last` the footer and the padding; *stream_crc is folded in block order.
+int32_t host_stream(const uint8_t* in, size_t n, uint32_t level, Out& O, uint32_t* stream_crc, bool last) {
     static const CrcTable table;
-    const uint32_t S = (uint32_t)level * kBaseBlock;
+    const uint32_t S = level * kBaseBlock;
     std::unique_ptr<Work> W(new Work);
     const size_t room = n < S ? n + n / 4u + 8u : S + 8u;  // a block holds at most S bytes, and at most 5/4 of the item
     W->block.resize(room);
@@ -185,8 +188,6 @@ extern "C" int32_t nx_bzip2_encode_host(const uint8_t* in, size_t n, int32_t lev
     W->ra.resize(room);
     W->rb.resize(room);
     W->stg.resize((size_t)((block_bits_bound(room) + 40u) / 32u + 2u));
-    Out O = {out, out_cap, 0, 0, 0, true};
-    uint32_t stream_crc = 0;
     rle1_init(W->R, S);
     for (size_t i = 0; i <= n;) {  // Bzip2Encoder.java:112-148, then finishEncode's closeBlock at i == n
         if (i < n && rle1_write(W->R, W->block.data(), table.t, in[i])) {
@@ -195,21 +196,86 @@ extern "C" int32_t nx_bzip2_encode_host(const uint8_t* in, size_t n, int32_t lev
         }
         if (!rle1_empty(W->R)) {  // Bzip2Encoder.java:154-161 closeBlock
             uint32_t crc = 0;
-            const int32_t st = host_block(*W, O, table.t, (uint32_t)level, &crc);
+            const int32_t st = host_block(*W, O, table.t, level, &crc);
             if (st != NX_OK) return st;
-            stream_crc = nx::bz2d::crc_combine_stream(stream_crc, crc);
+            *stream_crc = nx::bz2d::crc_combine_stream(*stream_crc, crc);
             rle1_init(W->R, S);
         }
         if (i == n) break;
     }
+    if (!last) return NX_OK;
     BitWriter b;  // Bzip2Encoder.java:220-223
-    begin_piece(*W, O, b, 8, (uint32_t)level);
+    begin_piece(*W, O, b, 8, level);
     bw_put(b, 24, nx::bz2d::kEndMagicHi);
     bw_put(b, 24, nx::bz2d::kEndMagicLo);
-    bw_put(b, 32, stream_crc);
+    bw_put(b, 32, *stream_crc);
     bw_flush(b);
-    const int32_t st = end_piece(*W, O, bw_bits(b), true);
+    return end_piece(*W, O, bw_bits(b), true);
+}
+}  // namespace
+
+extern "C" int32_t nx_bzip2_encode_host(const uint8_t* in, size_t n, int32_t level, uint8_t* out, size_t out_cap, size_t* out_len) {
+    if ((!in && n) || (!out && out_cap) || !out_len) return NX_ERR_INVALID_ARG;
+    *out_len = 0;
+    if (level < 1 || level > 9) return NX_ERR_BZIP2_LEVEL;  // Bzip2Encoder.java:98-101
+    Out O = {out, out_cap, 0, 0, 0, true};
+    uint32_t stream_crc = 0;
+    const int32_t st = host_stream(in, n, (uint32_t)level, O, &stream_crc, true);
     if (st != NX_OK) return st;
     *out_len = O.pos;
+    return NX_OK;
+}
+
+extern "C" size_t nx_bzip2_blocks_bound(size_t n, int32_t level) {
+    if (level < 1 || level > 9) return 0;
+    return (size_t)blocks_bound(n, (uint32_t)level);
+}
+
+extern "C" int32_t nx_bzip2_plan_resume_host(const uint8_t* in, size_t n, int32_t level, uint32_t state[3], int32_t close, uint64_t* cuts,
+                                             size_t cap, size_t* count) {
+    if ((!in && n) || (!cuts && cap) || !count || !state) return NX_ERR_INVALID_ARG;
+    *count = 0;
+    if (level < 1 || level > 9) return NX_ERR_BZIP2_LEVEL;
+    Plan P = {state[0], state[1], state[2]};
+    uint64_t c = 0;
+    plan_range(P, (uint32_t)level * kBaseBlock - 6u, in, n, close != 0, 0, cuts, cap, &c);
+    state[0] = P.len;
+    state[1] = P.run;
+    state[2] = P.cur;
+    *count = (size_t)c;
+    return NX_OK;
+}
+
+extern "C" int32_t nx_bzip2_plan_host(const uint8_t* in, size_t n, int32_t level, uint64_t* cuts, size_t cap, size_t* count) {
+    uint32_t state[3] = {0, 0, 0};
+    return nx_bzip2_plan_resume_host(in, n, level, state, 1, cuts, cap, count);
+}
+
+extern "C" int32_t nx_bzip2_encode_segment_host(const uint8_t* in, size_t n, int32_t level, nx_bzip2_seg* seg, uint8_t* out, size_t out_cap,
+                                                size_t* out_len) {
+    if ((!in && n) || (!out && out_cap) || !out_len || !seg) return NX_ERR_INVALID_ARG;
+    *out_len = 0;
+    if (level < 1 || level > 9) return NX_ERR_BZIP2_LEVEL;
+    const bool first = seg->flags & NX_BZIP2_SEG_FIRST, last = seg->flags & NX_BZIP2_SEG_LAST;
+    if (!first && seg->carry_count >= 32u) return NX_ERR_INVALID_ARG;
+    // the segment goes to a buffer of its own: without LAST up to three whole bytes are held back as carry
+    std::vector<uint8_t> buf(stream_bytes_bound(n, (uint32_t)level) + 8u);
+    Out O = {buf.data(), buf.size(), 0, first ? 0u : seg->carry_bits, first ? 0u : seg->carry_count, first};
+    uint32_t crc = first ? 0u : seg->crc;
+    const int32_t st = host_stream(in, n, (uint32_t)level, O, &crc, last);
+    if (st != NX_OK) return st;
+    if (!last && O.head) {  // no block: the header is still to be written
+        buf[0] = 'B', buf[1] = 'Z', buf[2] = 'h', buf[3] = (uint8_t)('0' + level);
+        O.pos = 4;
+    }
+    const size_t emit = last ? O.pos : O.pos / 4u * 4u;  // Bzip2BitWriter.java:41-56 hands over whole 32-bit words
+    if (emit > out_cap) return NX_ERR_BZIP2_ENCODE_FULL;
+    if (emit) memcpy(out, buf.data(), emit);
+    uint32_t carry = 0;
+    for (size_t k = emit; k < O.pos; ++k) carry = (carry << 8) | buf[k];
+    seg->carry_bits = last ? 0u : (carry << O.carry_n) | O.carry;
+    seg->carry_count = last ? 0u : (uint32_t)(O.pos - emit) * 8u + O.carry_n;
+    seg->crc = crc;
+    *out_len = emit;
     return NX_OK;
 }

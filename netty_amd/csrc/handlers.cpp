@@ -1042,6 +1042,130 @@ extern "C" int64_t nx_zstd_encoder_flush(nx_zstd_encoder* e, uint8_t* out, size_
     return w;
 }
 
+// ------------------------------------------------------------------ Bzip2Encoder
+// Bzip2Encoder.java:105-228 over nx_bzip2_encode_batch_split.  The planner runs on the host over every write
+// (nx_bzip2_plan_resume_host), the open block's input stays in host memory, and a write that closes k blocks
+// uploads their bytes and makes one call with a segment that is not the stream's last: the k blocks run on k
+// workgroups, the call hands back whole 32-bit words as Bzip2BitWriter.writeBits does, and the other bits and the
+// stream CRC wait in the handle.  close() sends the open block as the last segment.
+namespace {
+constexpr uint32_t kBzip2HandleBlocks = 4;  // blocks in flight the handle holds slots for; more run in rounds
+
+// data[0, len) = `blocks` whole blocks behind the handle's carry, as one item of one launch
+int64_t bzip2_segment(nx_bzip2_encoder* e, const uint8_t* data, size_t len, uint32_t blocks, bool last, uint8_t* out, size_t out_cap) {
+    if (len > 0xffffffffull) return NX_ERR_INVALID_ARG;
+    Gpu& g = e->g;
+    const size_t cap = nx_bzip2_max_compressed_length(len, e->level) + 8u;
+    struct Par {
+        uint64_t in_off, out_off;
+        uint32_t in_len, out_cap, out_len;
+        int32_t status;
+        nx_bzip2_seg seg;
+    } p = {0, 0, (uint32_t)len, (uint32_t)cap, 0, 0, e->seg};
+    p.seg.flags = last ? NX_BZIP2_SEG_LAST : 0u;
+    if (!g.din.ensure(len ? len : 1u) || !g.dout.ensure(cap) || !g.a0.ensure(sizeof p)) return NX_ERR_HIP;
+    if (!g.h2d(g.din.p, data, len) || !g.h2d(g.a0.p, &p, sizeof p)) return NX_ERR_HIP;
+    uint8_t* P = g.a0.as<uint8_t>();
+    const int32_t r = nx_bzip2_encode_batch_split(g.din.as<uint8_t>(), (const uint64_t*)(P + offsetof(Par, in_off)),
+                                                  (const uint32_t*)(P + offsetof(Par, in_len)), g.dout.as<uint8_t>(),
+                                                  (const uint64_t*)(P + offsetof(Par, out_off)), (const uint32_t*)(P + offsetof(Par, out_cap)),
+                                                  (uint32_t*)(P + offsetof(Par, out_len)), (int32_t*)(P + offsetof(Par, status)), 1, e->level,
+                                                  blocks, (nx_bzip2_seg*)(P + offsetof(Par, seg)), g.s);
+    if (r != NX_OK) return r;
+    e->launches += 1;
+    if (!g.d2h(&p, g.a0.p, sizeof p) || !g.sync()) return NX_ERR_HIP;
+    if (p.status != NX_OK) return p.status;
+    if (p.out_len > out_cap) return NX_ERR_INVALID_ARG;
+    if (!g.d2h(out, g.dout.p, p.out_len) || !g.sync()) return NX_ERR_HIP;
+    e->seg = p.seg;
+    return (int64_t)p.out_len;
+}
+
+// "BZh" and the level digit (Bzip2Encoder.java:114-119): 32 bits, so nothing is carried behind them
+int64_t bzip2_start(nx_bzip2_encoder* e, uint8_t* out, size_t out_cap) {
+    if (e->started) return 0;
+    if (out_cap < 4u) return NX_ERR_INVALID_ARG;
+    out[0] = 'B', out[1] = 'Z', out[2] = 'h', out[3] = (uint8_t)('0' + e->level);
+    e->started = true;
+    return 4;
+}
+}  // namespace
+
+extern "C" nx_bzip2_encoder* nx_bzip2_encoder_new(int32_t level) {
+    if (level < 1 || level > 9) return nullptr;  // Bzip2Encoder.java:98-101
+    auto* e = new nx_bzip2_encoder();
+    // the plan arrays' unit and slots for kBzip2HandleBlocks blocks at this level (Gpu::hold's size is the other handles')
+    if (!e->g.ok || nx::ws_hold(nx::WsKind::Bzip2Enc, e->g.dev, 1u + kBzip2HandleBlocks * (uint32_t)level, e->g.s) != NX_OK) {
+        delete e;
+        return nullptr;
+    }
+    e->g.held |= 1u << (int)nx::WsKind::Bzip2Enc;
+    e->level = level;
+    return e;
+}
+extern "C" void nx_bzip2_encoder_free(nx_bzip2_encoder* e) { delete e; }
+extern "C" const char* nx_bzip2_encoder_error(nx_bzip2_encoder* e) { return e && !e->err.empty() ? e->err.c_str() : nullptr; }
+extern "C" int32_t nx_bzip2_encoder_is_closed(const nx_bzip2_encoder* e) { return e && e->finished ? 1 : 0; }
+extern "C" uint64_t nx_bzip2_encoder_launches(const nx_bzip2_encoder* e) { return e ? e->launches : 0; }
+extern "C" size_t nx_bzip2_encoder_max_encoded_length(const nx_bzip2_encoder* e, size_t n) {
+    if (!e) return 0;
+    if (e->finished) return n;
+    return 4u + nx_bzip2_max_compressed_length(e->open.size() + n, e->level) + 8u;
+}
+
+extern "C" int64_t nx_bzip2_encoder_encode(nx_bzip2_encoder* e, const uint8_t* in, size_t n, uint8_t* out, size_t out_cap) {
+    const nx::NoGrowScope no_grow;
+    if (!e || (!in && n) || (!out && out_cap)) return NX_ERR_INVALID_ARG;
+    if (e->finished) {  // :107-110 out.writeBytes(in)
+        if (n > out_cap) return NX_ERR_INVALID_ARG;
+        nx::copy_bytes(out, in, n);
+        return (int64_t)n;
+    }
+    const int64_t w = bzip2_start(e, out, out_cap);  // State.INIT writes before it looks at `in`
+    if (w < 0) return w;
+    if (n == 0) return w;
+    std::vector<uint64_t> cuts(nx_bzip2_blocks_bound(n, e->level) + 2u);
+    size_t count = 0;
+    const int32_t r = nx_bzip2_plan_resume_host(in, n, e->level, e->plan, 0, cuts.data(), cuts.size(), &count);
+    if (r != NX_OK) return r;
+    if (count == 0) {  // :132-138 the block is not full
+        e->open.insert(e->open.end(), in, in + n);
+        return w;
+    }
+    const size_t closed = (size_t)cuts[count - 1];  // the bytes of `in` in the blocks this write closes
+    const uint8_t* src = in;
+    size_t len = closed;
+    if (!e->open.empty()) {
+        e->open.insert(e->open.end(), in, in + closed);
+        src = e->open.data();
+        len = e->open.size();
+    }
+    const int64_t b = bzip2_segment(e, src, len, (uint32_t)count, false, out + w, out_cap - (size_t)w);
+    if (b < 0) {
+        e->err = nx_status_string((int32_t)b);
+        return b;
+    }
+    e->open.assign(in + closed, in + n);
+    return w + b;
+}
+
+extern "C" int64_t nx_bzip2_encoder_close(nx_bzip2_encoder* e, uint8_t* out, size_t out_cap) {
+    const nx::NoGrowScope no_grow;
+    if (!e || (!out && out_cap)) return NX_ERR_INVALID_ARG;
+    if (e->finished) return 0;  // finishEncode :208-211
+    const int64_t w = bzip2_start(e, out, out_cap);  // (a stream that was never written to still gets its header)
+    if (w < 0) return w;
+    const int64_t b = bzip2_segment(e, e->open.data(), e->open.size(), e->open.empty() ? 0u : 1u, true, out + w, out_cap - (size_t)w);
+    if (b < 0) {
+        e->err = nx_status_string((int32_t)b);
+        return b;
+    }
+    e->finished = true;
+    e->open.clear();
+    e->open.shrink_to_fit();
+    return w + b;
+}
+
 // ------------------------------------------------------------------ ZstdDecoder
 // ZstdDecoder.java:59-122 over nx_zstd_decode_batch_ex: the cumulation is walked on the host
 // (nx_zstd_next_frame), every complete frame of the call is an item of one launch.  Where the handle

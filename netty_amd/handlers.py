@@ -340,6 +340,51 @@ class ZstdEncoder(_Encoder):
         return self._ret(_lib.load().nx_zstd_encoder_flush(self._h, out, cap), out)
 
 
+class Bzip2Encoder(_Encoder):
+    """Bzip2Encoder.java:96-228 over the GPU bzip2 encoder's split path: one stream over any number of writes,
+    the same bytes however the writes slice the input.  The first encode() writes "BZh" and the level digit;
+    a write that closes k blocks encodes them in one launch on k workgroups and returns the 32-bit words they
+    complete (a block that is not full yet stays in host memory); finish_encode() = close(): the open block,
+    the footer and the padding, after which encode() passes its input through (:107-110) and a second
+    finish_encode() returns nothing.  finish_encode() on an encoder that was never written to returns the
+    whole 14-byte empty stream (the Java writes the footer alone)."""
+
+    _free = "nx_bzip2_encoder_free"
+    MIN_BLOCK_SIZE, MAX_BLOCK_SIZE = 1, 9  # Bzip2Constants.java
+
+    def __init__(self, block_size_multiplier: int = MAX_BLOCK_SIZE):
+        if not self.MIN_BLOCK_SIZE <= block_size_multiplier <= self.MAX_BLOCK_SIZE:  # :98-101
+            raise ValueError(f"blockSizeMultiplier: {block_size_multiplier} (expected: 1-9)")
+        self.block_size_multiplier = int(block_size_multiplier)
+        self._h = _new(_lib.load().nx_bzip2_encoder_new(self.block_size_multiplier), "Bzip2Encoder")
+
+    def _out(self, n: int):
+        cap = _lib.load().nx_bzip2_encoder_max_encoded_length(self._h, n)
+        return (C.c_uint8 * max(cap, 1))(), cap
+
+    @staticmethod
+    def _ret(r, out) -> bytes:
+        if r < 0:
+            raise CompressionException(_lib.status_string(r))
+        return bytes(out[:r])
+
+    def encode(self, data: bytes) -> bytes:
+        out, cap = self._out(len(data))
+        return self._ret(_lib.load().nx_bzip2_encoder_encode(self._h, data, len(data), out, cap), out)
+
+    def finish_encode(self) -> bytes:
+        out, cap = self._out(0)
+        return self._ret(_lib.load().nx_bzip2_encoder_close(self._h, out, cap), out)
+
+    def is_closed(self) -> bool:
+        """Bzip2Encoder.isClosed() (:166-168)"""
+        return bool(_lib.load().nx_bzip2_encoder_is_closed(self._h))
+
+    def launches(self) -> int:
+        """nx_bzip2_encoder_launches: the split-path calls made so far (one per write that closes blocks)"""
+        return _lib.load().nx_bzip2_encoder_launches(self._h)
+
+
 class ZstdDecoder(_Decoder):
     """ZstdDecoder.java:59-122 over the GPU Zstandard frame decoder (nx_zstd_decoder_*).  Every complete
     frame of a read is decoded in one launch, content checksums verified (XXH64) and skippable frames
