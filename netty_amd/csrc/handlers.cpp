@@ -7,11 +7,22 @@
 //   FastLzFrameDecoder   FastLzFrameDecoder.java:113-207
 //   LzfEncoder           LzfEncoder.java:169-246
 //   LzfDecoder           LzfDecoder.java:112-241
+//   Lz4FrameEncoder      Lz4FrameEncoder.java:231-336
+//   Lz4FrameDecoder      Lz4FrameDecoder.java:121-261
+//   ZstdEncoder          ZstdEncoder.java:105-178
+//   ZstdDecoder          ZstdDecoder.java:59-122
+//   Bzip2Encoder         Bzip2Encoder.java:105-228
+//   JdkZlibEncoder       JdkZlibEncoder.java:123-137, :214-276, :308-340
+//   JdkZlibDecoder       JdkZlibDecoder.java:117-160, :198-520 (+ ZlibDecoder.java:49,62-84)
 //
 // Headers are parsed on the host exactly as the Java decode() does (they are a few bytes per
-// chunk); the per-chunk arithmetic (Snappy/FastLZ/LZF, CRC32C, Adler32) runs on the GPU.  Results
+// chunk); the per-chunk arithmetic (the codecs and their checksums) runs on the GPU.  Results
 // are applied in stream order, so the first failing chunk truncates the message list and marks the
 // decoder corrupted just like the reference's exception path.
+//
+// The seven encoders stage a launch through nx::h::EncodeItems (handles.hpp): the codec cuts its message
+// into items and says each one's slot size, calls its kernel with the typed device arrays, and says what
+// it reads back and where each item's bytes go.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -29,27 +40,30 @@ extern "C" int32_t nx_snappy_decode_batch(const uint8_t*, const uint64_t*, const
 
 namespace {
 using nx::h::DevBuf;
+using nx::h::EncodeItems;
 using nx::h::Gpu;
 using nx::h::MsgList;
+using nx::h::for_each_piece;
 using nx::h::kStreamStart;
+using nx::h::make_handle;
 
-inline uint32_t le24(const uint8_t* p) { return p[0] | (p[1] << 8) | ((uint32_t)p[2] << 16); }
 inline uint32_t le32(const uint8_t* p) { return p[0] | (p[1] << 8) | (p[2] << 16) | ((uint32_t)p[3] << 24); }
 inline uint32_t be16(const uint8_t* p) { return ((uint32_t)p[0] << 8) | p[1]; }
-inline uint32_t be24(const uint8_t* p) { return ((uint32_t)p[0] << 16) | ((uint32_t)p[1] << 8) | p[2]; }
 inline uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
+
+// the last failure's message of an encoder handle that keeps one (nullptr: none)
+template <class E>
+const char* last_error(const E* e) {
+    return e && !e->err.empty() ? e->err.c_str() : nullptr;
+}
 
 }  // namespace
 
 // ======================================================================= Snappy frame encoder
 
 extern "C" nx_snappy_frame_encoder* nx_snappy_frame_encoder_new(int32_t jumbo) {
-    auto* e = new nx_snappy_frame_encoder();
-    if (!e->g.hold(nx::WsKind::SnappyEnc)) {
-        delete e;
-        return nullptr;
-    }
-    e->slice = jumbo ? 65535 : 32767;  // SnappyFrameEncoder.java:31,39
+    auto* e = make_handle<nx_snappy_frame_encoder>(nx::WsKind::SnappyEnc);
+    if (e) e->slice = jumbo ? 65535 : 32767;  // SnappyFrameEncoder.java:31,39
     return e;
 }
 extern "C" void nx_snappy_frame_encoder_free(nx_snappy_frame_encoder* e) { delete e; }
@@ -67,93 +81,66 @@ extern "C" int64_t nx_snappy_frame_encoder_encode(nx_snappy_frame_encoder* e, co
         memcpy(out, kStreamStart, 10);
         op = 10;
     }
-    struct Sl {
-        uint64_t off;
-        uint32_t len;
-        bool comp;
+    EncodeItems it(e->g);
+    bool last_raw = false;  // the last slice goes out uncompressed (every other one is a compressed chunk)
+    auto add = [&](uint64_t off, uint32_t len, bool raw) {
+        it.add(off, len, (nx_snappy_max_compressed_length(len) + 15) & ~15ull);
+        last_raw = raw;
     };
-    std::vector<Sl> sl;
     int64_t dl = (int64_t)n;
     if (dl > 18) {  // MIN_COMPRESSIBLE_LENGTH (:46,90-113)
         uint64_t pos = 0;
         for (;;) {
             if (dl < 18) {
-                sl.push_back({pos, (uint32_t)dl, false});
+                add(pos, (uint32_t)dl, true);
                 break;
             }
             uint32_t len = dl > e->slice ? (uint32_t)e->slice : (uint32_t)dl;
-            sl.push_back({pos, len, true});
+            add(pos, len, false);
             pos += len;
             if (dl > e->slice) dl -= e->slice; else break;
         }
     } else {
-        sl.push_back({0, (uint32_t)n, false});
+        add(0, (uint32_t)n, true);
     }
-    const uint32_t ns = (uint32_t)sl.size();
-    std::vector<uint64_t> ioff(ns), ooff(ns);
-    std::vector<uint32_t> ilen(ns);
-    uint64_t ocur = 0;
-    for (uint32_t i = 0; i < ns; ++i) {
-        ioff[i] = sl[i].off;
-        ilen[i] = sl[i].len;
-        ooff[i] = ocur;
-        ocur += nx_snappy_max_compressed_length(sl[i].len);
-        ocur = (ocur + 15) & ~15ull;
-    }
+    const uint32_t ns = it.size();
+    auto comp = [&](uint32_t i) { return !(last_raw && i == ns - 1); };
     Gpu& g = e->g;
-    if (!g.din.ensure(n) || !g.dout.ensure(ocur) || !g.a0.ensure(8ull * ns) || !g.a1.ensure(8ull * ns) ||
-        !g.a2.ensure(4ull * ns) || !g.a3.ensure(4ull * ns) || !g.a4.ensure(4ull * ns) || !g.a5.ensure(4ull * ns))
-        return NX_ERR_HIP;
-    bool ok = g.h2d(g.din.p, in, n) && g.h2d(g.a0.p, ioff.data(), 8ull * ns) && g.h2d(g.a1.p, ooff.data(), 8ull * ns) &&
-              g.h2d(g.a2.p, ilen.data(), 4ull * ns);
-    if (!ok) return NX_ERR_HIP;
+    int32_t r = it.stage(in, n, 0, 4ull * ns);
+    if (r != NX_OK) return r;
+    uint32_t* d_crc = g.aux0.as<uint32_t>();
     // masked CRC32C of every slice (calculateAndWriteChecksum :150-152, writeUnencodedChunk :119-124)
-    int32_t r = nx_crc32c_masked_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.a5.as<uint32_t>(), ns, g.s);
+    r = nx_crc32c_masked_batch(it.d_in(), it.d_in_off(), it.d_in_len(), d_crc, ns, g.s);
     if (r != NX_OK) return r;
     // Snappy.encode of every slice (uncompressed slices are encoded too but ignored: keeps one launch)
-    r = nx_snappy_encode_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.dout.as<uint8_t>(),
-                               g.a1.as<uint64_t>(), g.a3.as<uint32_t>(), g.a4.as<int32_t>(), ns, g.s);
+    r = nx_snappy_encode_batch(it.d_in(), it.d_in_off(), it.d_in_len(), it.d_out(), it.d_out_off(), it.d_out_len(), it.d_status(), ns,
+                               g.s);
     if (r != NX_OK) return r;
-    std::vector<uint32_t> clen(ns), crc(ns);
-    ok = g.d2h(clen.data(), g.a3.p, 4ull * ns) && g.d2h(crc.data(), g.a5.p, 4ull * ns) && g.sync();
-    if (!ok) return NX_ERR_HIP;
+    std::vector<uint32_t> crc(ns);
+    if (!it.fetch(false, d_crc, crc.data())) return NX_ERR_HIP;  // the lengths and the CRCs; the status is not read
+    const std::vector<uint32_t>& clen = it.len;
     // the framed layout is known once the lengths are: each compressed chunk's bytes (and nothing
     // else of its slot) go straight to their place in `out`
+    auto body = [&](uint32_t i) { return comp(i) ? clen[i] : it.in_len[i]; };  // a chunk's bytes behind its CRC
     for (uint32_t i = 0; i < ns; ++i)
-        if (sl[i].comp && ((clen[i] + 4) >> 24)) return NX_ERR_INVALID_ARG;  // setChunkLength (:126-132)
-    {
-        size_t q = op;
-        for (uint32_t i = 0; i < ns && ok; ++i) {
-            if (sl[i].comp) {
-                ok = g.d2h(out + q + 8, g.dout.as<uint8_t>() + ooff[i], clen[i]);
-                q += 8 + clen[i];
-            } else {
-                q += 8 + sl[i].len;
-            }
-        }
-        if (!g.sync() || !ok) return NX_ERR_HIP;
+        if (comp(i) && ((clen[i] + 4) >> 24)) return NX_ERR_INVALID_ARG;  // setChunkLength (:126-132)
+    bool ok = true;
+    size_t q = op;
+    for (uint32_t i = 0; i < ns && ok; ++i) {
+        if (comp(i)) ok = it.copy_item(i, out + q + 8);
+        q += 8 + body(i);
     }
+    if (!g.sync() || !ok) return NX_ERR_HIP;
     for (uint32_t i = 0; i < ns; ++i) {
-        if (sl[i].comp) {
-            const uint32_t chunkLength = clen[i] + 4;  // setChunkLength (:126-132)
-            if (chunkLength >> 24) return NX_ERR_INVALID_ARG;
-            out[op++] = 0;
-            out[op++] = (uint8_t)chunkLength;
-            out[op++] = (uint8_t)(chunkLength >> 8);
-            out[op++] = (uint8_t)(chunkLength >> 16);
-            memcpy(out + op, &crc[i], 4);
-            op += 4 + clen[i];  // payload already copied from the device
-        } else {
-            const uint32_t cl = sl[i].len + 4;
-            out[op++] = 1;
-            out[op++] = (uint8_t)cl;
-            out[op++] = (uint8_t)(cl >> 8);
-            out[op++] = (uint8_t)(cl >> 16);
-            memcpy(out + op, &crc[i], 4);
-            op += 4;
-            nx::copy_bytes(out + op, in + sl[i].off, sl[i].len);
-            op += sl[i].len;
-        }
+        const uint32_t chunkLength = body(i) + 4;
+        out[op++] = comp(i) ? 0 : 1;
+        out[op++] = (uint8_t)chunkLength;
+        out[op++] = (uint8_t)(chunkLength >> 8);
+        out[op++] = (uint8_t)(chunkLength >> 16);
+        memcpy(out + op, &crc[i], 4);
+        op += 4;
+        if (!comp(i)) nx::copy_bytes(out + op, in + it.in_off[i], it.in_len[i]);  // (a compressed chunk's came from the device)
+        op += body(i);
     }
     return (int64_t)op;
 }
@@ -161,12 +148,8 @@ extern "C" int64_t nx_snappy_frame_encoder_encode(nx_snappy_frame_encoder* e, co
 // ======================================================================= Snappy frame decoder
 
 extern "C" nx_snappy_frame_decoder* nx_snappy_frame_decoder_new(int32_t validate) {
-    auto* d = new nx_snappy_frame_decoder();
-    if (!d->g.hold(nx::WsKind::DecRecords)) {
-        delete d;
-        return nullptr;
-    }
-    d->validate = validate != 0;
+    auto* d = make_handle<nx_snappy_frame_decoder>(nx::WsKind::DecRecords);
+    if (d) d->validate = validate != 0;
     return d;
 }
 extern "C" void nx_snappy_frame_decoder_free(nx_snappy_frame_decoder* d) { nx_decoder_unref(d); }
@@ -244,27 +227,32 @@ extern "C" int32_t nx_snappy_frame_decoder_decode(nx_snappy_frame_decoder* d, co
                 ioff[ncomp + j] = a.data - lo;
                 ilen[ncomp + j] = a.dlen;
             }
-            if (!g.din.ensure(span + 1) || !g.dout.ensure((size_t)ncomp * 65536 + 16) || !g.a0.ensure(8ull * nj) ||
-                !g.a1.ensure(8ull * ncomp + 8) || !g.a2.ensure(4ull * nj) || !g.a3.ensure(4ull * ncomp + 4) ||
-                !g.a4.ensure(4ull * ncomp + 4) || !g.a5.ensure(4ull * ncomp + 4) || !g.a6.ensure(4ull * nj + 4))
+            if (!g.din.ensure(span + 1) || !g.dout.ensure((size_t)ncomp * 65536 + 16) || !g.in_off.ensure(8ull * nj) ||
+                !g.out_off.ensure(8ull * ncomp + 8) || !g.in_len.ensure(4ull * nj) || !g.out_len.ensure(4ull * ncomp + 4) ||
+                !g.status.ensure(4ull * ncomp + 4) || !g.aux0.ensure(4ull * ncomp + 4) || !g.aux1.ensure(4ull * nj + 4))
                 return finish(NX_ERR_HIP);
-            bool ok = g.h2d(g.din.p, in + lo, span) && g.h2d(g.a0.p, ioff.data(), 8ull * nj) && g.h2d(g.a2.p, ilen.data(), 4ull * nj) &&
-                      g.h2d(g.a1.p, ooff.data(), 8ull * ncomp) && g.h2d(g.a5.p, expect.data(), 4ull * ncomp);
+            // the compressed chunks' statuses and the raw chunks' CRCs share aux1; g.status takes the kernel's
+            // consumed counts and aux0 the expected CRCs
+            uint32_t* d_cons = g.status.as<uint32_t>();
+            uint32_t* d_expect = g.aux0.as<uint32_t>();
+            int32_t* d_st = g.aux1.as<int32_t>();
+            uint32_t* d_ucrc = g.aux1.as<uint32_t>() + ncomp;
+            bool ok = g.h2d(g.din.p, in + lo, span) && g.h2d(g.in_off.p, ioff.data(), 8ull * nj) &&
+                      g.h2d(g.in_len.p, ilen.data(), 4ull * nj) && g.h2d(g.out_off.p, ooff.data(), 8ull * ncomp) &&
+                      g.h2d(d_expect, expect.data(), 4ull * ncomp);
             if (!ok) return finish(NX_ERR_HIP);
-            int32_t* d_st = g.a6.as<int32_t>();
-            uint32_t* d_ucrc = g.a6.as<uint32_t>() + ncomp;
             if (ncomp) {
-                int32_t r = nx_snappy_decode_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.dout.as<uint8_t>(),
-                                                   g.a1.as<uint64_t>(), nullptr, g.a3.as<uint32_t>(), g.a4.as<uint32_t>(), d_st,
-                                                   d->validate ? g.a5.as<uint32_t>() : nullptr, nullptr, ncomp, g.s);
+                int32_t r = nx_snappy_decode_batch(g.din.as<uint8_t>(), g.in_off.as<uint64_t>(), g.in_len.as<uint32_t>(),
+                                                   g.dout.as<uint8_t>(), g.out_off.as<uint64_t>(), nullptr, g.out_len.as<uint32_t>(), d_cons,
+                                                   d_st, d->validate ? d_expect : nullptr, nullptr, ncomp, g.s);
                 if (r != NX_OK) return finish(r);
             }
             if (nunc) {
-                int32_t r = nx_crc32c_masked_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>() + ncomp, g.a2.as<uint32_t>() + ncomp, d_ucrc,
-                                                   nunc, g.s);
+                int32_t r = nx_crc32c_masked_batch(g.din.as<uint8_t>(), g.in_off.as<uint64_t>() + ncomp, g.in_len.as<uint32_t>() + ncomp,
+                                                   d_ucrc, nunc, g.s);
                 if (r != NX_OK) return finish(r);
             }
-            ok = g.d2h(olen.data(), g.a3.p, 4ull * ncomp) && g.d2h(cons.data(), g.a4.p, 4ull * ncomp) &&
+            ok = g.d2h(olen.data(), g.out_len.p, 4ull * ncomp) && g.d2h(cons.data(), d_cons, 4ull * ncomp) &&
                  g.d2h(st.data(), d_st, 4ull * ncomp) && g.d2h(ucrc.data(), d_ucrc, 4ull * nunc) && g.sync();
             if (!ok) return finish(NX_ERR_HIP);
             // only the bytes each chunk produced cross PCIe (a message's olen, not its 64 KiB slot)
@@ -321,11 +309,8 @@ extern "C" int32_t nx_snappy_frame_decoder_decode(nx_snappy_frame_decoder* d, co
 
 extern "C" nx_fastlz_frame_encoder* nx_fastlz_frame_encoder_new(int32_t level, int32_t checksum) {
     if (level != 0 && level != 1 && level != 2) return nullptr;  // FastLzFrameEncoder.java:101-105
-    auto* e = new nx_fastlz_frame_encoder();
-    if (!e->g.hold(nx::WsKind::FastLzEnc)) {
-        delete e;
-        return nullptr;
-    }
+    auto* e = make_handle<nx_fastlz_frame_encoder>(nx::WsKind::FastLzEnc);
+    if (!e) return nullptr;
     e->level = level;
     e->checksum = checksum != 0;
     return e;
@@ -341,41 +326,36 @@ extern "C" int64_t nx_fastlz_frame_encoder_encode(nx_fastlz_frame_encoder* e, co
     if (out_cap < nx_fastlz_frame_max_encoded_length(n)) return NX_ERR_INVALID_ARG;
     const uint8_t* in = buf + r0;
     const size_t w = r0 + n;
-    const uint32_t nc = (uint32_t)((n + 65534) / 65535);
-    std::vector<uint64_t> ioff(nc), ooff(nc);
-    std::vector<uint32_t> ilen(nc);
-    std::vector<int32_t> lim(nc), lvl(nc, e->level);
-    uint64_t oc = 0;
-    for (uint32_t i = 0; i < nc; ++i) {
-        const size_t r = r0 + (size_t)i * 65535;
-        ioff[i] = (uint64_t)i * 65535;
-        ilen[i] = (uint32_t)((n - ioff[i]) < 65535 ? (n - ioff[i]) : 65535);
+    EncodeItems it(e->g);
+    std::vector<int32_t> lim;
+    for_each_piece(n, 65535, [&](size_t off, size_t len) {
+        const size_t r = r0 + off;
         const int64_t l64 = (int64_t)(w - r) - (int64_t)r;  // readableBytes() - inOffset (FastLz.java:552-557)
-        lim[i] = l64 < -0x40000000 ? -0x40000000 : (int32_t)l64;
-        ooff[i] = oc;
-        oc += nx_fastlz_max_compressed_length(ilen[i]) + 16;
-    }
+        lim.push_back(l64 < -0x40000000 ? -0x40000000 : (int32_t)l64);
+        it.add(off, (uint32_t)len, nx_fastlz_max_compressed_length(len) + 16);
+    });
+    const uint32_t nc = it.size();
+    const std::vector<int32_t> lvl(nc, e->level);
     Gpu& g = e->g;
-    if (!g.din.ensure(n) || !g.dout.ensure(oc) || !g.a0.ensure(8ull * nc) || !g.a1.ensure(8ull * nc) || !g.a2.ensure(4ull * nc) ||
-        !g.a3.ensure(4ull * nc) || !g.a4.ensure(4ull * nc) || !g.a5.ensure(4ull * nc) || !g.a6.ensure(8ull * nc))
-        return NX_ERR_HIP;
-    bool ok = g.h2d(g.din.p, in, n) && g.h2d(g.a0.p, ioff.data(), 8ull * nc) && g.h2d(g.a1.p, ooff.data(), 8ull * nc) &&
-              g.h2d(g.a2.p, ilen.data(), 4ull * nc) && g.h2d(g.a5.p, lim.data(), 4ull * nc) &&
-              g.h2d(g.a6.p, lvl.data(), 4ull * nc);
-    if (!ok) return NX_ERR_HIP;
-    int32_t r = nx_fastlz_compress_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.dout.as<uint8_t>(),
-                                         g.a1.as<uint64_t>(), g.a3.as<uint32_t>(), g.a6.as<int32_t>(), g.a5.as<int32_t>(),
-                                         g.a4.as<int32_t>(), nc, g.s);
+    int32_t r = it.stage(in, n, 0, 4ull * nc, 8ull * nc);
     if (r != NX_OK) return r;
-    std::vector<uint32_t> ad(nc);
-    if (e->checksum) {
-        // reuse a4 (status no longer needed after the compress kernel ran: stream-ordered)
-        r = nx_adler32_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.a4.as<uint32_t>(), nc, g.s);
+    int32_t* d_lim = g.aux0.as<int32_t>();
+    int32_t* d_lvl = g.aux1.as<int32_t>();
+    if (!g.h2d(d_lim, lim.data(), 4ull * nc) || !g.h2d(d_lvl, lvl.data(), 4ull * nc)) return NX_ERR_HIP;
+    r = nx_fastlz_compress_batch(it.d_in(), it.d_in_off(), it.d_in_len(), it.d_out(), it.d_out_off(), it.d_out_len(), d_lvl, d_lim,
+                                 it.d_status(), nc, g.s);
+    if (r != NX_OK) return r;
+    // The Adler32 values take the status array's place: this encoder never reads the statuses, and the
+    // checksum kernel runs after the compress kernel on the same stream.
+    uint32_t* d_adler = e->checksum ? reinterpret_cast<uint32_t*>(it.d_status()) : nullptr;
+    if (d_adler) {
+        r = nx_adler32_batch(it.d_in(), it.d_in_off(), it.d_in_len(), d_adler, nc, g.s);
         if (r != NX_OK) return r;
     }
-    std::vector<uint32_t> clen(nc);
-    ok = g.d2h(clen.data(), g.a3.p, 4ull * nc) && (!e->checksum || g.d2h(ad.data(), g.a4.p, 4ull * nc)) && g.sync();
-    if (!ok) return NX_ERR_HIP;
+    std::vector<uint32_t> ad(nc);
+    if (!it.fetch(false, d_adler, ad.data())) return NX_ERR_HIP;
+    const std::vector<uint32_t>&clen = it.len, &ilen = it.in_len;
+    bool ok = true;
     size_t op = 0;
     for (uint32_t i = 0; i < nc; ++i) {
         const uint32_t length = ilen[i];
@@ -400,11 +380,11 @@ extern "C" int64_t nx_fastlz_frame_encoder_encode(nx_fastlz_frame_encoder* e, co
             out[outputOffset + 1] = (uint8_t)chunkLength;
             outputOffset += 2;
             // only the compressed bytes cross PCIe, straight into their framed position
-            ok = ok && g.d2h(out + outputOffset + 2, g.dout.as<uint8_t>() + ooff[i], chunkLength);
+            ok = ok && it.copy_item(i, out + outputOffset + 2);
         } else {
             blockType = 0;
             chunkLength = length;
-            nx::copy_bytes(out + outputOffset + 2, in + ioff[i], length);
+            nx::copy_bytes(out + outputOffset + 2, in + it.in_off[i], length);
         }
         out[outputOffset] = (uint8_t)(length >> 8);
         out[outputOffset + 1] = (uint8_t)length;
@@ -427,8 +407,9 @@ struct FlzSync {
     static constexpr bool kReadsOn = true;  // decompress may read past its chunk (in_avail = readable bytes)
     static size_t stage_end(size_t n, size_t, size_t) { return n; }
     static int32_t decode(Gpu& g, uint32_t nz) {
-        return nx_fastlz_decompress_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.a5.as<uint32_t>(),
-                                          g.dout.as<uint8_t>(), g.a1.as<uint64_t>(), g.a3.as<uint32_t>(), g.a4.as<int32_t>(), nz, g.s);
+        return nx_fastlz_decompress_batch(g.din.as<uint8_t>(), g.in_off.as<uint64_t>(), g.in_len.as<uint32_t>(), g.aux0.as<uint32_t>(),
+                                          g.dout.as<uint8_t>(), g.out_off.as<uint64_t>(), g.out_len.as<uint32_t>(),
+                                          g.status.as<int32_t>(), nz, g.s);
     }
     static bool block_error(int32_t r, const Blk& b, uint8_t first, int32_t* code, std::string* msg) {
         return nx::af::flz_block_error(r, b.olen, first, code, msg);
@@ -453,8 +434,8 @@ struct LzfSync {
     static constexpr bool kReadsOn = false;
     static size_t stage_end(size_t, size_t p, size_t) { return p; }
     static int32_t decode(Gpu& g, uint32_t nz) {
-        return nx_lzf_decode_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.dout.as<uint8_t>(),
-                                   g.a1.as<uint64_t>(), g.a3.as<uint32_t>(), g.a4.as<int32_t>(), nz, g.s);
+        return nx_lzf_decode_batch(g.din.as<uint8_t>(), g.in_off.as<uint64_t>(), g.in_len.as<uint32_t>(), g.dout.as<uint8_t>(),
+                                   g.out_off.as<uint64_t>(), g.out_len.as<uint32_t>(), g.status.as<int32_t>(), nz, g.s);
     }
     static bool block_error(int32_t st, const Blk&, uint8_t, int32_t* code, std::string* msg) {
         if (st == NX_OK) return false;
@@ -474,8 +455,8 @@ struct Lz4Sync {
     static constexpr bool kReadsOn = false;
     static size_t stage_end(size_t, size_t, size_t last_end) { return last_end; }
     static int32_t decode(Gpu& g, uint32_t nz) {
-        return nx_lz4_decode_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.dout.as<uint8_t>(),
-                                   g.a1.as<uint64_t>(), g.a3.as<uint32_t>(), g.a4.as<int32_t>(), nz, g.s);
+        return nx_lz4_decode_batch(g.din.as<uint8_t>(), g.in_off.as<uint64_t>(), g.in_len.as<uint32_t>(), g.dout.as<uint8_t>(),
+                                   g.out_off.as<uint64_t>(), g.out_len.as<uint32_t>(), g.status.as<int32_t>(), nz, g.s);
     }
     static bool block_error(int32_t st, const Blk&, uint8_t, int32_t* code, std::string* msg) {
         if (st == NX_OK) return false;  // LZ4Exception → DecompressionException (:240-241)
@@ -569,23 +550,24 @@ int32_t alt_decode(D* d, const uint8_t* in, size_t n, size_t* consumed, const nx
             olen[job[i]] = b.olen;
             if (C::kReadsOn) iav[job[i]] = (uint32_t)(n - b.data);
         }
-        if (!g.din.ensure(span + 1) || !g.dout.ensure(ocap + 16) || !g.a0.ensure(8ull * nz + 8) || !g.a1.ensure(8ull * nz + 8) ||
-            !g.a2.ensure(4ull * nz + 4) || !g.a3.ensure(4ull * nz + 4) || !g.a4.ensure(4ull * nz + 4) ||
-            !g.a5.ensure(4ull * iav.size()) || !g.a6.ensure(16ull * nck))
+        if (!g.din.ensure(span + 1) || !g.dout.ensure(ocap + 16) || !g.in_off.ensure(8ull * nz + 8) || !g.out_off.ensure(8ull * nz + 8) ||
+            !g.in_len.ensure(4ull * nz + 4) || !g.out_len.ensure(4ull * nz + 4) || !g.status.ensure(4ull * nz + 4) ||
+            !g.aux0.ensure(4ull * iav.size()) || !g.aux1.ensure(16ull * nck))
             return finish(NX_ERR_HIP, 0);
-        uint64_t* d_coff = g.a6.as<uint64_t>();
+        // aux0: FastLZ's readable bytes per block; aux1: the checksum jobs' offsets, lengths and values
+        uint64_t* d_coff = g.aux1.as<uint64_t>();
         uint32_t* d_clen = reinterpret_cast<uint32_t*>(d_coff + nck);
         uint32_t* d_cval = d_clen + nck;
-        bool ok = g.h2d(g.din.p, in + lo, span) && g.h2d(g.a0.p, ioff.data(), 8ull * nz) && g.h2d(g.a1.p, ooff.data(), 8ull * nz) &&
-                  g.h2d(g.a2.p, ilen.data(), 4ull * nz) && g.h2d(g.a3.p, olen.data(), 4ull * nz) &&
-                  g.h2d(g.a5.p, iav.data(), 4ull * iav.size()) && g.h2d(d_coff, coff.data(), 8ull * nck) &&
-                  g.h2d(d_clen, clen.data(), 4ull * nck);
+        bool ok = g.h2d(g.din.p, in + lo, span) && g.h2d(g.in_off.p, ioff.data(), 8ull * nz) &&
+                  g.h2d(g.out_off.p, ooff.data(), 8ull * nz) && g.h2d(g.in_len.p, ilen.data(), 4ull * nz) &&
+                  g.h2d(g.out_len.p, olen.data(), 4ull * nz) && g.h2d(g.aux0.p, iav.data(), 4ull * iav.size()) &&
+                  g.h2d(d_coff, coff.data(), 8ull * nck) && g.h2d(d_clen, clen.data(), 4ull * nck);
         if (!ok) return finish(NX_ERR_HIP, 0);
         int32_t r = nz ? C::decode(g, nz) : NX_OK;
         if (r == NX_OK && ncz) r = C::checksum(g.dout.as<uint8_t>(), d_coff, d_clen, d_cval, ncz, g.s);
         if (r == NX_OK && ncr) r = C::checksum(g.din.as<uint8_t>(), d_coff + ncz, d_clen + ncz, d_cval + ncz, ncr, g.s);
         if (r != NX_OK) return finish(r, 0);
-        ok = g.d2h(res.data(), g.a4.p, 4ull * nz) && g.d2h(hout.data(), g.dout.p, ocap) && g.d2h(cval.data(), d_cval, 4ull * nck) &&
+        ok = g.d2h(res.data(), g.status.p, 4ull * nz) && g.d2h(hout.data(), g.dout.p, ocap) && g.d2h(cval.data(), d_cval, 4ull * nck) &&
              g.sync();
         if (!ok) return finish(NX_ERR_HIP, 0);
     }
@@ -614,12 +596,8 @@ int32_t alt_decode(D* d, const uint8_t* in, size_t n, size_t* consumed, const nx
 
 // ======================================================================= FastLZ frame decoder
 extern "C" nx_fastlz_frame_decoder* nx_fastlz_frame_decoder_new(int32_t validate) {
-    auto* d = new nx_fastlz_frame_decoder();
-    if (!d->g.hold(nx::WsKind::DecRecords)) {  // FastLZ blocks decode through the record expander
-        delete d;
-        return nullptr;
-    }
-    d->validate = validate != 0;
+    auto* d = make_handle<nx_fastlz_frame_decoder>(nx::WsKind::DecRecords);  // FastLZ blocks decode through the record expander
+    if (d) d->validate = validate != 0;
     return d;
 }
 extern "C" void nx_fastlz_frame_decoder_free(nx_fastlz_frame_decoder* d) { nx_alt_decoder_unref(d); }
@@ -643,12 +621,8 @@ extern "C" nx_lzf_encoder* nx_lzf_encoder_new_ex(int32_t total_length, int32_t c
 
 extern "C" nx_lzf_encoder* nx_lzf_encoder_new(int32_t compress_threshold) {
     if (compress_threshold < 16) return nullptr;  // LzfEncoder.java:152-156
-    auto* e = new nx_lzf_encoder();
-    if (!e->g.hold(nx::WsKind::LzfEnc)) {
-        delete e;
-        return nullptr;
-    }
-    e->threshold = compress_threshold;
+    auto* e = make_handle<nx_lzf_encoder>(nx::WsKind::LzfEnc);
+    if (e) e->threshold = compress_threshold;
     return e;
 }
 extern "C" void nx_lzf_encoder_free(nx_lzf_encoder* e) { delete e; }
@@ -673,45 +647,22 @@ extern "C" int64_t nx_lzf_encoder_encode(nx_lzf_encoder* e, const uint8_t* in, s
         } while (ip < n);
         return (int64_t)op;
     }
-    const uint32_t nc = (uint32_t)((n + 65534) / 65535);
-    std::vector<uint64_t> ioff(nc), ooff(nc);
-    std::vector<uint32_t> ilen(nc);
-    uint64_t oc = 0;
-    for (uint32_t i = 0; i < nc; ++i) {
-        ioff[i] = (uint64_t)i * 65535;
-        ilen[i] = (uint32_t)((n - ioff[i]) < 65535 ? (n - ioff[i]) : 65535);
-        ooff[i] = oc;
-        oc += nx_lzf_max_compressed_length(ilen[i]) + 16;
-    }
-    Gpu& g = e->g;
-    if (!g.din.ensure(n) || !g.dout.ensure(oc) || !g.a0.ensure(8ull * nc) || !g.a1.ensure(8ull * nc) || !g.a2.ensure(4ull * nc) ||
-        !g.a3.ensure(4ull * nc) || !g.a4.ensure(4ull * nc))
-        return NX_ERR_HIP;
-    bool ok = g.h2d(g.din.p, in, n) && g.h2d(g.a0.p, ioff.data(), 8ull * nc) && g.h2d(g.a1.p, ooff.data(), 8ull * nc) &&
-              g.h2d(g.a2.p, ilen.data(), 4ull * nc);
-    if (!ok) return NX_ERR_HIP;
-    int32_t r = nx_lzf_encode_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.dout.as<uint8_t>(),
-                                    g.a1.as<uint64_t>(), g.a3.as<uint32_t>(), g.a4.as<int32_t>(), nc, g.s);
+    EncodeItems it(e->g);
+    for_each_piece(n, 65535, [&](size_t off, size_t len) { it.add(off, (uint32_t)len, nx_lzf_max_compressed_length(len) + 16); });
+    int32_t r = it.stage(in, n);
     if (r != NX_OK) return r;
-    std::vector<uint32_t> olen(nc);
-    ok = g.d2h(olen.data(), g.a3.p, 4ull * nc) && g.sync();
-    if (!ok) return NX_ERR_HIP;
+    r = nx_lzf_encode_batch(it.d_in(), it.d_in_off(), it.d_in_len(), it.d_out(), it.d_out_off(), it.d_out_len(), it.d_status(),
+                            it.size(), e->g.s);
+    if (r != NX_OK) return r;
+    // the lengths only: this encoder has never read its items' statuses, and still does not
+    if (!it.fetch(false)) return NX_ERR_HIP;
     size_t op = 0;
-    for (uint32_t i = 0; i < nc && ok; ++i) {  // each block's bytes only, concatenated in place
-        ok = g.d2h(out + op, g.dout.as<uint8_t>() + ooff[i], olen[i]);
-        op += olen[i];
-    }
-    if (!g.sync() || !ok) return NX_ERR_HIP;
+    if (!it.copy_packed(out, &op)) return NX_ERR_HIP;  // each block's bytes only, concatenated in place
     return (int64_t)op;
 }
 
 extern "C" nx_lzf_decoder* nx_lzf_decoder_new(void) {
-    auto* d = new nx_lzf_decoder();
-    if (!d->g.hold(nx::WsKind::DecRecords)) {  // LZF blocks decode through the record expander
-        delete d;
-        return nullptr;
-    }
-    return d;
+    return make_handle<nx_lzf_decoder>(nx::WsKind::DecRecords);  // LZF blocks decode through the record expander
 }
 extern "C" void nx_lzf_decoder_free(nx_lzf_decoder* d) { nx_alt_decoder_unref(d); }
 
@@ -731,12 +682,9 @@ using nx::af::kLz4Magic;
 extern "C" nx_lz4_frame_encoder* nx_lz4_frame_encoder_new_ex(int32_t block_size, int32_t high_compressor, int32_t max_encode_size) {
     // compressionLevel(blockSize) :158-166; the device block encoder takes blocks below 32 MiB
     if (block_size < 64 || block_size > (1 << 25) || max_encode_size <= 0) return nullptr;
-    auto* e = new nx_lz4_frame_encoder();
+    auto* e = make_handle<nx_lz4_frame_encoder>(high_compressor ? nx::WsKind::Lz4HcEnc : nx::WsKind::Lz4Enc);
+    if (!e) return nullptr;
     e->high = high_compressor != 0;
-    if (!e->g.hold(e->high ? nx::WsKind::Lz4HcEnc : nx::WsKind::Lz4Enc)) {
-        delete e;
-        return nullptr;
-    }
     e->max_encode_size = max_encode_size;
     e->block_size = (uint32_t)block_size;
     const int32_t ceil_log2 = 32 - __builtin_clz((uint32_t)block_size - 1u);
@@ -748,7 +696,7 @@ extern "C" nx_lz4_frame_encoder* nx_lz4_frame_encoder_new(int32_t block_size) {
     return nx_lz4_frame_encoder_new_ex(block_size, 0, 0x7FFFFFFF);
 }
 extern "C" void nx_lz4_frame_encoder_free(nx_lz4_frame_encoder* e) { delete e; }
-extern "C" const char* nx_lz4_frame_encoder_error(nx_lz4_frame_encoder* e) { return e && !e->err.empty() ? e->err.c_str() : nullptr; }
+extern "C" const char* nx_lz4_frame_encoder_error(nx_lz4_frame_encoder* e) { return last_error(e); }
 extern "C" size_t nx_lz4_frame_max_encoded_length(size_t n, int32_t block_size) {
     const size_t bs = block_size > 0 ? (size_t)block_size : 65536;
     return (n / bs + 2) * (kLz4Header + 16 + bs / 255) + n + kLz4Header;
@@ -758,44 +706,19 @@ namespace {
 // flushBufferedData (:248-284) for nb consecutive blocks of `src` (the last may be short).
 int64_t lz4_flush_blocks(nx_lz4_frame_encoder* e, const uint8_t* src, size_t n, uint8_t* out, size_t out_cap) {
     if (n == 0) return 0;
-    const uint32_t bs = e->block_size;
-    const uint32_t nb = (uint32_t)((n + bs - 1) / bs);
-    std::vector<uint64_t> ioff(nb), ooff(nb);
-    std::vector<uint32_t> ilen(nb);
-    uint64_t oc = 0;
-    for (uint32_t i = 0; i < nb; ++i) {
-        ioff[i] = (uint64_t)i * bs;
-        ilen[i] = (uint32_t)((n - ioff[i]) < bs ? (n - ioff[i]) : bs);
-        ooff[i] = oc;
-        oc += kLz4Header + nx_lz4_max_compressed_length(ilen[i]);
-    }
-    Gpu& g = e->g;
-    if (!g.din.ensure(n) || !g.dout.ensure(oc) || !g.a0.ensure(8ull * nb) || !g.a1.ensure(8ull * nb) || !g.a2.ensure(4ull * nb) ||
-        !g.a3.ensure(4ull * nb) || !g.a4.ensure(4ull * nb))
-        return NX_ERR_HIP;
-    bool ok = g.h2d(g.din.p, src, n) && g.h2d(g.a0.p, ioff.data(), 8ull * nb) && g.h2d(g.a1.p, ooff.data(), 8ull * nb) &&
-              g.h2d(g.a2.p, ilen.data(), 4ull * nb);
-    if (!ok) return NX_ERR_HIP;
-    int32_t r = nx_lz4_frame_encode_batch_ex(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.dout.as<uint8_t>(),
-                                             g.a1.as<uint64_t>(), g.a3.as<uint32_t>(), e->level, e->high ? 1 : 0, g.a4.as<int32_t>(), nb,
-                                             g.s);
+    EncodeItems it(e->g);
+    for_each_piece(n, e->block_size,
+                   [&](size_t off, size_t len) { it.add(off, (uint32_t)len, kLz4Header + nx_lz4_max_compressed_length(len)); });
+    int32_t r = it.stage(src, n);
     if (r != NX_OK) return r;
-    std::vector<uint32_t> olen(nb);
-    std::vector<int32_t> st(nb);
-    ok = g.d2h(olen.data(), g.a3.p, 4ull * nb) && g.d2h(st.data(), g.a4.p, 4ull * nb) && g.sync();
-    if (!ok) return NX_ERR_HIP;
+    r = nx_lz4_frame_encode_batch_ex(it.d_in(), it.d_in_off(), it.d_in_len(), it.d_out(), it.d_out_off(), it.d_out_len(), e->level,
+                                     e->high ? 1 : 0, it.d_status(), it.size(), e->g.s);
+    if (r != NX_OK) return r;
+    if (!it.fetch(true)) return NX_ERR_HIP;
+    r = it.check_packed(out_cap);
+    if (r != NX_OK) return r;
     size_t op = 0;
-    for (uint32_t i = 0; i < nb; ++i) {
-        if (st[i] != NX_OK) return st[i];
-        if (op + olen[i] > out_cap) return NX_ERR_INVALID_ARG;
-        op += olen[i];
-    }
-    op = 0;
-    for (uint32_t i = 0; i < nb && ok; ++i) {  // each framed block's bytes only, concatenated in place
-        ok = g.d2h(out + op, g.dout.as<uint8_t>() + ooff[i], olen[i]);
-        op += olen[i];
-    }
-    if (!g.sync() || !ok) return NX_ERR_HIP;
+    if (!it.copy_packed(out, &op)) return NX_ERR_HIP;  // each framed block's bytes only, concatenated in place
     return (int64_t)op;
 }
 }  // namespace
@@ -852,25 +775,8 @@ extern "C" int64_t nx_lz4_frame_encoder_encode(nx_lz4_frame_encoder* e, const ui
         return (int64_t)n;
     }
     // :241-248 — fill the block buffer; every full buffer is flushed
-    const size_t have = e->buf.size();
-    const size_t total = have + n;
-    const size_t full = total / e->block_size * e->block_size;
-    if (full == 0) {
-        e->buf.insert(e->buf.end(), in, in + n);
-        return 0;
-    }
-    std::vector<uint8_t> joined;
-    const uint8_t* src = in;
-    if (have) {
-        joined.reserve(full);
-        joined.insert(joined.end(), e->buf.begin(), e->buf.end());
-        joined.insert(joined.end(), in, in + (full - have));
-        src = joined.data();
-    }
-    const int64_t w = lz4_flush_blocks(e, src, full, out, out_cap);
-    if (w < 0) return w;
-    e->buf.assign(in + (full - have), in + n);
-    return w;
+    return nx::h::write_blocks(e->buf, e->block_size, in, n,
+                               [&](const uint8_t* src, size_t full) { return lz4_flush_blocks(e, src, full, out, out_cap); });
 }
 
 static int64_t lz4_flush_buffer(nx_lz4_frame_encoder* e, uint8_t* out, size_t out_cap) {
@@ -912,50 +818,22 @@ constexpr size_t kZstdSlice = 65536;  // a frame of the batch encoder holds at m
 // short): one launch for all of them.  A block over 64 KiB is cut into 64 KiB slices, each its own frame.
 int64_t zstd_flush_blocks(nx_zstd_encoder* e, const uint8_t* src, size_t n, uint8_t* out, size_t out_cap) {
     if (n == 0) return 0;
-    const size_t bs = e->block_size;
-    std::vector<uint64_t> ioff, ooff;
-    std::vector<uint32_t> ilen;
-    uint64_t oc = 0;
-    for (size_t b = 0; b < n; b += bs) {
-        const size_t blen = n - b < bs ? n - b : bs;
-        for (size_t q = 0; q < blen; q += kZstdSlice) {
-            const uint32_t len = (uint32_t)(blen - q < kZstdSlice ? blen - q : kZstdSlice);
-            ioff.push_back(b + q);
-            ilen.push_back(len);
-            ooff.push_back(oc);
-            oc += (nx_zstd_max_compressed_length(len) + 15) / 16 * 16;
-        }
-    }
-    const uint32_t nb = (uint32_t)ilen.size();
-    Gpu& g = e->g;
-    if (!g.din.ensure(n) || !g.dout.ensure(oc) || !g.a0.ensure(8ull * nb) || !g.a1.ensure(8ull * nb) || !g.a2.ensure(4ull * nb) ||
-        !g.a3.ensure(4ull * nb) || !g.a4.ensure(4ull * nb))
-        return NX_ERR_HIP;
-    bool ok = g.h2d(g.din.p, src, n) && g.h2d(g.a0.p, ioff.data(), 8ull * nb) && g.h2d(g.a1.p, ooff.data(), 8ull * nb) &&
-              g.h2d(g.a2.p, ilen.data(), 4ull * nb);
-    if (!ok) return NX_ERR_HIP;
-    const int32_t r = nx_zstd_encode_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.dout.as<uint8_t>(),
-                                           g.a1.as<uint64_t>(), g.a3.as<uint32_t>(), g.a4.as<int32_t>(), nb, e->level, g.s);
+    EncodeItems it(e->g);
+    for_each_piece(n, e->block_size, [&](size_t b, size_t blen) {
+        for_each_piece(blen, kZstdSlice, [&](size_t q, size_t len) {
+            it.add(b + q, (uint32_t)len, (nx_zstd_max_compressed_length(len) + 15) / 16 * 16);
+        });
+    });
+    int32_t r = it.stage(src, n);
     if (r != NX_OK) return r;
-    std::vector<uint32_t> olen(nb);
-    std::vector<int32_t> st(nb);
-    ok = g.d2h(olen.data(), g.a3.p, 4ull * nb) && g.d2h(st.data(), g.a4.p, 4ull * nb) && g.sync();
-    if (!ok) return NX_ERR_HIP;
+    r = nx_zstd_encode_batch(it.d_in(), it.d_in_off(), it.d_in_len(), it.d_out(), it.d_out_off(), it.d_out_len(), it.d_status(),
+                             it.size(), e->level, e->g.s);
+    if (r != NX_OK) return r;
+    if (!it.fetch(true)) return NX_ERR_HIP;
+    r = it.check_packed(out_cap);
+    if (r != NX_OK) return r;
     size_t op = 0;
-    for (uint32_t i = 0; i < nb; ++i) {
-        if (st[i] != NX_OK) return st[i];
-        if (op + olen[i] > out_cap) return NX_ERR_INVALID_ARG;
-        op += olen[i];
-    }
-    // one copy of the slots up to the last frame's end, then the frames are packed on the host (a small
-    // block_size makes thousands of frames a call: a copy each would cost more than the bytes between them)
-    std::vector<uint8_t> slots((size_t)ooff[nb - 1] + olen[nb - 1]);
-    if (!g.d2h(slots.data(), g.dout.p, slots.size()) || !g.sync()) return NX_ERR_HIP;
-    op = 0;
-    for (uint32_t i = 0; i < nb; ++i) {
-        nx::copy_bytes(out + op, slots.data() + ooff[i], olen[i]);
-        op += olen[i];
-    }
+    if (!it.copy_span_packed(out, &op)) return NX_ERR_HIP;
     return (int64_t)op;
 }
 
@@ -986,18 +864,15 @@ int32_t zstd_check_size(nx_zstd_encoder* e, uint64_t remaining) {
 extern "C" nx_zstd_encoder* nx_zstd_encoder_new(int32_t level, int32_t block_size, int32_t max_encode_size) {
     // checkInRange(compressionLevel, MIN, MAX), checkPositive(blockSize), checkPositive(maxEncodeSize) :92-95
     if (level < -131072 || level > 22 || block_size <= 0 || max_encode_size <= 0) return nullptr;
-    auto* e = new nx_zstd_encoder();
-    if (!e->g.hold(nx::WsKind::ZstdEnc)) {
-        delete e;
-        return nullptr;
-    }
+    auto* e = make_handle<nx_zstd_encoder>(nx::WsKind::ZstdEnc);
+    if (!e) return nullptr;
     e->level = level;
     e->block_size = (uint32_t)block_size;
     e->max_encode_size = max_encode_size;
     return e;
 }
 extern "C" void nx_zstd_encoder_free(nx_zstd_encoder* e) { delete e; }
-extern "C" const char* nx_zstd_encoder_error(nx_zstd_encoder* e) { return e && !e->err.empty() ? e->err.c_str() : nullptr; }
+extern "C" const char* nx_zstd_encoder_error(nx_zstd_encoder* e) { return last_error(e); }
 extern "C" size_t nx_zstd_max_encoded_length(size_t pending, int32_t block_size) {
     const size_t bs = block_size > 0 ? (size_t)block_size : 65536;
     return pending / bs * nx_zstd_max_compressed_length(bs) + nx_zstd_max_compressed_length(pending % bs);
@@ -1011,24 +886,8 @@ extern "C" int64_t nx_zstd_encoder_encode(nx_zstd_encoder* e, const uint8_t* in,
         if (r != NX_OK) return r;
     }
     // :136-143 — fill the block buffer; every full buffer is flushed
-    const size_t have = e->buf.size();
-    const size_t full = (have + n) / e->block_size * e->block_size;
-    if (full == 0) {
-        e->buf.insert(e->buf.end(), in, in + n);
-        return 0;
-    }
-    std::vector<uint8_t> joined;
-    const uint8_t* src = in;
-    if (have) {
-        joined.reserve(full);
-        joined.insert(joined.end(), e->buf.begin(), e->buf.end());
-        joined.insert(joined.end(), in, in + (full - have));
-        src = joined.data();
-    }
-    const int64_t w = zstd_flush_blocks(e, src, full, out, out_cap);
-    if (w < 0) return w;
-    e->buf.assign(in + (full - have), in + n);
-    return w;
+    return nx::h::write_blocks(e->buf, e->block_size, in, n,
+                               [&](const uint8_t* src, size_t full) { return zstd_flush_blocks(e, src, full, out, out_cap); });
 }
 
 extern "C" int64_t nx_zstd_encoder_flush(nx_zstd_encoder* e, uint8_t* out, size_t out_cap) {
@@ -1063,9 +922,10 @@ int64_t bzip2_segment(nx_bzip2_encoder* e, const uint8_t* data, size_t len, uint
         nx_bzip2_seg seg;
     } p = {0, 0, (uint32_t)len, (uint32_t)cap, 0, 0, e->seg};
     p.seg.flags = last ? NX_BZIP2_SEG_LAST : 0u;
-    if (!g.din.ensure(len ? len : 1u) || !g.dout.ensure(cap) || !g.a0.ensure(sizeof p)) return NX_ERR_HIP;
-    if (!g.h2d(g.din.p, data, len) || !g.h2d(g.a0.p, &p, sizeof p)) return NX_ERR_HIP;
-    uint8_t* P = g.a0.as<uint8_t>();
+    DevBuf& par = g.aux0;  // the one item's arrays, uploaded and read back whole
+    if (!g.din.ensure(len ? len : 1u) || !g.dout.ensure(cap) || !par.ensure(sizeof p)) return NX_ERR_HIP;
+    if (!g.h2d(g.din.p, data, len) || !g.h2d(par.p, &p, sizeof p)) return NX_ERR_HIP;
+    uint8_t* P = par.as<uint8_t>();
     const int32_t r = nx_bzip2_encode_batch_split(g.din.as<uint8_t>(), (const uint64_t*)(P + offsetof(Par, in_off)),
                                                   (const uint32_t*)(P + offsetof(Par, in_len)), g.dout.as<uint8_t>(),
                                                   (const uint64_t*)(P + offsetof(Par, out_off)), (const uint32_t*)(P + offsetof(Par, out_cap)),
@@ -1073,7 +933,7 @@ int64_t bzip2_segment(nx_bzip2_encoder* e, const uint8_t* data, size_t len, uint
                                                   blocks, (nx_bzip2_seg*)(P + offsetof(Par, seg)), g.s);
     if (r != NX_OK) return r;
     e->launches += 1;
-    if (!g.d2h(&p, g.a0.p, sizeof p) || !g.sync()) return NX_ERR_HIP;
+    if (!g.d2h(&p, par.p, sizeof p) || !g.sync()) return NX_ERR_HIP;
     if (p.status != NX_OK) return p.status;
     if (p.out_len > out_cap) return NX_ERR_INVALID_ARG;
     if (!g.d2h(out, g.dout.p, p.out_len) || !g.sync()) return NX_ERR_HIP;
@@ -1104,7 +964,7 @@ extern "C" nx_bzip2_encoder* nx_bzip2_encoder_new(int32_t level) {
     return e;
 }
 extern "C" void nx_bzip2_encoder_free(nx_bzip2_encoder* e) { delete e; }
-extern "C" const char* nx_bzip2_encoder_error(nx_bzip2_encoder* e) { return e && !e->err.empty() ? e->err.c_str() : nullptr; }
+extern "C" const char* nx_bzip2_encoder_error(nx_bzip2_encoder* e) { return last_error(e); }
 extern "C" int32_t nx_bzip2_encoder_is_closed(const nx_bzip2_encoder* e) { return e && e->finished ? 1 : 0; }
 extern "C" uint64_t nx_bzip2_encoder_launches(const nx_bzip2_encoder* e) { return e ? e->launches : 0; }
 extern "C" size_t nx_bzip2_encoder_max_encoded_length(const nx_bzip2_encoder* e, size_t n) {
@@ -1172,12 +1032,8 @@ extern "C" int64_t nx_bzip2_encoder_close(nx_bzip2_encoder* e, uint8_t* out, siz
 // departs from the reference (whole frames only) is said at its declaration in netty_amd.h.
 extern "C" nx_zstd_decoder* nx_zstd_decoder_new(int32_t maximum_allocation_size) {
     if (maximum_allocation_size < 0) return nullptr;  // checkPositiveOrZero (:64)
-    auto* d = new nx_zstd_decoder();
-    if (!d->g.hold(nx::WsKind::ZstdDec)) {
-        delete d;
-        return nullptr;
-    }
-    d->max_alloc = maximum_allocation_size;
+    auto* d = make_handle<nx_zstd_decoder>(nx::WsKind::ZstdDec);
+    if (d) d->max_alloc = maximum_allocation_size;
     return d;
 }
 extern "C" void nx_zstd_decoder_free(nx_zstd_decoder* d) { delete d; }
@@ -1242,9 +1098,10 @@ extern "C" int32_t nx_zstd_decoder_decode(nx_zstd_decoder* d, const uint8_t* in,
             par32[i] = items[i].in_len;
             par32[nb + i] = items[i].out_cap;
         }
-        if (!g.din.ensure(bytes) || !g.a0.ensure(24ull * nb) || !g.dout.ensure(res + oc)) return NX_ERR_HIP;
-        if (!g.h2d(g.din.p, in, bytes) || !g.h2d(g.a0.p, par.data(), 24ull * nb)) return NX_ERR_HIP;
-        const uint64_t* dpar = g.a0.as<uint64_t>();
+        DevBuf& geom = g.aux0;  // the four geometry arrays, packed as `par` is
+        if (!g.din.ensure(bytes) || !geom.ensure(24ull * nb) || !g.dout.ensure(res + oc)) return NX_ERR_HIP;
+        if (!g.h2d(g.din.p, in, bytes) || !g.h2d(geom.p, par.data(), 24ull * nb)) return NX_ERR_HIP;
+        const uint64_t* dpar = geom.as<uint64_t>();
         const uint32_t* dpar32 = reinterpret_cast<const uint32_t*>(dpar + 2ull * nb);
         uint32_t* dres = g.dout.as<uint32_t>();
         const int32_t r = nx_zstd_decode_batch_ex(g.din.as<uint8_t>(), dpar, dpar32, g.dout.as<uint8_t>(), dpar + nb, dpar32 + nb, dres,
@@ -1283,12 +1140,8 @@ extern "C" int32_t nx_zstd_decoder_decode(nx_zstd_decoder* d, const uint8_t* in,
 }
 
 extern "C" nx_lz4_frame_decoder* nx_lz4_frame_decoder_new(int32_t validate_checksums) {
-    auto* d = new nx_lz4_frame_decoder();
-    if (!d->g.hold(nx::WsKind::DecRecords)) {
-        delete d;
-        return nullptr;
-    }
-    d->validate = validate_checksums != 0;
+    auto* d = make_handle<nx_lz4_frame_decoder>(nx::WsKind::DecRecords);
+    if (d) d->validate = validate_checksums != 0;
     return d;
 }
 extern "C" void nx_lz4_frame_decoder_free(nx_lz4_frame_decoder* d) { nx_alt_decoder_unref(d); }
@@ -1354,11 +1207,8 @@ constexpr size_t kZlibDictMax = 32768;  // what of a dictionary the window can h
 extern "C" nx_zlib_encoder* nx_zlib_encoder_new(int32_t wrapper, int32_t level) {
     if (level < -1 || level > 9) return nullptr;     // checkInRange (:124-125)
     if (wrapper < 0 || wrapper > 2) return nullptr;  // ZLIB_OR_NONE is not allowed for compression (:128-132)
-    auto* e = new nx_zlib_encoder();
-    if (!e->g.hold(nx::WsKind::DeflateEnc)) {
-        delete e;
-        return nullptr;
-    }
+    auto* e = make_handle<nx_zlib_encoder>(nx::WsKind::DeflateEnc);
+    if (!e) return nullptr;
     e->wrapper = wrapper;
     e->level = level;
     return e;
@@ -1395,59 +1245,44 @@ extern "C" int64_t nx_zlib_encoder_encode(nx_zlib_encoder* e, const uint8_t* in,
     if (out_cap < nx_zlib_max_encoded_length(n)) return NX_ERR_INVALID_ARG;
     // the stream's first slice lies behind the dictionary's tail (its history prefix) in din
     const uint32_t tail = e->dict_armed ? (uint32_t)e->dict.size() : 0u;
-    std::vector<uint64_t> ioff, ooff;
-    std::vector<uint32_t> ilen, plen;
-    uint64_t oc = 0;
+    EncodeItems it(e->g);
+    std::vector<uint32_t> plen;
     nx::zl::for_slices(n, tail, [&](size_t q, uint32_t len, uint32_t pre) {
-        ioff.push_back(tail + q);
-        ilen.push_back(len);
+        it.add(tail + q, len, (nx_deflate_max_compressed_length(len) + 127) & ~(size_t)127);
         plen.push_back(pre);
-        ooff.push_back(oc);
-        oc += (nx_deflate_max_compressed_length(len) + 127) & ~(size_t)127;
     });
-    const uint32_t ns = (uint32_t)ilen.size();
+    const uint32_t ns = it.size();
     Gpu& g = e->g;
-    if (!g.din.ensure(tail + n) || !g.dout.ensure(oc) || !g.a0.ensure(8ull * ns) || !g.a1.ensure(8ull * ns) ||
-        !g.a2.ensure(4ull * ns) || !g.a3.ensure(4ull * ns) || !g.a4.ensure(4ull * ns) || !g.a5.ensure(4ull * ns) ||
-        (tail && !g.a6.ensure(4ull * ns)))
+    int32_t r = it.stage(in, n, tail, 4ull * ns, tail ? 4ull * ns : 0);
+    if (r != NX_OK) return r;
+    uint32_t* d_sum = g.aux0.as<uint32_t>();   // each slice's CRC32 / Adler32
+    uint32_t* d_plen = g.aux1.as<uint32_t>();  // each slice's history prefix (the first write of a dictionary stream)
+    if (tail && (!g.h2d(d_plen, plen.data(), 4ull * ns) ||
+                 hipMemcpyAsync(g.din.p, e->ddict.p, tail, hipMemcpyDeviceToDevice, g.s) != hipSuccess))
         return NX_ERR_HIP;
-    bool ok = g.h2d(g.din.as<uint8_t>() + tail, in, n) && g.h2d(g.a0.p, ioff.data(), 8ull * ns) &&
-              g.h2d(g.a1.p, ooff.data(), 8ull * ns) && g.h2d(g.a2.p, ilen.data(), 4ull * ns);
-    if (tail)
-        ok = ok && g.h2d(g.a6.p, plen.data(), 4ull * ns) &&
-             hipMemcpyAsync(g.din.p, e->ddict.p, tail, hipMemcpyDeviceToDevice, g.s) == hipSuccess;
-    if (!ok) return NX_ERR_HIP;
-    int32_t r = NX_OK;
     if (e->wrapper == 1)
-        r = nx_crc32_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.a5.as<uint32_t>(), ns, g.s);
+        r = nx_crc32_batch(it.d_in(), it.d_in_off(), it.d_in_len(), d_sum, ns, g.s);
     else if (e->wrapper == 0)
-        r = nx_adler32_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.a5.as<uint32_t>(), ns, g.s);
+        r = nx_adler32_batch(it.d_in(), it.d_in_off(), it.d_in_len(), d_sum, ns, g.s);
     if (r != NX_OK) return r;
     if (tail)
-        r = nx_deflate_encode_batch_ex(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.a6.as<uint32_t>(),
-                                       g.dout.as<uint8_t>(), g.a1.as<uint64_t>(), g.a3.as<uint32_t>(), g.a4.as<int32_t>(), ns,
-                                       e->level, g.s);
+        r = nx_deflate_encode_batch_ex(it.d_in(), it.d_in_off(), it.d_in_len(), d_plen, it.d_out(), it.d_out_off(), it.d_out_len(),
+                                       it.d_status(), ns, e->level, g.s);
     else
-        r = nx_deflate_encode_batch(g.din.as<uint8_t>(), g.a0.as<uint64_t>(), g.a2.as<uint32_t>(), g.dout.as<uint8_t>(),
-                                    g.a1.as<uint64_t>(), g.a3.as<uint32_t>(), g.a4.as<int32_t>(), ns, e->level, g.s);
+        r = nx_deflate_encode_batch(it.d_in(), it.d_in_off(), it.d_in_len(), it.d_out(), it.d_out_off(), it.d_out_len(), it.d_status(),
+                                    ns, e->level, g.s);
     if (r != NX_OK) return r;
-    std::vector<uint32_t> olen(ns), sum(ns, 0u);
-    std::vector<int32_t> st(ns);
-    ok = g.d2h(olen.data(), g.a3.p, 4ull * ns) && g.d2h(st.data(), g.a4.p, 4ull * ns) &&
-         (e->wrapper == 2 || g.d2h(sum.data(), g.a5.p, 4ull * ns)) && g.sync();
-    if (!ok) return NX_ERR_HIP;
-    for (uint32_t i = 0; i < ns; ++i)
-        if (st[i] != NX_OK) return st[i];
+    std::vector<uint32_t> sum(ns, 0u);
+    if (!it.fetch(true, e->wrapper == 2 ? nullptr : d_sum, sum.data())) return NX_ERR_HIP;
+    r = it.first_status();
+    if (r != NX_OK) return r;
     size_t op = 0;
     if (e->write_header) {
         e->write_header = false;
         op = nx::zl::write_header(e, out);
     }
-    for (uint32_t i = 0; i < ns && ok; ++i) {  // each slice's bytes only, concatenated in place
-        ok = g.d2h(out + op, g.dout.as<uint8_t>() + ooff[i], olen[i]);
-        op += olen[i];
-    }
-    if (!g.sync() || !ok) return NX_ERR_HIP;
+    if (!it.copy_packed(out, &op)) return NX_ERR_HIP;  // each slice's bytes only, concatenated in place
+    const std::vector<uint32_t>& ilen = it.in_len;
     for (uint32_t i = 0; i < ns; ++i) {
         if (e->wrapper == 1) e->crc = nx_crc32_combine(e->crc, sum[i], ilen[i]);
         else if (e->wrapper == 0) e->adler = nx_adler32_combine(e->adler, sum[i], ilen[i]);

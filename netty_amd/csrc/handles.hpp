@@ -1,5 +1,6 @@
-// handles.hpp — device context and the Snappy handler handles shared by the synchronous handler layer
-// (handlers.cpp) and the asynchronous cross-channel batcher (batcher.cpp).  Private to the library.
+// handles.hpp — device context, the synchronous encoders' launch staging (EncodeItems) and the Snappy handler
+// handles shared by the synchronous handler layer (handlers.cpp) and the asynchronous cross-channel batcher
+// (batcher.cpp).  Private to the library.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -10,6 +11,7 @@
 #include <string>
 #include <vector>
 #include "../../include/netty_amd.h"
+#include "encode_items.hpp"
 #include "nx_common.hpp"
 #include "workspace.hpp"
 
@@ -50,7 +52,9 @@ struct Gpu {
     int dev = 0;
     bool ok = false;
     uint32_t held = 0;  // bit per WsKind whose shared workspace this handle holds (workspace.hpp)
-    DevBuf din, dout, a0, a1, a2, a3, a4, a5, a6;
+    // a launch's bytes and its per-item arrays, named for what the kernels take them as; aux0 and aux1 are
+    // the codec's own (a checksum per item, FastLZ's limits and levels, the decoders' checksum lists)
+    DevBuf din, dout, in_off, out_off, in_len, out_len, status, aux0, aux1;
     Gpu() {
         int n = 0;
         if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return;
@@ -78,6 +82,97 @@ struct Gpu {
     bool d2h(void* h, const void* d, size_t n) { return n == 0 || hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, s) == hipSuccess; }
     bool sync() { return hipStreamSynchronize(s) == hipSuccess; }
 };
+
+#pragma GCC visibility push(hidden)  // the library exports its C ABI, not its staging
+// One encode launch of a synchronous handle: the item table, staged into the handle's named arrays, and
+// what comes back.  The order of its copies and syncs is the encoders' own: every array is sized before
+// the first upload; the input bytes go up, then in_off, out_off and in_len; the lengths (and what else
+// the codec reads) come back with one sync, the items' bytes with a second.
+struct EncodeItems : ItemTable {
+    Gpu& g;
+    std::vector<uint32_t> len;  // fetch(): the bytes each item produced
+    std::vector<int32_t> st;    // fetch(true, ..): each item's status
+    explicit EncodeItems(Gpu& gpu) : g(gpu) {}
+    // Size the arrays (aux0 / aux1 too, for the codec's own uploads) and upload src[0, n) to din + din_prefix
+    // and the three item arrays.
+    int32_t stage(const uint8_t* src, size_t n, size_t din_prefix = 0, size_t aux0_bytes = 0, size_t aux1_bytes = 0) {
+        const size_t k = size();
+        if (!g.din.ensure(din_prefix + n) || !g.dout.ensure(out_bytes) || !g.in_off.ensure(8 * k) || !g.out_off.ensure(8 * k) ||
+            !g.in_len.ensure(4 * k) || !g.out_len.ensure(4 * k) || !g.status.ensure(4 * k) || !g.aux0.ensure(aux0_bytes) ||
+            !g.aux1.ensure(aux1_bytes))
+            return NX_ERR_HIP;
+        const bool ok = g.h2d(g.din.as<uint8_t>() + din_prefix, src, n) && g.h2d(g.in_off.p, in_off.data(), 8 * k) &&
+                        g.h2d(g.out_off.p, out_off.data(), 8 * k) && g.h2d(g.in_len.p, in_len.data(), 4 * k);
+        return ok ? NX_OK : NX_ERR_HIP;
+    }
+    // a kernel's parameters, in the types it takes them
+    const uint8_t* d_in() const { return g.din.as<uint8_t>(); }
+    const uint64_t* d_in_off() const { return g.in_off.as<uint64_t>(); }
+    const uint32_t* d_in_len() const { return g.in_len.as<uint32_t>(); }
+    uint8_t* d_out() const { return g.dout.as<uint8_t>(); }
+    const uint64_t* d_out_off() const { return g.out_off.as<uint64_t>(); }
+    uint32_t* d_out_len() const { return g.out_len.as<uint32_t>(); }
+    int32_t* d_status() const { return g.status.as<int32_t>(); }
+    // The lengths, the statuses if asked for, and one more 32-bit value per item (a checksum) from d_extra if
+    // given; then the sync.
+    bool fetch(bool with_status, const void* d_extra = nullptr, uint32_t* extra = nullptr) {
+        const size_t k = size();
+        len = std::vector<uint32_t>(k);
+        st = std::vector<int32_t>(with_status ? k : 0);
+        return g.d2h(len.data(), g.out_len.p, 4 * k) && (!with_status || g.d2h(st.data(), g.status.p, 4 * k)) &&
+               (!d_extra || g.d2h(extra, d_extra, 4 * k)) && g.sync();
+    }
+    int32_t first_status() const {  // in item order
+        for (int32_t s : st)
+            if (s != NX_OK) return s;
+        return NX_OK;
+    }
+    // first_status, and NX_ERR_INVALID_ARG where the items' bytes, packed, would pass out_cap: whichever
+    // an item reaches first
+    int32_t check_packed(size_t out_cap) const {
+        size_t op = 0;
+        for (uint32_t i = 0; i < size(); ++i) {
+            if (st[i] != NX_OK) return st[i];
+            if (op + len[i] > out_cap) return NX_ERR_INVALID_ARG;
+            op += len[i];
+        }
+        return NX_OK;
+    }
+    // Gather 1: an item's bytes (and nothing else of its slot) straight to their place in the caller's
+    // buffer.  The caller syncs once after its last item.
+    bool copy_item(uint32_t i, uint8_t* dst) { return g.d2h(dst, d_out() + out_off[i], len[i]); }
+    // ... every item, one behind the other from out + *op (advanced); synced
+    bool copy_packed(uint8_t* out, size_t* op) {
+        bool ok = true;
+        for (uint32_t i = 0; i < size() && ok; ++i) {
+            ok = copy_item(i, out + *op);
+            *op += len[i];
+        }
+        return g.sync() && ok;
+    }
+    // Gather 2 (Zstd): one copy of the slots up to the last frame's end, then the frames are packed on the
+    // host (a small block_size makes thousands of frames a call: a copy each would cost more than the bytes
+    // between them).
+    bool copy_span_packed(uint8_t* out, size_t* op) {
+        std::vector<uint8_t> slots((size_t)out_off.back() + len.back());
+        if (!g.d2h(slots.data(), g.dout.p, slots.size()) || !g.sync()) return false;
+        for (uint32_t i = 0; i < size(); ++i) {
+            copy_bytes(out + *op, slots.data() + out_off[i], len[i]);
+            *op += len[i];
+        }
+        return true;
+    }
+};
+
+// new H holding the device workspace of kind k, or nullptr
+template <class H>
+H* make_handle(WsKind k) {
+    auto* h = new H();
+    if (h->g.hold(k)) return h;
+    delete h;
+    return nullptr;
+}
+#pragma GCC visibility pop
 
 struct MsgList {
     std::vector<nx_msg> msgs;
