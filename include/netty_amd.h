@@ -355,7 +355,8 @@ int32_t nx_zstd_decode_host_ex(const uint8_t* in, size_t n, uint8_t* out, size_t
  * which this library does not carry; no encoder has written one since bzip2 0.9.5).  Where the Java throws an
  * unchecked array-index exception libbz2 decides: a selector index at or above the table count is
  * DECODING_BLOCK, a code length outside 1..23 or a code index outside the alphabet is CODE.  A block that ends
- * right after four equal bytes is a run of four.  "block length exceeds max block length"
+ * right after four equal bytes, its count byte missing, is DECODING_BLOCK (the Java reads on past the block's
+ * end, libbz2 calls the block corrupt).  "block length exceeds max block length"
  * (Bzip2BlockDecompressor.java:234) cannot be reached under the declared-size check and has no code.
  * One wave per stream, a stream's blocks one after another; the inverse BWT walk of a block is split into
  * nx_bzip2_decode_chains() sublists over the wave's lanes.  One slot of NX_WS_BZIP2_DEC workspace per stream

@@ -345,6 +345,8 @@ __device__ int32_t decode_block(WaveLds& L, uint8_t* slot, uint8_t* out, uint32_
     st = flush_out(L, out + opos, room - opos, dcnt, &crc, lane);
     if (st != NX_OK) return st;
     opos += dcnt;
+    st = (int32_t)uni((uint32_t)rle_end(L.R));  // (lane 0's last rle_step lies before the wave_sync above)
+    if (st != NX_OK) return st;
     if (~crc != uni(L.B.crc)) return NX_ERR_BZIP2_BLOCK_CRC;
     *produced = opos;
     return NX_OK;

@@ -23,7 +23,8 @@
 // (Bzip2BlockDecompressor.java:234) cannot be reached under the declared-size checks and has no code.
 // A block with the randomised bit set is refused (NX_ERR_BZIP2_RANDOMISED): this library does not carry
 // the format's 512-entry table.  A block that ends right after four equal bytes, with no count byte, is
-// a run of four (libbz2).
+// NX_ERR_BZIP2_DECODING_BLOCK (rle_end): the Java reads the count past the block's end
+// (Bzip2BlockDecompressor.java:297) and never meets the end again, libbz2 calls the block corrupt.
 //
 // Nothing is assumed about the input: no read leaves [in, in + n) (the bit reader hands out zeros past the
 // end and raises `over`, which every caller turns into NX_ERR_BZIP2_TRUNCATED before it trusts a value),
@@ -444,6 +445,8 @@ NX_HD void rle_step(Rle& R, const uint8_t* src, uint32_t n, uint32_t* used, uint
     *used = i;
     *cnt = c;
 }
+// After the block's last byte: four equal bytes whose count byte is missing are refused.
+NX_HD int32_t rle_end(const Rle& R) { return R.want_count ? NX_ERR_BZIP2_DECODING_BLOCK : NX_OK; }
 
 }  // namespace bz2d
 }  // namespace nx

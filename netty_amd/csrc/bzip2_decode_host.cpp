@@ -61,6 +61,8 @@ int32_t host_block(Work& W, const uint32_t* T, uint8_t* out, size_t cap, size_t*
         for (uint32_t k = 0; k < run_len; ++k) crc = crc_byte(T, crc, run_byte);
         pos += (size_t)cnt + run_len;
     }
+    st = rle_end(R);
+    if (st != NX_OK) return st;
     *produced = pos;
     *crc_out = ~crc;
     return NX_OK;
