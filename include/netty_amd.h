@@ -382,6 +382,70 @@ int32_t nx_bzip2_decode_host(const uint8_t* in, size_t n, uint8_t* out, size_t o
  * STREAM_ID, BLOCK_SIZE or BLOCK_HEADER.
  */
 int32_t nx_bzip2_stream_info(const uint8_t* in, size_t n, uint32_t* level, uint32_t* first_block_crc, uint32_t* is_empty);
+/*
+ * The same decode with a stream's blocks on several waves (DESIGN.md "Bzip2 decode, split").  bzip2 blocks are
+ * independent once their first bit is known and each starts with a 48-bit magic, so the call scans for the
+ * magics, decodes every candidate on a wave of its own and then follows the chain from the stream's first block.
+ * Launches on the one stream, none of which waits for another wave:
+ *   scan    k_bzip2_scan finds the block magic 0x314159265359 and the end magic 0x177245385090 at every bit
+ *           position of every item (a count pass, an exclusive scan, an emit pass: the list is in position
+ *           order whatever the scheduling);
+ * then, in rounds of as many candidates as the workspace has slots, taken in list order:
+ *   front   one wave per candidate: headers, tables, symbols, merged pointers and the inverse BWT walk into the
+ *           wave's slot; records status, end bit and the length the final stage will give;
+ *   stitch  one lane per item: from bit 32 follows end bit -> the candidate at exactly that bit, gives every
+ *           member its output offset and folds the stream CRC; a candidate the chain never reaches is a decoy
+ *           (data that spells a magic, or bytes after the stream) and is dropped whatever its status;
+ *   back    one wave per member: the final run-length stage from the slot to the member's offset, the cap
+ *           check and the block CRC;
+ * and a last launch that ends a stream at the first member whose final stage failed.
+ * Contract: status, out_len, consumed and the bytes out[0, out_len) of every item are those of
+ * nx_bzip2_decode_batch, valid input or not (bytes beyond out_len inside the cap are unspecified in both).
+ * The one new outcome: an item whose magics do not fit what is left of max_blocks gets
+ * NX_ERR_BZIP2_DECODE_BLOCKS (out_len and consumed 0); the items around it are unaffected.
+ *   max_blocks = the most candidates the call lists, over all items (a stream of b blocks has b + 1 and
+ *                whatever decoys its bytes hold); the call enqueues ceil(max_blocks / slots) rounds of three
+ *                launches whose waves exit at once when nothing is left, so a generous value costs empty
+ *                launches: pass the blocks + 1 of every item and a few spare per item (a decoy has
+ *                probability 2^-48 per bit and magic), or the sum of count[] of an nx_bzip2_scan_batch before.
+ *   blocks     = per item, the members of its chain that decoded (may be NULL).
+ * No host synchronisation.  Workspace: NX_WS_BZIP2_DEC, one slot per candidate of a round (sized by
+ * nx_bzip2_decoder_reserve for both calls); the call's lists live in a stream-ordered allocation.
+ * Which call is faster depends on the batch: many one-block streams fill the device on the serial call and
+ * gain nothing here; few streams of many blocks are what this one is for.  Callers choose.
+ *
+ * nx_bzip2_scan_batch is the scan alone.  positions[first[i] .. + count[i]) are item i's candidates in
+ * ascending order: the bit position in the item, NX_BZIP2_CAND_END set for the end magic.  status[i] is NX_OK
+ * or NX_ERR_BZIP2_DECODE_BLOCKS (then count[i] = 0).  All device arrays; positions holds max_blocks entries.
+ */
+#define NX_BZIP2_CAND_END (1ull << 63)
+int32_t nx_bzip2_scan_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n, uint32_t max_blocks,
+                            uint64_t* positions, uint32_t* first, uint32_t* count, int32_t* status, void* stream);
+int32_t nx_bzip2_decode_batch_split(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                                    const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len, uint32_t* consumed,
+                                    int32_t* status, uint32_t n, uint32_t max_blocks, uint32_t* blocks, void* stream);
+/*
+ * The host forms of the split path, by the same functions (csrc/bzip2_decode_core.hpp).  NOT product paths:
+ * the CPU check and the GPU tests' second opinion, like nx_bzip2_decode_host.
+ * nx_bzip2_scan_host: the candidates of in[0, n) in positions[0 .. min(*count, cap)), as the batch call lists
+ * them; *count is their number whatever cap is.
+ * nx_bzip2_decode_block_host: the one block whose magic stands at bit_pos, of a stream of the given level
+ * (1..9): its bytes at out, and in *info its status (also returned), the bit after its end-of-block symbol,
+ * its length before and after the final run-length stage and its stored and computed CRC (fields past the
+ * point of failure are 0).  NX_ERR_BZIP2_BLOCK_HEADER where no block magic stands at bit_pos.
+ * nx_bzip2_decode_split_host: one item of nx_bzip2_decode_batch_split: scan, every candidate's front, stitch,
+ * the members' back.
+ */
+typedef struct {
+    int32_t status;
+    uint32_t pre_len, final_len, stored_crc, computed_crc;
+    uint64_t end_bit;
+} nx_bzip2_block_info;
+int32_t nx_bzip2_scan_host(const uint8_t* in, size_t n, uint64_t* positions, size_t cap, size_t* count);
+int32_t nx_bzip2_decode_block_host(const uint8_t* in, size_t n, uint64_t bit_pos, int32_t level, uint8_t* out, size_t out_cap,
+                                   nx_bzip2_block_info* info);
+int32_t nx_bzip2_decode_split_host(const uint8_t* in, size_t n, uint8_t* out, size_t out_cap, size_t* out_len, size_t* consumed,
+                                   size_t max_blocks, size_t* blocks);
 
 /*
  * Replaces Bzip2Encoder.java (with Bzip2BlockCompressor, Bzip2MTFAndRLE2StageEncoder, Bzip2HuffmanStageEncoder,
@@ -760,6 +824,39 @@ int64_t nx_bzip2_encoder_encode(nx_bzip2_encoder* e, const uint8_t* in, size_t n
 int64_t nx_bzip2_encoder_close(nx_bzip2_encoder* e, uint8_t* out, size_t out_cap);
 int32_t nx_bzip2_encoder_is_closed(const nx_bzip2_encoder* e);
 uint64_t nx_bzip2_encoder_launches(const nx_bzip2_encoder* e);
+/*
+ * Bzip2Decoder.java:93-343 as a handle over nx_bzip2_decode_batch_split's kernels: the stream as the channel
+ * delivers it.  _decode behaves as nx_zstd_decoder_decode: in[0..n) is the cumulation, *consumed the bytes read,
+ * msgs one message per block in order (:306-318; the reference returns after each block and is called again,
+ * here all blocks of a call come from one sequence).  The four header bytes are parsed on the host
+ * ("Unexpected stream identifier contents. Mismatched bzip2 protocol version?", "block size is invalid").  The
+ * handle keeps the level, the running stream CRC and the 0..7 bits already used of the first unconsumed byte.
+ * A call uploads the cumulation once, scans it, and where a block can be attempted runs one front / stitch /
+ * back sequence over the chain head and every candidate the scan found; the results and the decoded bytes come
+ * back in two copies (the lists, then exactly the bytes of the blocks that decoded).  The output slot is sized
+ * for a declared block size per candidate; blocks that expand beyond it (long runs) make the handle repeat the
+ * sequence with a larger slot, the only case of more than one sequence a call.
+ * A block is attempted only when a later magic (block or end, a decoy too) stands in the received bytes, the
+ * end-of-stream marker only when its 10 bytes do.  A tail block that answers NX_ERR_BZIP2_TRUNCATED (a block
+ * behind a decoy magic) is "wait": *consumed stops at the byte that holds its first bit, the call returns NX_OK
+ * and the block is not attempted again until one more magic has arrived behind it, so a block still arriving
+ * is never decoded again and again.  After the end marker (stream CRC checked) the handle is closed and every
+ * later call consumes all its input and delivers nothing (:328-330).  On the first failing block the messages
+ * of the blocks before it are delivered and the call returns the status with the reference's exception text as
+ * err_msg; later calls discard their input.  Differences from the reference: that discarding (the reference
+ * keeps no such state and would go on from wherever the throw left it); the cumulation holds a whole compressed
+ * block, about 900 KB at most, because the reference decodes inside a partial block and this handle does not;
+ * randomised blocks are refused (NX_ERR_BZIP2_RANDOMISED).
+ * _stats: the decode sequences launched, the chain blocks attempted (decoys the chain never reaches are not
+ * counted) and the blocks emitted.
+ */
+typedef struct nx_bzip2_decoder nx_bzip2_decoder;
+nx_bzip2_decoder* nx_bzip2_decoder_new(void);
+void nx_bzip2_decoder_free(nx_bzip2_decoder* d);
+int32_t nx_bzip2_decoder_decode(nx_bzip2_decoder* d, const uint8_t* in, size_t n, size_t* consumed, const nx_msg** msgs, size_t* n_msgs,
+                                const char** err_msg);
+int32_t nx_bzip2_decoder_is_closed(const nx_bzip2_decoder* d);
+int32_t nx_bzip2_decoder_stats(const nx_bzip2_decoder* d, uint64_t* launches, uint64_t* blocks_attempted, uint64_t* blocks_emitted);
 
 /* ZstdDecoder(maximumAllocationSize)  ZstdDecoder.java:59-122.  NULL for a negative size
  * (checkPositiveOrZero, :64).  _decode as nx_lzf_decoder_decode: in[0..n) is the cumulation, *consumed the

@@ -138,6 +138,9 @@
 #define NX_ERR_BZIP2_ENCODE_FULL          (-126)
 /* This library's own (nx_bzip2_encode_batch_split): the item's blocks fall beyond the call's max_blocks. */
 #define NX_ERR_BZIP2_ENCODE_BLOCKS        (-127)
+/* This library's own (nx_bzip2_scan_batch, nx_bzip2_decode_batch_split): the item holds more block and
+ * end-of-stream magics than the call's max_blocks leaves room for. */
+#define NX_ERR_BZIP2_DECODE_BLOCKS        (-128)
 
 /* Device frame scan (nx_snappy_frame_scan_batch), one code per SnappyFrameDecoder throw site: */
 /* :116-118  "Unexpected length of stream identifier: %d" */

@@ -26,6 +26,10 @@ class NxMsg(C.Structure):
     _fields_ = [("data", C.POINTER(C.c_uint8)), ("len", C.c_size_t)]
 
 
+class Bzip2BlockInfo(C.Structure):  # nx_bzip2_block_info
+    _fields_ = [("status", i32), ("pre_len", u32), ("final_len", u32), ("stored_crc", u32), ("computed_crc", u32), ("end_bit", u64)]
+
+
 _SIGS = {
     "nx_version": (C.c_char_p, []),
     "nx_status_string": (C.c_char_p, [i32]),
@@ -62,6 +66,16 @@ _SIGS = {
     "nx_bzip2_decoder_reserve": (i32, [u32, vp]),
     "nx_bzip2_decode_chains": (u32, []),
     "nx_bzip2_decode_host": (i32, [C.c_char_p, sz, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
+    "nx_bzip2_scan_batch": (i32, [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp]),
+    "nx_bzip2_decode_batch_split": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, vp, vp]),
+    "nx_bzip2_scan_host": (i32, [C.c_char_p, sz, C.POINTER(u64), sz, C.POINTER(sz)]),
+    "nx_bzip2_decode_block_host": (i32, [C.c_char_p, sz, u64, i32, vp, sz, vp]),
+    "nx_bzip2_decode_split_host": (i32, [C.c_char_p, sz, vp, sz, C.POINTER(sz), C.POINTER(sz), sz, C.POINTER(sz)]),
+    "nx_bzip2_decoder_new": (vp, []),
+    "nx_bzip2_decoder_free": (None, [vp]),
+    "nx_bzip2_decoder_decode": (i32, [vp, C.c_char_p, sz, C.POINTER(sz), C.POINTER(C.POINTER(NxMsg)), C.POINTER(sz), C.POINTER(C.c_char_p)]),
+    "nx_bzip2_decoder_is_closed": (i32, [vp]),
+    "nx_bzip2_decoder_stats": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
     "nx_bzip2_encode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, u32, i32, vp]),
     "nx_bzip2_encoder_reserve": (i32, [u32, i32, vp]),
     "nx_bzip2_encoder_slot_bytes": (C.c_uint64, [i32]),

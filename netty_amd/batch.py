@@ -295,20 +295,99 @@ def zstd_next_frame(data: bytes):
     return 0, kind.value, fb.value, ob.value, fl.value
 
 
-def bzip2_decode(inp, in_off, in_len, out, out_off, out_cap):
+def bzip2_decode(inp, in_off, in_len, out, out_off, out_cap, split: bool = False, max_blocks=None):
     """One complete bzip2 stream per item (nx_bzip2_decode_batch): item i starts at inp[in_off[i]], only its
     first stream is decoded and bytes after it inside in_len[i] are left alone; it decodes into
     out[out_off[i] : + out_cap[i]].  Returns (out_len, consumed, status): the decoded size (on an error, the
     bytes of the blocks completed before it), the stream's compressed size and 0 or one NX_ERR_BZIP2_* code
-    (-110 .. -124) per item.  A block with the randomised bit set is refused (NX_ERR_BZIP2_RANDOMISED, -124)."""
+    (-110 .. -124) per item.  A block with the randomised bit set is refused (NX_ERR_BZIP2_RANDOMISED, -124).
+
+    split=True takes nx_bzip2_decode_batch_split: the same results item for item, a stream's blocks on several
+    waves, and a fourth tensor, every item's chain length (the blocks that decoded).  max_blocks is the most
+    candidates (block and end-of-stream magics, decoys included) the call lists over all items; an item whose
+    candidates fall beyond it gets NX_ERR_BZIP2_DECODE_BLOCKS (-128).  The default runs bzip2_scan first and
+    reads the count back, which synchronises; a caller that knows a bound passes it and the call does not."""
     n = in_len.numel()
     dev = inp.device
     out_len = torch.empty(n, dtype=torch.int32, device=dev)
     consumed = torch.empty(n, dtype=torch.int32, device=dev)
     status = torch.empty(n, dtype=torch.int32, device=dev)
-    _chk(_lib.load().nx_bzip2_decode_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_cap),
-                                           _ptr(out_len), _ptr(consumed), _ptr(status), n, _stream()), "nx_bzip2_decode_batch")
-    return out_len, consumed, status
+    if not split:
+        _chk(_lib.load().nx_bzip2_decode_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_cap),
+                                               _ptr(out_len), _ptr(consumed), _ptr(status), n, _stream()), "nx_bzip2_decode_batch")
+        return out_len, consumed, status
+    if max_blocks is None:
+        # a generous list for the pre-scan; should an item overflow even that, say so instead of passing it on
+        _, _, count, sst = bzip2_scan(inp, in_off, in_len, max_blocks=int(in_len.sum().item()) // 6 + n + 1)
+        if int((sst != 0).sum().item()):
+            raise RuntimeError("bzip2_decode(split=True): the pre-scan's list overflowed; pass max_blocks")
+        max_blocks = int(count.sum().item())
+    blocks = torch.empty(n, dtype=torch.int32, device=dev)
+    _chk(_lib.load().nx_bzip2_decode_batch_split(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_cap),
+                                                 _ptr(out_len), _ptr(consumed), _ptr(status), n, int(max_blocks), _ptr(blocks), _stream()),
+         "nx_bzip2_decode_batch_split")
+    return out_len, consumed, status, blocks
+
+
+def bzip2_scan(inp, in_off, in_len, max_blocks: int):
+    """nx_bzip2_scan_batch: every bit position of every item at which the block magic or the end-of-stream
+    magic stands.  Returns (positions, first, count, status): item i's candidates are
+    positions[first[i] : first[i] + count[i]] in ascending order, int64 with the sign bit (BZIP2_CAND_END) set for
+    the end magic; status is 0, or NX_ERR_BZIP2_DECODE_BLOCKS (-128) with count 0 for an item whose candidates do
+    not fit what is left of max_blocks."""
+    n = in_len.numel()
+    dev = inp.device
+    positions = torch.zeros(max(int(max_blocks), 1), dtype=torch.int64, device=dev)
+    first = torch.empty(n, dtype=torch.int32, device=dev)
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    _chk(_lib.load().nx_bzip2_scan_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), n, int(max_blocks), _ptr(positions), _ptr(first),
+                                         _ptr(count), _ptr(status), _stream()), "nx_bzip2_scan_batch")
+    return positions, first, count, status
+
+
+BZIP2_CAND_END = -(1 << 63)  # NX_BZIP2_CAND_END as the sign bit of an int64 position
+
+
+def bzip2_scan_host(data: bytes):
+    """nx_bzip2_scan_host on host bytes: [(bit position, is_end)] of every magic in `data`, ascending (not a
+    product path)."""
+    import ctypes as C
+    data = bytes(data)
+    cnt = C.c_size_t(0)
+    L = _lib.load()
+    L.nx_bzip2_scan_host(data, len(data), None, 0, C.byref(cnt))
+    pos = (C.c_uint64 * max(cnt.value, 1))()
+    _chk(L.nx_bzip2_scan_host(data, len(data), pos, cnt.value, C.byref(cnt)), "nx_bzip2_scan_host")
+    return [(v & ((1 << 63) - 1), bool(v >> 63)) for v in pos[:cnt.value]]
+
+
+def bzip2_decode_block_host(data: bytes, bit_pos: int, level: int, out_cap: int):
+    """nx_bzip2_decode_block_host on host bytes: the one block whose magic stands at bit_pos of a stream at
+    `level`.  Returns (status, bytes, info) with info = dict(end_bit, pre_len, final_len, stored_crc,
+    computed_crc) (not a product path)."""
+    import ctypes as C
+    data = bytes(data)
+    buf = C.create_string_buffer(max(int(out_cap), 1))
+    info = _lib.Bzip2BlockInfo()
+    st = _lib.load().nx_bzip2_decode_block_host(data, len(data), int(bit_pos), int(level), C.cast(buf, C.c_void_p), int(out_cap),
+                                                C.byref(info))
+    got = buf.raw[:info.final_len] if st == 0 else b""
+    return st, got, {k: getattr(info, k) for k in ("end_bit", "pre_len", "final_len", "stored_crc", "computed_crc")}
+
+
+def bzip2_decode_split_host(data: bytes, out_cap: int, max_blocks=None):
+    """nx_bzip2_decode_split_host on host bytes: (status, decoded bytes, consumed, blocks) of the first stream of
+    `data` by scan, per-candidate decode and stitch on the CPU (not a product path); max_blocks defaults to no
+    limit."""
+    import ctypes as C
+    data = bytes(data)
+    buf = C.create_string_buffer(max(int(out_cap), 1))
+    ol, cs, nb = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    mb = (1 << 62) if max_blocks is None else int(max_blocks)
+    st = _lib.load().nx_bzip2_decode_split_host(data, len(data), C.cast(buf, C.c_void_p), int(out_cap), C.byref(ol), C.byref(cs), mb,
+                                                C.byref(nb))
+    return st, buf.raw[:ol.value], cs.value, nb.value
 
 
 def bzip2_decoder_reserve(max_streams: int):

@@ -92,6 +92,24 @@ NX_HD uint32_t br_bits(BitReader& r, uint32_t k) {  // k <= 32
     return (uint32_t)((r.buf >> r.cnt) & ((1ull << k) - 1ull));
 }
 NX_HD uint32_t br_bit(BitReader& r) { return br_bits(r, 1); }
+// A reader that starts at a bit position: byte `at` with its first `used` bits (0..7) already taken.
+NX_HD void br_init_bit(BitReader& r, const uint8_t* p, uint32_t n, uint32_t at, uint32_t used) {
+    br_init(r, p, n, at);
+    if (used != 0u && at < n) {
+        r.buf = p[at];
+        r.at = at + 1u;
+        r.cnt = 8u - used;
+    } else if (used != 0u) {
+        r.over = 1;  // the byte that holds the position is not there
+    }
+}
+NX_HD void br_init_bitpos(BitReader& r, const uint8_t* p, uint32_t n, uint64_t bitpos) {
+    const uint64_t at = bitpos >> 3;
+    br_init_bit(r, p, n, at < n ? (uint32_t)at : n, at < n ? (uint32_t)(bitpos & 7u) : 0u);
+}
+// The position of the next unread bit (br_bits loads a byte only when it needs one, so fewer than eight bits
+// wait in buf).  Meaningful while `over` is clear.
+NX_HD uint64_t br_bitpos(const BitReader& r) { return 8ull * r.at - r.cnt; }
 
 // ------------------------------------------------------------------ CRC-32, bzip2's bit order (Crc32.java)
 NX_HD uint32_t crc_table_entry(uint32_t i) {
@@ -447,6 +465,203 @@ NX_HD void rle_step(Rle& R, const uint8_t* src, uint32_t n, uint32_t* used, uint
 }
 // After the block's last byte: four equal bytes whose count byte is missing are refused.
 NX_HD int32_t rle_end(const Rle& R) { return R.want_count ? NX_ERR_BZIP2_DECODING_BLOCK : NX_OK; }
+// The bytes src[0, n) become in the final stage, without writing them: what rle_step's outputs add up to.
+NX_HD uint32_t rle_length(Rle& R, const uint8_t* src, uint32_t n) {
+    uint32_t total = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint8_t b = src[i];
+        if (R.want_count) {
+            R.want_count = 0;
+            R.acc = 0;
+            total += b;
+            continue;
+        }
+        if ((int32_t)b != R.last) {
+            R.last = b;
+            R.acc = 1;
+        } else if (++R.acc == 4u) {
+            R.want_count = 1;
+        }
+        total += 1u;
+    }
+    return total;
+}
+
+// ------------------------------------------------------------------ the split decode: magic scan and chain stitch
+// A stream's blocks are independent once their first bit is known, and each starts with the 48-bit block
+// magic.  The split decode (bzip2_decode_split.hip, nx_bzip2_decode_split_host) scans an item for both magics
+// at every bit position, decodes every candidate block on its own (the front: everything up to the pre-RLE
+// bytes, and the length the final stage will give), then walks the chain from the stream's first block: a
+// block's end bit names the candidate that follows it.  A candidate the chain never reaches is a decoy (the
+// magic's 48 bits spelt by data, or standing in bytes after the stream) and its result is dropped.
+constexpr uint64_t kCandEnd = 1ull << 63;  // a candidate's kind flag: the end-of-stream magic
+constexpr uint64_t kCandPos = kCandEnd - 1ull;
+constexpr uint64_t kMagicBlock = ((uint64_t)kBlockMagicHi << 24) | kBlockMagicLo;
+constexpr uint64_t kMagicEnd = ((uint64_t)kEndMagicHi << 24) | kEndMagicLo;
+constexpr uint32_t kScanWindow = 8;        // bytes whose bit positions one window tests (it reads 6 more)
+constexpr uint32_t kScanSegments = 64;     // an item is scanned in this many segments
+constexpr int32_t kChainOpen = 1;          // SplitItem::status while the chain is being walked
+// bytes per segment of an item of n bytes: a multiple of a wave's 64 windows
+NX_HD uint64_t scan_segment_bytes(uint32_t n) {
+    const uint64_t per = ((uint64_t)n + kScanSegments - 1u) / kScanSegments, step = 64u * kScanWindow;
+    return (per + step - 1u) / step * step;
+}
+// The magics that start in the eight bytes from b0: bit k of *blk (*end) is set when the block (end) magic
+// stands at bit 8 b0 + k and lies inside the item's n bytes.
+NX_HD void scan_window(const uint8_t* p, uint32_t n, uint64_t b0, uint64_t* blk, uint64_t* end) {
+    uint64_t mb = 0, me = 0;
+    if (b0 < n) {
+        uint8_t w[kScanWindow + 6];
+        for (uint32_t j = 0; j < kScanWindow + 6u; ++j) w[j] = b0 + j < n ? p[b0 + j] : (uint8_t)0;
+        uint64_t v = 0;  // the 56 bits from byte j
+        for (uint32_t j = 0; j < 6u; ++j) v = (v << 8) | w[j];
+        for (uint32_t j = 0; j < kScanWindow; ++j) {
+            v = ((v << 8) | w[j + 6u]) & ((1ull << 56) - 1ull);
+            for (uint32_t s = 0; s < 8u; ++s) {
+                const uint64_t m = (v >> (8u - s)) & ((1ull << 48) - 1ull);
+                const uint32_t k = 8u * j + s;
+                if ((m == kMagicBlock || m == kMagicEnd) && 8ull * b0 + k + 48u <= 8ull * n) {
+                    if (m == kMagicBlock) mb |= 1ull << k;
+                    else me |= 1ull << k;
+                }
+            }
+        }
+    }
+    *blk = mb;
+    *end = me;
+}
+
+// What the front of a candidate block leaves, and what the stitch and the back add.
+struct CandResult {
+    uint64_t end_bit;    // the bit after the block's end-of-block symbol
+    int32_t status;      // of stages 1-4
+    uint32_t pre_len;    // bytes before the final run-length stage
+    uint32_t final_len;  // bytes after it
+    uint32_t crc;        // the block's stored CRC
+    uint32_t member;     // stitch: the chain reaches this block
+    uint32_t off;        // stitch: where its bytes go in the item's output
+    int32_t back_status; // back: OUTPUT_FULL, the missing count byte, BLOCK_CRC or NX_OK
+    uint32_t crc_got;    // back: the CRC of its bytes
+};
+// Where an item's chain starts when the item is not a whole stream (the Bzip2Decoder handle): the stream's
+// header has been read before, the first block's magic stands at bit `expect` of the item, `crc` is the stream
+// CRC folded so far.  Such an item is a stream still arriving, so a block is attempted only when a later
+// candidate has arrived behind it, and the block at `expect` only when more than seen_after candidates have:
+// the number that stood behind it when it last answered TRUNCATED.
+struct SplitStart {
+    uint64_t expect;
+    uint32_t crc, level, seen_after, pad;
+};
+constexpr int32_t kNotAttempted = 2;  // CandResult::status of a block the rule above holds back
+// An item's chain, carried from round to round.
+struct SplitItem {
+    uint64_t expect;   // where the chain's next member must stand
+    uint64_t head;     // where the chain began
+    uint32_t cursor;   // the first of the item's candidates the chain has not passed
+    uint32_t off;      // output bytes given to members so far
+    uint32_t crc;      // the stream CRC folded over them
+    uint32_t blocks;   // members so far
+    uint32_t level;
+    uint32_t consumed;
+    int32_t status;    // kChainOpen, or how the stream ended
+    uint32_t arriving;        // a SplitStart was given
+    uint32_t seen_after;
+    uint32_t tail_attempted;  // status is TRUNCATED and it is the answer of a block's front
+};
+NX_HD void split_begin(SplitItem& I, const uint8_t* in, uint32_t n, const SplitStart* start = nullptr) {
+    I.expect = 32;
+    I.cursor = I.off = I.crc = I.blocks = I.level = I.consumed = 0;
+    I.arriving = I.seen_after = I.tail_attempted = 0;
+    if (start) {
+        I.expect = start->expect;
+        I.crc = start->crc;
+        I.level = start->level;
+        I.seen_after = start->seen_after;
+        I.arriving = 1;
+        I.status = kChainOpen;
+    } else {
+        const int32_t st = stream_header(in, n, &I.level);
+        I.status = st == NX_OK ? kChainOpen : st;
+    }
+    I.head = I.expect;
+}
+// Whether the block at bit `pos` is decoded now: always in a whole stream; in one still arriving, when enough
+// candidates stand behind it (`later` of them).
+NX_HD bool split_attempt(const SplitItem& I, uint64_t pos, uint32_t later) {
+    return !I.arriving || later > (pos == I.head ? I.seen_after : 0u);
+}
+// Extends the chain over the item's candidates pos[0, count), of which the first `ready` have a front result.
+// The order of the checks is decode_stream's: ten bytes of magic and CRC or TRUNCATED, the end magic and the
+// stream CRC, the block magic or BLOCK_HEADER, then the block.  Returns with I.status == kChainOpen when the
+// next member waits for a later round.
+NX_HD void split_stitch(SplitItem& I, const uint8_t* in, uint32_t n, uint32_t cap, const uint64_t* pos, CandResult* res, uint32_t count,
+                        uint32_t ready) {
+    while (I.status == kChainOpen) {  // every pass takes a candidate or ends the chain
+        if (I.expect + 80u > 8ull * n) {
+            I.status = NX_ERR_BZIP2_TRUNCATED;
+            break;
+        }
+        while (I.cursor < count && (pos[I.cursor] & kCandPos) < I.expect) I.cursor += 1u;
+        if (I.cursor == count || (pos[I.cursor] & kCandPos) != I.expect) {
+            I.status = NX_ERR_BZIP2_BLOCK_HEADER;  // neither magic stands there
+            break;
+        }
+        if (pos[I.cursor] & kCandEnd) {
+            BitReader r;
+            br_init_bitpos(r, in, n, I.expect + 48u);
+            const uint32_t crc = br_bits(r, 32);
+            if (crc != I.crc) {
+                I.status = NX_ERR_BZIP2_STREAM_CRC;
+            } else {
+                I.status = NX_OK;
+                I.consumed = r.at;  // the combined CRC's last byte holds the padding
+            }
+            break;
+        }
+        if (I.cursor >= ready) return;
+        CandResult& c = res[I.cursor];
+        if (c.status == kNotAttempted) {
+            I.status = NX_ERR_BZIP2_TRUNCATED;  // still arriving
+            break;
+        }
+        if (c.status != NX_OK) {
+            I.status = c.status;
+            I.tail_attempted = c.status == NX_ERR_BZIP2_TRUNCATED;
+            break;
+        }
+        if (c.final_len > cap - I.off) {
+            I.status = NX_ERR_BZIP2_OUTPUT_FULL;
+            break;
+        }
+        c.member = 1;
+        c.off = I.off;
+        I.off += c.final_len;
+        I.crc = crc_combine_stream(I.crc, c.crc);
+        I.blocks += 1u;
+        I.expect = c.end_bit;
+        I.cursor += 1u;
+    }
+}
+// After the last back: the first member whose final stage failed ends the stream there.
+NX_HD void split_finish(const SplitItem& I, const CandResult* res, uint32_t count, int32_t* status, uint32_t* out_len, uint32_t* consumed,
+                        uint32_t* blocks) {
+    uint32_t members = 0;
+    for (uint32_t k = 0; k < count && k < I.cursor; ++k) {
+        if (!res[k].member) continue;
+        if (res[k].back_status != NX_OK) {
+            *status = res[k].back_status;
+            *out_len = res[k].off;
+            *consumed = 0;
+            *blocks = members;
+            return;
+        }
+        members += 1u;
+    }
+    *status = I.status == kChainOpen ? NX_ERR_INTERNAL : I.status;
+    *out_len = I.off;
+    *consumed = I.status == NX_OK ? I.consumed : 0u;
+    *blocks = I.blocks;
+}
 
 }  // namespace bz2d
 }  // namespace nx

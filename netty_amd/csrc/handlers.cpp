@@ -33,6 +33,7 @@
 #include "frame_parse.hpp"
 #include "handles.hpp"
 #include "alt_frames.hpp"
+#include "bzip2_decode_split.hpp"
 
 extern "C" int32_t nx_snappy_decode_batch(const uint8_t*, const uint64_t*, const uint32_t*, uint8_t*, const uint64_t*,
                                           const uint32_t*, uint32_t*, uint32_t*, int32_t*, const uint32_t*, uint32_t*, uint32_t,
@@ -1733,4 +1734,171 @@ extern "C" int32_t nx_zlib_decoder_decode(nx_zlib_decoder* d, const uint8_t* in,
         if (step <= zl::kHalt) return finish(step - zl::kHalt);  // the launch itself failed: the decoder is as it was
     }
     return finish(step < 0 ? step : NX_OK);
+}
+
+// ------------------------------------------------------------------ Bzip2Decoder
+// Bzip2Decoder.java:93-343 over the split decode (bzip2_decode_split.hip).  The four header bytes are parsed
+// here; everything behind them is one item of decode_split_launch whose chain starts at the carried bit
+// position with the carried stream CRC.  Where the handle departs from the reference is said at its
+// declaration in netty_amd.h.
+extern "C" nx_bzip2_decoder* nx_bzip2_decoder_new(void) { return make_handle<nx_bzip2_decoder>(nx::WsKind::Bzip2Dec); }
+extern "C" void nx_bzip2_decoder_free(nx_bzip2_decoder* d) { delete d; }
+extern "C" int32_t nx_bzip2_decoder_is_closed(const nx_bzip2_decoder* d) { return d && d->closed ? 1 : 0; }
+extern "C" int32_t nx_bzip2_decoder_stats(const nx_bzip2_decoder* d, uint64_t* launches, uint64_t* blocks_attempted,
+                                          uint64_t* blocks_emitted) {
+    if (!d || !launches || !blocks_attempted || !blocks_emitted) return NX_ERR_INVALID_ARG;
+    *launches = d->launches;
+    *blocks_attempted = d->attempted;
+    *blocks_emitted = d->emitted;
+    return NX_OK;
+}
+
+extern "C" int32_t nx_bzip2_decoder_decode(nx_bzip2_decoder* d, const uint8_t* in, size_t n, size_t* consumed, const nx_msg** msgs,
+                                           size_t* n_msgs, const char** err_msg) {
+    using namespace nx::bz2d;
+    const nx::NoGrowScope no_grow;
+    if (!d || (!in && n) || !consumed || !msgs || !n_msgs) return NX_ERR_INVALID_ARG;
+    MsgList& ml = d->ml;
+    ml.clear();
+    *consumed = 0;
+    *msgs = nullptr;
+    *n_msgs = 0;
+    if (err_msg) *err_msg = nullptr;
+    if (d->closed || d->corrupted) {  // :328-330 in.skipBytes(in.readableBytes()); after an error: this handle's own state
+        *consumed = n;
+        return NX_OK;
+    }
+    auto fail = [&](int32_t st) {
+        d->corrupted = true;
+        ml.err = nx_status_string(st);
+        if (err_msg) *err_msg = ml.err.c_str();
+        *msgs = ml.msgs.data();
+        *n_msgs = ml.msgs.size();
+        *consumed = n;
+        return st;
+    };
+    size_t pos = 0;
+    if (!d->have_header) {  // :101-119
+        if (n < 4) return NX_OK;
+        uint32_t level = 0;
+        const int32_t st = stream_header(in, 4, &level);
+        if (st != NX_OK) return fail(st);
+        d->have_header = true;
+        d->level = level;
+        d->crc = 0;
+        d->bit_used = 0;
+        d->seen_after = 0;
+        pos = 4;
+    }
+    *consumed = pos;
+    constexpr size_t kMaxCumulation = 0x7fffffffu;
+    const size_t rem = n - pos < kMaxCumulation ? n - pos : kMaxCumulation;
+    if (8ull * rem < d->bit_used + 80ull) return NX_OK;  // not even a magic and a CRC
+    Gpu& g = d->g;
+    // the scan, and its list back: what stands in the received bytes decides whether anything is attempted
+    const uint32_t scan_cap = (uint32_t)(rem / 6 + 2);
+    if (!g.din.ensure(rem + 16) || !g.aux1.ensure(8ull * scan_cap + 64) || !g.in_off.ensure(64) || !g.status.ensure(64)) return NX_ERR_HIP;
+    struct Geom {
+        uint64_t in_off, out_off;
+        uint32_t in_len, out_cap;
+        SplitStart start;
+    } geom = {0, 0, (uint32_t)rem, 0, {d->bit_used, d->crc, d->level, d->seen_after, 0}};
+    if (!g.h2d(g.din.p, in + pos, rem) || !g.h2d(g.in_off.p, &geom, sizeof geom)) return NX_ERR_HIP;
+    const uint8_t* dgeom = g.in_off.as<uint8_t>();
+    uint32_t* dscan = g.status.as<uint32_t>();  // first, count, status
+    int32_t r = nx_bzip2_scan_batch(g.din.as<uint8_t>(), reinterpret_cast<const uint64_t*>(dgeom),
+                                    reinterpret_cast<const uint32_t*>(dgeom + 16), 1, scan_cap, g.aux1.as<uint64_t>(), dscan, dscan + 1,
+                                    reinterpret_cast<int32_t*>(dscan + 2), g.s);
+    if (r != NX_OK) return r;
+    uint32_t scan[3] = {0, 0, 0};
+    if (!g.d2h(scan, dscan, 12) || !g.sync()) return NX_ERR_HIP;
+    if ((int32_t)scan[2] != NX_OK) return NX_ERR_INTERNAL;  // (six bytes a magic: scan_cap always suffices for distinct magics)
+    const uint32_t count = scan[1];
+    std::vector<uint64_t> cand(count);
+    if (count && (!g.d2h(cand.data(), g.aux1.p, 8ull * count) || !g.sync())) return NX_ERR_HIP;
+    uint32_t head = 0;
+    while (head < count && (cand[head] & kCandPos) < d->bit_used) head += 1;
+    const bool at_head = head < count && (cand[head] & kCandPos) == d->bit_used;
+    if (!at_head) {
+        // neither magic where the next block must stand: "bad block header" once its 48 bits are all there
+        // (the reference looks after ten bytes, :122-140)
+        return fail(NX_ERR_BZIP2_BLOCK_HEADER);
+    }
+    if (!(cand[head] & kCandEnd) && count - 1u - head <= d->seen_after) return NX_OK;  // the block is still arriving
+    // one decode sequence over the chain head and every candidate; the output slot grows if the blocks need it
+    uint64_t cap = (uint64_t)count * d->level * kBaseBlock + 65536;
+    SplitLists S;
+    const size_t lists_bytes = split_lists_layout(S, nullptr, 1, count, true);
+    if (!g.aux0.ensure(lists_bytes) || !g.out_len.ensure(64)) return NX_ERR_HIP;
+    split_lists_layout(S, g.aux0.p, 1, count, true);
+    const size_t back_off = (size_t)(reinterpret_cast<uint8_t*>(S.first) - static_cast<uint8_t*>(g.aux0.p));
+    const size_t back_bytes = lists_bytes - back_off;
+    SplitLists H;  // the same layout over the host copy
+    const SplitItem* I = nullptr;
+    for (int attempt = 0;; ++attempt) {
+        if (cap > 0xffffffffull) cap = 0xffffffffull;
+        geom.out_cap = (uint32_t)cap;
+        if (!g.dout.ensure(cap) || !g.h2d(g.in_off.p, &geom, sizeof geom)) return NX_ERR_HIP;
+        uint32_t* dres = g.out_len.as<uint32_t>();  // out_len, consumed, status, blocks
+        r = decode_split_launch(g.din.as<uint8_t>(), reinterpret_cast<const uint64_t*>(dgeom), reinterpret_cast<const uint32_t*>(dgeom + 16),
+                                g.dout.as<uint8_t>(), reinterpret_cast<const uint64_t*>(dgeom + 8),
+                                reinterpret_cast<const uint32_t*>(dgeom + 20), dres, dres + 1, reinterpret_cast<int32_t*>(dres + 2), 1, count,
+                                dres + 3, reinterpret_cast<const SplitStart*>(dgeom + 24), g.aux0.p, g.s);
+        if (r != NX_OK) return r;
+        d->lists.resize(lists_bytes);
+        if (!g.d2h(d->lists.data() + back_off, static_cast<uint8_t*>(g.aux0.p) + back_off, back_bytes) || !g.sync()) return NX_ERR_HIP;
+        d->launches += 1;
+        split_lists_layout(H, d->lists.data(), 1, count, true);
+        I = H.items;
+        if (I->status != NX_ERR_BZIP2_OUTPUT_FULL || cap == 0xffffffffull || attempt == 8) break;
+        // the block at the cursor did not fit: room for it and a declared size for each behind it, at least twice the slot
+        const uint64_t need = (uint64_t)I->off + H.res[I->cursor].final_len + (uint64_t)(count - I->cursor) * d->level * kBaseBlock;
+        cap = need > 2 * cap ? need : 2 * cap;
+    }
+    // the members in chain order: a message each (:306-318) up to the first whose final stage failed
+    int32_t bad = NX_OK;
+    uint32_t members = 0, crc = d->crc;
+    uint64_t total = 0, next_bit = d->bit_used;
+    struct Piece {
+        uint32_t off, len;
+    };
+    std::vector<Piece> pieces;
+    for (uint32_t k = 0; k < I->cursor && k < count; ++k) {
+        const CandResult& c = H.res[k];
+        if (!c.member) continue;
+        members += 1;
+        if (c.back_status != NX_OK) {
+            bad = c.back_status;
+            break;
+        }
+        pieces.push_back({c.off, c.final_len});
+        total = (uint64_t)c.off + c.final_len;
+        crc = crc_combine_stream(crc, c.crc);
+        next_bit = c.end_bit;
+    }
+    const bool front_answer = bad == NX_OK && I->status != NX_OK && I->status != NX_ERR_BZIP2_STREAM_CRC && I->status != NX_ERR_BZIP2_OUTPUT_FULL &&
+                              I->status != NX_ERR_BZIP2_BLOCK_HEADER && (I->status != NX_ERR_BZIP2_TRUNCATED || I->tail_attempted);
+    d->attempted += members + (front_answer ? 1u : 0u);
+    d->emitted += pieces.size();
+    d->back.resize(total);
+    if (total && (!g.d2h(d->back.data(), g.dout.p, total) || !g.sync())) return NX_ERR_HIP;
+    for (const Piece& p : pieces) ml.msgs.push_back({d->back.data() + p.off, p.len});
+    if (bad != NX_OK) return fail(bad);
+    if (I->status == NX_OK) {  // the end marker, stream CRC checked: EOF (:126-135); what follows is skipped
+        d->closed = true;
+        *msgs = ml.msgs.data();
+        *n_msgs = ml.msgs.size();
+        *consumed = n;
+        return NX_OK;
+    }
+    if (I->status != NX_ERR_BZIP2_TRUNCATED) return fail(I->status);
+    // wait, as the reference waits: stop at the byte that holds the waiting block's first bit
+    if (I->tail_attempted) d->seen_after = count - 1u - I->cursor;
+    else if (!pieces.empty()) d->seen_after = 0;
+    d->crc = crc;
+    d->bit_used = (uint32_t)(next_bit & 7u);
+    *consumed = pos + (size_t)(next_bit >> 3);
+    *msgs = ml.msgs.data();
+    *n_msgs = ml.msgs.size();
+    return NX_OK;
 }

@@ -305,3 +305,16 @@ struct nx_zstd_decoder {
     std::vector<uint8_t> back;   // the last launch's results and output slots, as copied back
     uint64_t launches = 0, frames = 0;  // nx_zstd_decoder_stats
 };
+
+// Bzip2Decoder (handlers.cpp): the stream header's level, the running stream CRC and the bits already used of the
+// cumulation's first byte are carried between calls; a call's blocks come from one scan-and-decode sequence.
+struct nx_bzip2_decoder {
+    nx::h::Gpu g;
+    nx::h::MsgList ml;
+    bool have_header = false, closed = false, corrupted = false;
+    uint32_t level = 0, crc = 0, bit_used = 0;
+    uint32_t seen_after = 0;     // candidates behind the waiting block when its front last answered TRUNCATED
+    std::vector<uint8_t> back;   // the last call's decoded bytes
+    std::vector<uint8_t> lists;  // the last call's chain lists, as copied back
+    uint64_t launches = 0, attempted = 0, emitted = 0;  // nx_bzip2_decoder_stats
+};

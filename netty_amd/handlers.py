@@ -385,6 +385,35 @@ class Bzip2Encoder(_Encoder):
         return _lib.load().nx_bzip2_encoder_launches(self._h)
 
 
+class Bzip2Decoder(_Decoder):
+    """Bzip2Decoder.java:93-343 over the GPU bzip2 decoder's split path (nx_bzip2_decoder_*): the stream as the
+    channel delivers it, one message per block.  A read uploads the cumulation, scans it for block and
+    end-of-stream magics and decodes every block that has a later magic behind it in one launch sequence, a
+    block per wave; a block still arriving waits in the cumulation (readable_bytes(), a whole compressed block
+    at most: the reference decodes inside a partial block, this handle does not).  After the end-of-stream
+    marker is_closed() is true and further input is swallowed (:328-330).  The first failing block raises
+    DecompressionException with the reference's text (its code as .status, the messages of the blocks before
+    it as .decoded); afterwards input is swallowed too, a state the reference does not have.  Randomised
+    blocks are refused."""
+
+    _free = "nx_bzip2_decoder_free"
+    _decode_fn = "nx_bzip2_decoder_decode"
+
+    def __init__(self):
+        super().__init__()
+        self._h = _new(_lib.load().nx_bzip2_decoder_new(), "Bzip2Decoder")
+
+    def is_closed(self) -> bool:
+        """the end-of-stream marker has been read and its stream CRC checked (State.EOF)"""
+        return bool(_lib.load().nx_bzip2_decoder_is_closed(self._h))
+
+    def stats(self) -> dict:
+        """launch sequences made so far, chain blocks attempted and blocks emitted"""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _lib.load().nx_bzip2_decoder_stats(self._h, C.byref(a), C.byref(b), C.byref(c))
+        return {"launches": a.value, "blocks_attempted": b.value, "blocks_emitted": c.value}
+
+
 class ZstdDecoder(_Decoder):
     """ZstdDecoder.java:59-122 over the GPU Zstandard frame decoder (nx_zstd_decoder_*).  Every complete
     frame of a read is decoded in one launch, content checksums verified (XXH64) and skippable frames
