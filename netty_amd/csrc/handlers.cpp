@@ -12,6 +12,7 @@
 //   ZstdEncoder          ZstdEncoder.java:105-178
 //   ZstdDecoder          ZstdDecoder.java:59-122
 //   Bzip2Encoder         Bzip2Encoder.java:105-228
+//   Bzip2Decoder         Bzip2Decoder.java:93-343
 //   JdkZlibEncoder       JdkZlibEncoder.java:123-137, :214-276, :308-340
 //   JdkZlibDecoder       JdkZlibDecoder.java:117-160, :198-520 (+ ZlibDecoder.java:49,62-84)
 //
@@ -23,6 +24,14 @@
 // The seven encoders stage a launch through nx::h::EncodeItems (handles.hpp): the codec cuts its message
 // into items and says each one's slot size, calls its kernel with the typed device arrays, and says what
 // it reads back and where each item's bytes go.
+//
+// The seven decoders start a call with nx::h::DecodeCall (decode_call.hpp): it checks the arguments, empties
+// the handle's message list, and is the one place that writes consumed, msgs, n_msgs and err_msg (finish,
+// fail, skip_all); marking the decoder corrupted stays the codec's line.  The decoders with item lists (Snappy;
+// FastLZ, LZF and LZ4 in alt_decode) stage their launch through nx::h::DecodeItems (handles.hpp): the items and a
+// second list of checksum jobs, typed device accessors on the launch lines, one fetch.  The single-item decoders
+// (zlib, Bzip2; Bzip2Encoder's segment too) hand their kernels the fields of one small struct through
+// nx::h::ParamBlock; Zstd's packed geometry and results are typed views (ZstdGeometry, ZstdResults).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -40,8 +49,11 @@ extern "C" int32_t nx_snappy_decode_batch(const uint8_t*, const uint64_t*, const
                                           void*);
 
 namespace {
+using nx::h::DecodeCall;
+using nx::h::DecodeItems;
 using nx::h::DevBuf;
 using nx::h::EncodeItems;
+using nx::h::ParamBlock;
 using nx::h::Gpu;
 using nx::h::MsgList;
 using nx::h::for_each_piece;
@@ -51,6 +63,13 @@ using nx::h::make_handle;
 inline uint32_t le32(const uint8_t* p) { return p[0] | (p[1] << 8) | (p[2] << 16) | ((uint32_t)p[3] << 24); }
 inline uint32_t be16(const uint8_t* p) { return ((uint32_t)p[0] << 8) | p[1]; }
 inline uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
+
+// a decode() call's first failure in stream order: the status, the exception's text, where the reader stops
+struct Failure {
+    int32_t code = NX_OK;
+    std::string text;
+    size_t at = 0;
+};
 
 // the last failure's message of an encoder handle that keeps one (nullptr: none)
 template <class E>
@@ -162,27 +181,12 @@ using nx::fr::snappy_parse_one;
 extern "C" int32_t nx_snappy_frame_decoder_decode(nx_snappy_frame_decoder* d, const uint8_t* in, size_t n, size_t* consumed,
                                                   const nx_msg** msgs, size_t* n_msgs, const char** err_msg) {
     const nx::NoGrowScope no_grow;
-    if (!d || (!in && n)) return NX_ERR_INVALID_ARG;
-    MsgList& ml = d->ml;
-    ml.clear();
-    size_t rd = 0;
-    auto finish = [&](int32_t r) {
-        *consumed = rd;
-        *msgs = ml.msgs.data();
-        *n_msgs = ml.msgs.size();
-        if (err_msg) *err_msg = ml.err.empty() ? nullptr : ml.err.c_str();
-        return r;
-    };
-    auto corrupt = [&](size_t at, int32_t code, const std::string& msg) {
-        ml.err = msg;
-        d->corrupted = true;  // :227-230
-        rd = at;
-        return finish(code);
-    };
-    if (d->corrupted) {  // :86-89
-        rd = n;
-        return finish(NX_OK);
-    }
+    DecodeCall call(d, in, n, consumed, msgs, n_msgs, err_msg);
+    if (call.refused()) return NX_ERR_INVALID_ARG;
+    if (d->corrupted) return call.skip_all();  // :86-89
+    MsgList& ml = call.ml();
+    size_t& rd = call.rd;
+    Failure bad;  // the first failing chunk ends the call, as the Java exception does
     for (;;) {  // loops again only for the validating-mode leftover case below
         std::vector<SnappyAction> acts;
         size_t p = rd;
@@ -207,103 +211,81 @@ extern "C" int32_t nx_snappy_frame_decoder_decode(nx_snappy_frame_decoder* d, co
             lo = a.data < lo ? a.data : lo;
             hi = a.data + a.dlen > hi ? a.data + a.dlen : hi;
         }
-        const uint32_t ncomp = (uint32_t)comp_idx.size(), nunc = (uint32_t)unc_idx.size(), nj = ncomp + nunc;
-        std::vector<uint32_t> olen(ncomp), cons(ncomp), ucrc(nunc);
-        std::vector<int32_t> st(ncomp);
-        std::vector<std::vector<uint8_t>> outs(ncomp);  // each decoded chunk, exactly olen bytes
-        Gpu& g = d->g;
-        if (nj) {
-            const size_t span = hi - lo;
-            std::vector<uint64_t> ioff(nj), ooff(ncomp);
-            std::vector<uint32_t> ilen(nj), expect(ncomp);
-            for (uint32_t j = 0; j < ncomp; ++j) {
-                const SnappyAction& a = acts[comp_idx[j]];
-                ioff[j] = a.data - lo;
-                ilen[j] = a.dlen;
-                ooff[j] = (uint64_t)j * 65536;
-                expect[j] = a.crc;
-            }
-            for (uint32_t j = 0; j < nunc; ++j) {
-                const SnappyAction& a = acts[unc_idx[j]];
-                ioff[ncomp + j] = a.data - lo;
-                ilen[ncomp + j] = a.dlen;
-            }
-            if (!g.din.ensure(span + 1) || !g.dout.ensure((size_t)ncomp * 65536 + 16) || !g.in_off.ensure(8ull * nj) ||
-                !g.out_off.ensure(8ull * ncomp + 8) || !g.in_len.ensure(4ull * nj) || !g.out_len.ensure(4ull * ncomp + 4) ||
-                !g.status.ensure(4ull * ncomp + 4) || !g.aux0.ensure(4ull * ncomp + 4) || !g.aux1.ensure(4ull * nj + 4))
-                return finish(NX_ERR_HIP);
-            // the compressed chunks' statuses and the raw chunks' CRCs share aux1; g.status takes the kernel's
-            // consumed counts and aux0 the expected CRCs
-            uint32_t* d_cons = g.status.as<uint32_t>();
-            uint32_t* d_expect = g.aux0.as<uint32_t>();
-            int32_t* d_st = g.aux1.as<int32_t>();
-            uint32_t* d_ucrc = g.aux1.as<uint32_t>() + ncomp;
-            bool ok = g.h2d(g.din.p, in + lo, span) && g.h2d(g.in_off.p, ioff.data(), 8ull * nj) &&
-                      g.h2d(g.in_len.p, ilen.data(), 4ull * nj) && g.h2d(g.out_off.p, ooff.data(), 8ull * ncomp) &&
-                      g.h2d(d_expect, expect.data(), 4ull * ncomp);
-            if (!ok) return finish(NX_ERR_HIP);
-            if (ncomp) {
-                int32_t r = nx_snappy_decode_batch(g.din.as<uint8_t>(), g.in_off.as<uint64_t>(), g.in_len.as<uint32_t>(),
-                                                   g.dout.as<uint8_t>(), g.out_off.as<uint64_t>(), nullptr, g.out_len.as<uint32_t>(), d_cons,
-                                                   d_st, d->validate ? d_expect : nullptr, nullptr, ncomp, g.s);
-                if (r != NX_OK) return finish(r);
-            }
-            if (nunc) {
-                int32_t r = nx_crc32c_masked_batch(g.din.as<uint8_t>(), g.in_off.as<uint64_t>() + ncomp, g.in_len.as<uint32_t>() + ncomp,
-                                                   d_ucrc, nunc, g.s);
-                if (r != NX_OK) return finish(r);
-            }
-            ok = g.d2h(olen.data(), g.out_len.p, 4ull * ncomp) && g.d2h(cons.data(), d_cons, 4ull * ncomp) &&
-                 g.d2h(st.data(), d_st, 4ull * ncomp) && g.d2h(ucrc.data(), d_ucrc, 4ull * nunc) && g.sync();
-            if (!ok) return finish(NX_ERR_HIP);
-            // only the bytes each chunk produced cross PCIe (a message's olen, not its 64 KiB slot)
-            for (uint32_t j = 0; j < ncomp && ok; ++j) {
-                if (st[j] != NX_OK && st[j] != NX_ERR_SNAPPY_CRC_MISMATCH) continue;
-                outs[j].resize(olen[j]);
-                ok = g.d2h(outs[j].data(), g.dout.as<uint8_t>() + (size_t)j * 65536, olen[j]);
-            }
-            if (!g.sync() || !ok) return finish(NX_ERR_HIP);
+        // the items are the compressed chunks, a 64 KiB slot each; the raw chunks to CRC ride behind them
+        DecodeItems it(d->g, true);
+        std::vector<uint32_t> expect;
+        for (int i : comp_idx) {
+            it.add(acts[i].data - lo, acts[i].dlen, 65536);
+            expect.push_back(acts[i].crc);
         }
+        for (int i : unc_idx) it.add_job(acts[i].data - lo, acts[i].dlen);
+        const uint32_t ncomp = it.size(), nunc = it.jobs();
+        std::vector<std::vector<uint8_t>> outs(ncomp);  // each decoded chunk, exactly olen bytes
+        if (ncomp + nunc) {
+            int32_t r = it.stage(in + lo, hi - lo, nullptr, &expect);
+            if (r == NX_OK && ncomp)
+                r = nx_snappy_decode_batch(it.d_in(), it.d_in_off(), it.d_in_len(), it.d_out(), it.d_out_off(), nullptr, it.d_out_len(),
+                                           it.d_used(), it.d_status(), d->validate ? it.d_item_word() : nullptr, nullptr, ncomp, d->g.s);
+            if (r == NX_OK && nunc) r = nx_crc32c_masked_batch(it.d_in(), it.d_job_off(), it.d_job_len(), it.d_job_val(), nunc, d->g.s);
+            if (r != NX_OK) return call.finish(r);
+            if (!it.fetch()) return call.finish(NX_ERR_HIP);
+            // only the bytes each chunk produced cross PCIe (a message's olen, not its 64 KiB slot)
+            bool ok = true;
+            for (uint32_t j = 0; j < ncomp && ok; ++j) {
+                if (it.st[j] != NX_OK && it.st[j] != NX_ERR_SNAPPY_CRC_MISMATCH) continue;
+                outs[j].resize(it.len[j]);
+                ok = it.copy_item(j, outs[j].data());
+            }
+            if (!d->g.sync() || !ok) return call.finish(NX_ERR_HIP);
+        }
+        const std::vector<uint32_t>&olen = it.len, &cons = it.used, &ucrc = it.job_val;
+        const std::vector<int32_t>& st = it.st;
         // ---- apply in stream order (the first failing chunk ends the call, as the Java exception does)
         bool reparse = false;
         char buf[128];
         for (const SnappyAction& a : acts) {
-            if (a.kind == SAct::Error) return corrupt(a.end, NX_ERR_FRAME_CORRUPT, a.err);
-            if (a.kind == SAct::Stream) {
+            if (a.kind == SAct::Error) {
+                bad = {NX_ERR_FRAME_CORRUPT, a.err, a.end};
+            } else if (a.kind == SAct::Stream) {
                 d->started = true;
             } else if (a.kind == SAct::Uncomp) {
                 if (d->validate && ucrc[a.job] != a.crc) {  // :171-175
                     snprintf(buf, sizeof buf, "mismatching checksum: %x (expected: %x)", ucrc[a.job], a.crc);
-                    return corrupt(a.end, NX_ERR_SNAPPY_CRC_MISMATCH, buf);
+                    bad = {NX_ERR_SNAPPY_CRC_MISMATCH, buf, a.end};
+                } else {
+                    ml.msgs.push_back({in + a.data, a.dlen});  // readRetainedSlice: a view of the cumulation
                 }
-                ml.msgs.push_back({in + a.data, a.dlen});  // readRetainedSlice: a view of the cumulation
             } else if (a.kind == SAct::Comp) {
                 const int j = a.job;
                 if (st[j] == NX_ERR_SNAPPY_CRC_MISMATCH) {
                     snprintf(buf, sizeof buf, "mismatching checksum: %x (expected: %x)",
                              nx::host_mask(nx::host_crc32c(outs[j].data(), olen[j])), a.crc);
-                    return corrupt(a.end, st[j], buf);
-                }
-                if (st[j] != NX_OK)
-                    return corrupt(a.end, st[j], nx::fr::snappy_block_error(st[j], cons[j] >= 4 ? le32(in + a.data + cons[j] - 4) : 0u,
-                                                                           nx_status_string));
-                ml.owned.push_back(std::move(outs[j]));
-                ml.msgs.push_back({ml.owned.back().data(), olen[j]});
-                if (d->validate && cons[j] < a.dlen) {
-                    // validating mode restores the writer index and leaves the unread chunk bytes in
-                    // the cumulation (:206-212); they are parsed again as the next chunk header.
-                    rd = a.data + cons[j];
-                    d->skip = 0;
-                    reparse = true;
-                    break;
+                    bad = {st[j], buf, a.end};
+                } else if (st[j] != NX_OK) {
+                    bad = {st[j], nx::fr::snappy_block_error(st[j], cons[j] >= 4 ? le32(in + a.data + cons[j] - 4) : 0u, nx_status_string),
+                           a.end};
+                } else {
+                    ml.owned.push_back(std::move(outs[j]));
+                    ml.msgs.push_back({ml.owned.back().data(), olen[j]});
+                    if (d->validate && cons[j] < a.dlen) {
+                        // validating mode restores the writer index and leaves the unread chunk bytes in
+                        // the cumulation (:206-212); they are parsed again as the next chunk header.
+                        rd = a.data + cons[j];
+                        d->skip = 0;
+                        reparse = true;
+                        break;
+                    }
                 }
             }
+            if (bad.code != NX_OK) break;
             rd = a.end;
             d->skip = a.skip;
         }
         if (!reparse) break;
     }
-    return finish(NX_OK);
+    if (bad.code == NX_OK) return call.finish(NX_OK);
+    d->corrupted = true;  // :227-230
+    return call.fail(bad.code, bad.text, bad.at);
 }
 
 // ======================================================================= FastLZ frame encoder
@@ -407,10 +389,9 @@ struct FlzSync {
     static constexpr auto walk = nx::af::flz_walk;
     static constexpr bool kReadsOn = true;  // decompress may read past its chunk (in_avail = readable bytes)
     static size_t stage_end(size_t n, size_t, size_t) { return n; }
-    static int32_t decode(Gpu& g, uint32_t nz) {
-        return nx_fastlz_decompress_batch(g.din.as<uint8_t>(), g.in_off.as<uint64_t>(), g.in_len.as<uint32_t>(), g.aux0.as<uint32_t>(),
-                                          g.dout.as<uint8_t>(), g.out_off.as<uint64_t>(), g.out_len.as<uint32_t>(),
-                                          g.status.as<int32_t>(), nz, g.s);
+    static int32_t decode(const DecodeItems& it, uint32_t nz) {  // the item word: the bytes readable from the block on
+        return nx_fastlz_decompress_batch(it.d_in(), it.d_in_off(), it.d_in_len(), it.d_item_word(), it.d_out(), it.d_out_off(),
+                                          it.d_out_len(), it.d_status(), nz, it.g.s);
     }
     static bool block_error(int32_t r, const Blk& b, uint8_t first, int32_t* code, std::string* msg) {
         return nx::af::flz_block_error(r, b.olen, first, code, msg);
@@ -434,9 +415,9 @@ struct LzfSync {
     static constexpr auto walk = nx::af::lzf_walk;
     static constexpr bool kReadsOn = false;
     static size_t stage_end(size_t, size_t p, size_t) { return p; }
-    static int32_t decode(Gpu& g, uint32_t nz) {
-        return nx_lzf_decode_batch(g.din.as<uint8_t>(), g.in_off.as<uint64_t>(), g.in_len.as<uint32_t>(), g.dout.as<uint8_t>(),
-                                   g.out_off.as<uint64_t>(), g.out_len.as<uint32_t>(), g.status.as<int32_t>(), nz, g.s);
+    static int32_t decode(const DecodeItems& it, uint32_t nz) {
+        return nx_lzf_decode_batch(it.d_in(), it.d_in_off(), it.d_in_len(), it.d_out(), it.d_out_off(), it.d_out_len(), it.d_status(), nz,
+                                   it.g.s);
     }
     static bool block_error(int32_t st, const Blk&, uint8_t, int32_t* code, std::string* msg) {
         if (st == NX_OK) return false;
@@ -455,9 +436,9 @@ struct Lz4Sync {
     static constexpr auto walk = nx::af::lz4_walk;
     static constexpr bool kReadsOn = false;
     static size_t stage_end(size_t, size_t, size_t last_end) { return last_end; }
-    static int32_t decode(Gpu& g, uint32_t nz) {
-        return nx_lz4_decode_batch(g.din.as<uint8_t>(), g.in_off.as<uint64_t>(), g.in_len.as<uint32_t>(), g.dout.as<uint8_t>(),
-                                   g.out_off.as<uint64_t>(), g.out_len.as<uint32_t>(), g.status.as<int32_t>(), nz, g.s);
+    static int32_t decode(const DecodeItems& it, uint32_t nz) {
+        return nx_lz4_decode_batch(it.d_in(), it.d_in_off(), it.d_in_len(), it.d_out(), it.d_out_off(), it.d_out_len(), it.d_status(), nz,
+                                   it.g.s);
     }
     static bool block_error(int32_t st, const Blk&, uint8_t, int32_t* code, std::string* msg) {
         if (st == NX_OK) return false;  // LZ4Exception → DecompressionException (:240-241)
@@ -484,114 +465,74 @@ struct Lz4Sync {
 template <class C, class D>
 int32_t alt_decode(D* d, const uint8_t* in, size_t n, size_t* consumed, const nx_msg** msgs, size_t* n_msgs, const char** err_msg) {
     const nx::NoGrowScope no_grow;
-    if (!d || (!in && n) || !consumed || !msgs || !n_msgs) return NX_ERR_INVALID_ARG;
-    MsgList& ml = d->ml;
-    ml.clear();
-    auto finish = [&](int32_t r, size_t rd) {
-        *consumed = rd;
-        *msgs = ml.msgs.data();
-        *n_msgs = ml.msgs.size();
-        if (err_msg) *err_msg = ml.err.empty() ? nullptr : ml.err.c_str();
-        return r;
-    };
-    auto fail = [&](int32_t code, const std::string& msg, size_t rd) {  // the decoder turns CORRUPTED
-        ml.err = msg;
-        d->st.state = 3;
-        d->corrupted = true;
-        return finish(code, rd);
-    };
-    if (C::skips(*d)) return finish(NX_OK, n);
+    DecodeCall call(d, in, n, consumed, msgs, n_msgs, err_msg);
+    if (call.refused()) return NX_ERR_INVALID_ARG;
+    if (C::skips(*d)) return call.skip_all();
+    MsgList& ml = call.ml();
     // host parse (decode() as callDecode drives it) on a copy of the header state, committed at the end
     auto ns = d->st;
     std::vector<Blk> blks;
     nx::af::WalkErr werr;
     const size_t p = C::walk(in, n, ns, blks, werr);
     const uint32_t nb = (uint32_t)blks.size();
-    // decode jobs: every compressed block, into its 16-byte aligned slot of dout
-    std::vector<uint32_t> job(nb), cjob(nb);
-    std::vector<uint64_t> ooff;
-    uint64_t ocap = 0;
-    for (uint32_t i = 0; i < nb; ++i)
-        if (blks[i].comp) {
-            job[i] = (uint32_t)ooff.size();
-            ooff.push_back(ocap);
-            ocap += ((uint64_t)blks[i].olen + 15) & ~15ull;
-        }
-    const uint32_t nz = (uint32_t)ooff.size();
-    // checksum jobs: the decoded blocks first (their bytes in dout), then the raw ones (where they lie
-    // in the staged input, din)
     const size_t lo = nb ? blks.front().data : 0;
-    std::vector<uint64_t> coff;
-    std::vector<uint32_t> clen;
+    // the items: every compressed block, into its 16-byte aligned slot of dout
+    DecodeItems it(d->g, false);
+    std::vector<uint32_t> job(nb), cjob(nb), olen, iav;
+    for (uint32_t i = 0; i < nb; ++i) {
+        const Blk& b = blks[i];
+        if (!b.comp) continue;
+        job[i] = it.size();
+        it.add(b.data - lo, b.clen, ((uint64_t)b.olen + 15) & ~15ull);
+        olen.push_back(b.olen);
+        if (C::kReadsOn) iav.push_back((uint32_t)(n - b.data));
+    }
+    // the checksum jobs: the decoded blocks first (their bytes in dout), then the raw ones (where they lie
+    // in the staged input, din)
     uint32_t ncz = 0;
     for (int raw = 0; raw < 2; ++raw) {
         for (uint32_t i = 0; i < nb; ++i) {
             const Blk& b = blks[i];
             if (b.comp == (raw != 0) || !C::checked(*d, b)) continue;
-            cjob[i] = (uint32_t)coff.size();
-            coff.push_back(b.comp ? ooff[job[i]] : b.data - lo);
-            clen.push_back(b.comp ? b.olen : b.clen);
+            cjob[i] = it.jobs();
+            it.add_job(b.comp ? it.out_off[job[i]] : b.data - lo, b.comp ? b.olen : b.clen);
         }
-        if (!raw) ncz = (uint32_t)coff.size();
+        if (!raw) ncz = it.jobs();
     }
-    const uint32_t nck = (uint32_t)coff.size(), ncr = nck - ncz;
-    std::vector<int32_t> res(nz);
-    std::vector<uint32_t> cval(nck);
-    std::vector<uint8_t> hout(ocap);
-    Gpu& g = d->g;
-    if (nz || nck) {  // everything is uploaded before the first launch; one sync at the end
-        const size_t span = C::stage_end(n, p, blks.back().end) - lo;
-        std::vector<uint64_t> ioff(nz);
-        std::vector<uint32_t> ilen(nz), olen(nz), iav(C::kReadsOn ? nz : 0);
-        for (uint32_t i = 0; i < nb; ++i) {
-            const Blk& b = blks[i];
-            if (!b.comp) continue;
-            ioff[job[i]] = b.data - lo;
-            ilen[job[i]] = b.clen;
-            olen[job[i]] = b.olen;
-            if (C::kReadsOn) iav[job[i]] = (uint32_t)(n - b.data);
-        }
-        if (!g.din.ensure(span + 1) || !g.dout.ensure(ocap + 16) || !g.in_off.ensure(8ull * nz + 8) || !g.out_off.ensure(8ull * nz + 8) ||
-            !g.in_len.ensure(4ull * nz + 4) || !g.out_len.ensure(4ull * nz + 4) || !g.status.ensure(4ull * nz + 4) ||
-            !g.aux0.ensure(4ull * iav.size()) || !g.aux1.ensure(16ull * nck))
-            return finish(NX_ERR_HIP, 0);
-        // aux0: FastLZ's readable bytes per block; aux1: the checksum jobs' offsets, lengths and values
-        uint64_t* d_coff = g.aux1.as<uint64_t>();
-        uint32_t* d_clen = reinterpret_cast<uint32_t*>(d_coff + nck);
-        uint32_t* d_cval = d_clen + nck;
-        bool ok = g.h2d(g.din.p, in + lo, span) && g.h2d(g.in_off.p, ioff.data(), 8ull * nz) &&
-                  g.h2d(g.out_off.p, ooff.data(), 8ull * nz) && g.h2d(g.in_len.p, ilen.data(), 4ull * nz) &&
-                  g.h2d(g.out_len.p, olen.data(), 4ull * nz) && g.h2d(g.aux0.p, iav.data(), 4ull * iav.size()) &&
-                  g.h2d(d_coff, coff.data(), 8ull * nck) && g.h2d(d_clen, clen.data(), 4ull * nck);
-        if (!ok) return finish(NX_ERR_HIP, 0);
-        int32_t r = nz ? C::decode(g, nz) : NX_OK;
-        if (r == NX_OK && ncz) r = C::checksum(g.dout.as<uint8_t>(), d_coff, d_clen, d_cval, ncz, g.s);
-        if (r == NX_OK && ncr) r = C::checksum(g.din.as<uint8_t>(), d_coff + ncz, d_clen + ncz, d_cval + ncz, ncr, g.s);
-        if (r != NX_OK) return finish(r, 0);
-        ok = g.d2h(res.data(), g.status.p, 4ull * nz) && g.d2h(hout.data(), g.dout.p, ocap) && g.d2h(cval.data(), d_cval, 4ull * nck) &&
-             g.sync();
-        if (!ok) return finish(NX_ERR_HIP, 0);
+    const uint32_t nz = it.size(), ncr = it.jobs() - ncz;
+    std::vector<uint8_t> hout(it.out_bytes);
+    if (nz || it.jobs()) {  // everything is uploaded before the first launch; one sync at the end
+        int32_t r = it.stage(in + lo, C::stage_end(n, p, blks.back().end) - lo, &olen, C::kReadsOn ? &iav : nullptr);
+        if (r == NX_OK && nz) r = C::decode(it, nz);
+        if (r == NX_OK && ncz) r = C::checksum(it.d_out(), it.d_job_off(), it.d_job_len(), it.d_job_val(), ncz, d->g.s);
+        if (r == NX_OK && ncr) r = C::checksum(it.d_in(), it.d_job_off(ncz), it.d_job_len(ncz), it.d_job_val(ncz), ncr, d->g.s);
+        if (r != NX_OK) return call.finish(r);
+        if (!it.fetch(hout.data())) return call.finish(NX_ERR_HIP);
     }
     // apply in stream order: a block's failure, then its checksum, then its message
+    Failure bad;
     for (uint32_t i = 0; i < nb; ++i) {
         const Blk& b = blks[i];
-        int32_t code = NX_OK;
-        std::string emsg;
-        size_t at = 0;
-        if (b.comp && C::block_error(res[job[i]], b, b.data < n ? in[b.data] : 0, &code, &emsg)) return fail(code, emsg, b.data);
-        if (C::checked(*d, b) && C::checksum_error(cval[cjob[i]], b, &code, &emsg, &at)) return fail(code, emsg, at);
+        if (b.comp && C::block_error(it.st[job[i]], b, b.data < n ? in[b.data] : 0, &bad.code, &bad.text)) bad.at = b.data;
+        if (bad.code != NX_OK || (C::checked(*d, b) && C::checksum_error(it.job_val[cjob[i]], b, &bad.code, &bad.text, &bad.at))) break;
         if (!C::emits(b)) continue;
         if (b.comp) {  // decoded bytes are owned by the message list; a raw block is a view of `in`
-            const uint8_t* data = hout.data() + ooff[job[i]];
+            const uint8_t* data = hout.data() + it.out_off[job[i]];
             ml.owned.emplace_back(data, data + b.olen);
             ml.msgs.push_back({ml.owned.back().data(), b.olen});
         } else {
             ml.msgs.push_back({in + b.data, b.clen});
         }
     }
-    if (werr.set) return fail(werr.code, werr.msg, werr.at);
+    if (bad.code == NX_OK && werr.set) bad = {werr.code, werr.msg, werr.at};
+    if (bad.code != NX_OK) {  // the decoder turns CORRUPTED
+        d->st.state = 3;
+        d->corrupted = true;
+        return call.fail(bad.code, bad.text, bad.at);
+    }
     d->st = ns;
-    return finish(NX_OK, p);
+    call.rd = p;
+    return call.finish(NX_OK);
 }
 }  // namespace
 
@@ -923,18 +864,15 @@ int64_t bzip2_segment(nx_bzip2_encoder* e, const uint8_t* data, size_t len, uint
         nx_bzip2_seg seg;
     } p = {0, 0, (uint32_t)len, (uint32_t)cap, 0, 0, e->seg};
     p.seg.flags = last ? NX_BZIP2_SEG_LAST : 0u;
-    DevBuf& par = g.aux0;  // the one item's arrays, uploaded and read back whole
-    if (!g.din.ensure(len ? len : 1u) || !g.dout.ensure(cap) || !par.ensure(sizeof p)) return NX_ERR_HIP;
-    if (!g.h2d(g.din.p, data, len) || !g.h2d(par.p, &p, sizeof p)) return NX_ERR_HIP;
-    uint8_t* P = par.as<uint8_t>();
-    const int32_t r = nx_bzip2_encode_batch_split(g.din.as<uint8_t>(), (const uint64_t*)(P + offsetof(Par, in_off)),
-                                                  (const uint32_t*)(P + offsetof(Par, in_len)), g.dout.as<uint8_t>(),
-                                                  (const uint64_t*)(P + offsetof(Par, out_off)), (const uint32_t*)(P + offsetof(Par, out_cap)),
-                                                  (uint32_t*)(P + offsetof(Par, out_len)), (int32_t*)(P + offsetof(Par, status)), 1, e->level,
-                                                  blocks, (nx_bzip2_seg*)(P + offsetof(Par, seg)), g.s);
+    const ParamBlock<Par> P(g, g.aux0);  // the one item's arrays, uploaded and read back whole
+    if (!g.din.ensure(len ? len : 1u) || !g.dout.ensure(cap) || !P.ensure()) return NX_ERR_HIP;
+    if (!g.h2d(g.din.p, data, len) || !P.upload(p)) return NX_ERR_HIP;
+    const int32_t r = nx_bzip2_encode_batch_split(g.din.as<uint8_t>(), P.field(&Par::in_off), P.field(&Par::in_len), g.dout.as<uint8_t>(),
+                                                  P.field(&Par::out_off), P.field(&Par::out_cap), P.field(&Par::out_len),
+                                                  P.field(&Par::status), 1, e->level, blocks, P.field(&Par::seg), g.s);
     if (r != NX_OK) return r;
     e->launches += 1;
-    if (!g.d2h(&p, par.p, sizeof p) || !g.sync()) return NX_ERR_HIP;
+    if (!P.download(p, &Par::in_off) || !g.sync()) return NX_ERR_HIP;
     if (p.status != NX_OK) return p.status;
     if (p.out_len > out_cap) return NX_ERR_INVALID_ARG;
     if (!g.d2h(out, g.dout.p, p.out_len) || !g.sync()) return NX_ERR_HIP;
@@ -1048,17 +986,10 @@ extern "C" int32_t nx_zstd_decoder_stats(const nx_zstd_decoder* d, uint64_t* lau
 extern "C" int32_t nx_zstd_decoder_decode(nx_zstd_decoder* d, const uint8_t* in, size_t n, size_t* consumed, const nx_msg** msgs,
                                           size_t* n_msgs, const char** err_msg) {
     const nx::NoGrowScope no_grow;
-    if (!d || (!in && n) || !consumed || !msgs || !n_msgs) return NX_ERR_INVALID_ARG;
-    MsgList& ml = d->ml;
-    ml.clear();
-    *consumed = 0;
-    *msgs = nullptr;
-    *n_msgs = 0;
-    if (err_msg) *err_msg = nullptr;
-    if (d->corrupted) {  // :71-75: in.skipBytes(in.readableBytes())
-        *consumed = n;
-        return NX_OK;
-    }
+    DecodeCall call(d, in, n, consumed, msgs, n_msgs, err_msg);
+    if (call.refused()) return NX_ERR_INVALID_ARG;
+    if (d->corrupted) return call.skip_all();  // :71-75: in.skipBytes(in.readableBytes())
+    MsgList& ml = call.ml();
     // the walk: skippable frames are stepped over, complete frames become items, a frame the input ends
     // inside stops it; `fail` is the status of the first frame the walker refuses
     constexpr uint64_t kMaxBound = 128ull << 20, kMaxFrameBytes = 0x7FFFFFFFull;  // the kernel's positions and lengths
@@ -1087,57 +1018,51 @@ extern "C" int32_t nx_zstd_decoder_decode(nx_zstd_decoder* d, const uint8_t* in,
     if (!items.empty()) {
         // one copy of the bytes and one of the items' geometry in, one launch, one copy back: the device
         // output starts with the three result arrays, the slots follow
+        using nx::h::ZstdGeometry;
+        using nx::h::ZstdResults;
         Gpu& g = d->g;
         const uint32_t nb = (uint32_t)items.size();
-        const size_t res = ((size_t)12 * nb + 15) / 16 * 16;
+        const size_t res = ZstdResults::bytes(nb);
         const size_t bytes = (size_t)items.back().in_off + items.back().in_len;
-        std::vector<uint64_t> par(3ull * nb);  // in_off, out_off, then in_len and out_cap (32 bits each)
-        uint32_t* par32 = reinterpret_cast<uint32_t*>(par.data() + 2ull * nb);
+        std::vector<uint64_t> par(ZstdGeometry::bytes(nb) / 8);
+        const ZstdGeometry hg(par.data(), nb);
         for (uint32_t i = 0; i < nb; ++i) {
-            par[i] = items[i].in_off;
-            par[nb + i] = res + items[i].out_off;
-            par32[i] = items[i].in_len;
-            par32[nb + i] = items[i].out_cap;
+            hg.in_off[i] = items[i].in_off;
+            hg.out_off[i] = res + items[i].out_off;
+            hg.in_len[i] = items[i].in_len;
+            hg.out_cap[i] = items[i].out_cap;
         }
-        DevBuf& geom = g.aux0;  // the four geometry arrays, packed as `par` is
-        if (!g.din.ensure(bytes) || !geom.ensure(24ull * nb) || !g.dout.ensure(res + oc)) return NX_ERR_HIP;
-        if (!g.h2d(g.din.p, in, bytes) || !g.h2d(geom.p, par.data(), 24ull * nb)) return NX_ERR_HIP;
-        const uint64_t* dpar = geom.as<uint64_t>();
-        const uint32_t* dpar32 = reinterpret_cast<const uint32_t*>(dpar + 2ull * nb);
-        uint32_t* dres = g.dout.as<uint32_t>();
-        const int32_t r = nx_zstd_decode_batch_ex(g.din.as<uint8_t>(), dpar, dpar32, g.dout.as<uint8_t>(), dpar + nb, dpar32 + nb, dres,
-                                                  dres + nb, reinterpret_cast<int32_t*>(dres + 2ull * nb), nb,
-                                                  NX_ZSTD_DECODE_VERIFY_CHECKSUM, g.s);
-        if (r != NX_OK) return r;
+        DevBuf& geom = g.aux0;
+        if (!g.din.ensure(bytes) || !geom.ensure(ZstdGeometry::bytes(nb)) || !g.dout.ensure(res + oc)) return call.finish(NX_ERR_HIP);
+        if (!g.h2d(g.din.p, in, bytes) || !g.h2d(geom.p, par.data(), ZstdGeometry::bytes(nb))) return call.finish(NX_ERR_HIP);
+        const ZstdGeometry dg(geom.p, nb);
+        const ZstdResults dr(g.dout.p, nb);
+        const int32_t r = nx_zstd_decode_batch_ex(g.din.as<uint8_t>(), dg.in_off, dg.in_len, g.dout.as<uint8_t>(), dg.out_off, dg.out_cap,
+                                                  dr.consumed, dr.out_len, dr.status, nb, NX_ZSTD_DECODE_VERIFY_CHECKSUM, g.s);
+        if (r != NX_OK) return call.finish(r);
         d->back.resize(res + oc);
-        if (!g.d2h(d->back.data(), g.dout.p, res + oc) || !g.sync()) return NX_ERR_HIP;
+        if (!g.d2h(d->back.data(), g.dout.p, res + oc) || !g.sync()) return call.finish(NX_ERR_HIP);
         d->launches += 1;
         d->frames += nb;
-        const uint32_t* out_len = reinterpret_cast<const uint32_t*>(d->back.data()) + nb;
-        const int32_t* status = reinterpret_cast<const int32_t*>(d->back.data()) + 2ull * nb;
+        const ZstdResults hr(d->back.data(), nb);
         for (uint32_t i = 0; i < nb; ++i) {
-            if (status[i] != NX_OK) {  // the first failing frame: what the walker found later comes after it
-                fail = status[i];
+            if (hr.status[i] != NX_OK) {  // the first failing frame: what the walker found later comes after it
+                fail = hr.status[i];
                 break;
             }
             // :99-110: buffers of min(maximumAllocationSize, uncompressedLength), fired while readable
             const uint8_t* o = d->back.data() + res + items[i].out_off;
-            const size_t len = out_len[i] <= items[i].out_cap ? out_len[i] : items[i].out_cap;
+            const size_t len = hr.out_len[i] <= items[i].out_cap ? hr.out_len[i] : items[i].out_cap;
             const size_t piece = d->max_alloc > 0 ? (size_t)d->max_alloc : len;
             for (size_t at = 0; at < len; at += piece) ml.msgs.push_back({o + at, len - at < piece ? len - at : piece});
         }
     }
-    *msgs = ml.msgs.data();
-    *n_msgs = ml.msgs.size();
     if (fail != NX_OK) {  // :116-118: CORRUPTED, the exception's text is libzstd's for the error
         d->corrupted = true;
-        ml.err = nx_status_string(fail);
-        if (err_msg) *err_msg = ml.err.c_str();
-        *consumed = n;
-        return fail;
+        return call.fail(fail, nx_status_string(fail), n);
     }
-    *consumed = pos;
-    return NX_OK;
+    call.rd = pos;
+    return call.finish(NX_OK);
 }
 
 extern "C" nx_lz4_frame_decoder* nx_lz4_frame_decoder_new(int32_t validate_checksums) {
@@ -1340,14 +1265,6 @@ uint32_t crc32_host(uint32_t crc, const uint8_t* p, size_t n) {
     return ~crc;
 }
 
-struct ZPar {  // the launch's arguments and results, one small copy each way
-    uint64_t in_off, out_off, sum_off;
-    uint32_t in_len, hist_len, out_cap;
-    uint32_t consumed, out_len;
-    int32_t status;
-    uint32_t sum;
-};
-
 enum { kZNeed = 0, kZOk = 1 };  // (< 0: failed, ml.err holds the message)
 
 // readGZIPHeader (:343-433), state for state.  xlen starts at -1 and the two length bytes are OR-ed
@@ -1467,7 +1384,7 @@ extern "C" nx_zlib_decoder* nx_zlib_decoder_new(int32_t wrapper, int32_t decompr
     if (wrapper < 0 || wrapper > 3 || max_allocation < 0) return nullptr;  // checkPositiveOrZero (ZlibDecoder.java:49)
     auto* d = new nx_zlib_decoder();
     if (!d->g.ok || !d->win[0].ensure(kZlibHist + kZlibChunk) || !d->win[1].ensure(kZlibHist + kZlibChunk) ||
-        !d->st.ensure(NX_INFLATE_STATE_BYTES) || !d->par.ensure(sizeof(ZPar)) ||
+        !d->st.ensure(NX_INFLATE_STATE_BYTES) || !d->par.ensure(sizeof(nx::h::ZlibLaunch)) ||
         hipMemsetAsync(d->st.p, 0, NX_INFLATE_STATE_BYTES, d->g.s) != hipSuccess || !d->g.sync()) {
         delete d;
         return nullptr;
@@ -1652,28 +1569,12 @@ int body_result(nx_zlib_decoder* d, Call& c, uint32_t consumed, uint32_t m, int3
 }  // namespace zl
 }  // namespace nx
 
-extern "C" int32_t nx_zlib_decoder_decode(nx_zlib_decoder* d, const uint8_t* in, size_t n, size_t* consumed, const nx_msg** msgs,
-                                          size_t* n_msgs, const char** err_msg) {
-    const nx::NoGrowScope no_grow;
-    if (!d || (!in && n) || !consumed || !msgs || !n_msgs) return NX_ERR_INVALID_ARG;
-    if (d->owner.load()) return NX_ERR_INVALID_ARG;  // a batcher decoder stays a batcher decoder
+namespace {
+// The synchronous driver of those steps: the status of the call, with c.rd, c.err and c.acc left for the frame.
+int32_t zlib_sync_steps(nx_zlib_decoder* d, nx::zl::Call& c) {
     namespace zl = nx::zl;
-    MsgList& ml = d->ml;
-    ml.clear();
+    using nx::h::ZlibLaunch;
     Gpu& g = d->g;
-    zl::Call c;
-    c.in = in;
-    c.n = n;
-    auto finish = [&](int32_t r) {
-        ml.err = c.err;
-        if (!c.acc.empty()) ml.owned.push_back(std::move(c.acc));
-        for (auto& o : ml.owned) ml.msgs.push_back({o.data(), o.size()});
-        *consumed = c.rd;
-        *msgs = ml.msgs.data();
-        *n_msgs = ml.msgs.size();
-        if (err_msg) *err_msg = ml.err.empty() ? nullptr : ml.err.c_str();
-        return r;
-    };
     struct SyncIo : zl::BodyIo {  // the launch's bytes come by a copy of their own; the carry is a device copy
         nx_zlib_decoder* d;
         bool take(uint8_t* dst, uint32_t m) override {
@@ -1693,47 +1594,64 @@ extern "C" int32_t nx_zlib_decoder_decode(nx_zlib_decoder* d, const uint8_t* in,
         }
     } io;
     io.d = d;
+    const ParamBlock<ZlibLaunch> P(g, d->par);
     bool uploaded = false;  // the cumulation is copied to the device once, when a body needs it
     int step = zl::kWrapper;
     for (;;) {
         if (step == zl::kWrapper) step = zl::wrapper_step(d, c);
         if (step != zl::kBody) break;
         if (!uploaded) {
-            if (!g.din.ensure(n) || !g.h2d(g.din.p, in, n)) return finish(NX_ERR_HIP);
+            if (!g.din.ensure(c.n) || !g.h2d(g.din.p, c.in, c.n)) return NX_ERR_HIP;
             uploaded = true;
         }
         if (d->st_fresh) {  // inflater.reset() (:321): a new member starts from the all-zero state
-            if (hipMemsetAsync(d->st.p, 0, NX_INFLATE_STATE_BYTES, g.s) != hipSuccess) return finish(NX_ERR_HIP);
+            if (hipMemsetAsync(d->st.p, 0, NX_INFLATE_STATE_BYTES, g.s) != hipSuccess) return NX_ERR_HIP;
             d->st_fresh = false;
         }
         uint8_t* W = d->win[d->cur].as<uint8_t>();
-        ZPar p{};
+        ZlibLaunch p{};
         p.in_off = c.rd;
-        p.in_len = (uint32_t)(n - c.rd < 0x7FFFFFFFu ? n - c.rd : 0x7FFFFFFFu);
+        p.in_len = (uint32_t)(c.n - c.rd < 0x7FFFFFFFu ? c.n - c.rd : 0x7FFFFFFFu);
         p.out_off = kZlibHist - d->hist;
         p.hist_len = d->hist;
         p.out_cap = kZlibChunk;
         p.sum_off = kZlibHist;
-        uint8_t* P = d->par.as<uint8_t>();
-        if (!g.h2d(P, &p, offsetof(ZPar, consumed))) return finish(NX_ERR_HIP);
-        int32_t r = nx_inflate_batch(g.din.as<uint8_t>(), (const uint64_t*)(P + offsetof(ZPar, in_off)),
-                                     (const uint32_t*)(P + offsetof(ZPar, in_len)), W, (const uint64_t*)(P + offsetof(ZPar, out_off)),
-                                     (const uint32_t*)(P + offsetof(ZPar, hist_len)), (const uint32_t*)(P + offsetof(ZPar, out_cap)),
-                                     d->st.as<uint8_t>(), (uint32_t*)(P + offsetof(ZPar, consumed)),
-                                     (uint32_t*)(P + offsetof(ZPar, out_len)), (int32_t*)(P + offsetof(ZPar, status)), 1, g.s);
-        if (r != NX_OK) return finish(r);
+        if (!P.upload(p, nx::h::field_offset(&ZlibLaunch::consumed))) return NX_ERR_HIP;  // the arguments: up to the first result
+        int32_t r = nx_inflate_batch(g.din.as<uint8_t>(), P.field(&ZlibLaunch::in_off), P.field(&ZlibLaunch::in_len), W,
+                                     P.field(&ZlibLaunch::out_off), P.field(&ZlibLaunch::hist_len), P.field(&ZlibLaunch::out_cap),
+                                     d->st.as<uint8_t>(), P.field(&ZlibLaunch::consumed), P.field(&ZlibLaunch::out_len),
+                                     P.field(&ZlibLaunch::status), 1, g.s);
+        if (r != NX_OK) return r;
         if (d->gzip || d->zlib) {  // the checksum of what this launch produced (crc.update, :265-267)
             auto sum = d->gzip ? nx_crc32_batch : nx_adler32_batch;
-            r = sum(W, (const uint64_t*)(P + offsetof(ZPar, sum_off)), (const uint32_t*)(P + offsetof(ZPar, out_len)),
-                    (uint32_t*)(P + offsetof(ZPar, sum)), 1, g.s);
-            if (r != NX_OK) return finish(r);
+            r = sum(W, P.field(&ZlibLaunch::sum_off), P.field(&ZlibLaunch::out_len), P.field(&ZlibLaunch::sum), 1, g.s);
+            if (r != NX_OK) return r;
         }
-        if (!g.d2h(&p.consumed, P + offsetof(ZPar, consumed), sizeof(ZPar) - offsetof(ZPar, consumed)) || !g.sync())
-            return finish(NX_ERR_HIP);
+        if (!P.download(p, &ZlibLaunch::consumed) || !g.sync()) return NX_ERR_HIP;
         step = zl::body_result(d, c, p.consumed, p.out_len, p.status, p.sum, io);
-        if (step <= zl::kHalt) return finish(step - zl::kHalt);  // the launch itself failed: the decoder is as it was
+        if (step <= zl::kHalt) return step - zl::kHalt;  // the launch itself failed: the decoder is as it was
     }
-    return finish(step < 0 ? step : NX_OK);
+    return step < 0 ? step : NX_OK;
+}
+}  // namespace
+
+extern "C" int32_t nx_zlib_decoder_decode(nx_zlib_decoder* d, const uint8_t* in, size_t n, size_t* consumed, const nx_msg** msgs,
+                                          size_t* n_msgs, const char** err_msg) {
+    const nx::NoGrowScope no_grow;
+    if (d && d->owner.load()) return NX_ERR_INVALID_ARG;  // a batcher decoder stays a batcher decoder
+    DecodeCall call(d, in, n, consumed, msgs, n_msgs, err_msg);
+    if (call.refused()) return NX_ERR_INVALID_ARG;
+    nx::zl::Call c;
+    c.in = in;
+    c.n = n;
+    const int32_t r = zlib_sync_steps(d, c);
+    // the call's messages: each launch's bytes, or with maxAllocation the one accumulated buffer
+    MsgList& ml = call.ml();
+    ml.err = c.err;
+    if (!c.acc.empty()) ml.owned.push_back(std::move(c.acc));
+    for (auto& o : ml.owned) ml.msgs.push_back({o.data(), o.size()});
+    call.rd = c.rd;
+    return call.finish(r);
 }
 
 // ------------------------------------------------------------------ Bzip2Decoder
@@ -1753,36 +1671,36 @@ extern "C" int32_t nx_bzip2_decoder_stats(const nx_bzip2_decoder* d, uint64_t* l
     return NX_OK;
 }
 
+namespace {
+// the first failing block: the decoder swallows what follows, the exception's text is the status's
+int32_t bzip2_corrupt(nx_bzip2_decoder* d, DecodeCall& call, int32_t st) {
+    d->corrupted = true;
+    return call.fail(st, nx_status_string(st), call.n);
+}
+// where, in the lists' memory, the part that is copied back begins
+size_t split_lists_back_offset(const nx::bz2d::SplitLists& S) {
+    return (size_t)(reinterpret_cast<const uint8_t*>(S.first) - static_cast<const uint8_t*>(S.mem));
+}
+}  // namespace
+
 extern "C" int32_t nx_bzip2_decoder_decode(nx_bzip2_decoder* d, const uint8_t* in, size_t n, size_t* consumed, const nx_msg** msgs,
                                            size_t* n_msgs, const char** err_msg) {
     using namespace nx::bz2d;
+    using nx::h::Bzip2Geom;
+    using nx::h::Bzip2Result;
+    using nx::h::Bzip2Scan;
     const nx::NoGrowScope no_grow;
-    if (!d || (!in && n) || !consumed || !msgs || !n_msgs) return NX_ERR_INVALID_ARG;
-    MsgList& ml = d->ml;
-    ml.clear();
-    *consumed = 0;
-    *msgs = nullptr;
-    *n_msgs = 0;
-    if (err_msg) *err_msg = nullptr;
-    if (d->closed || d->corrupted) {  // :328-330 in.skipBytes(in.readableBytes()); after an error: this handle's own state
-        *consumed = n;
-        return NX_OK;
-    }
-    auto fail = [&](int32_t st) {
-        d->corrupted = true;
-        ml.err = nx_status_string(st);
-        if (err_msg) *err_msg = ml.err.c_str();
-        *msgs = ml.msgs.data();
-        *n_msgs = ml.msgs.size();
-        *consumed = n;
-        return st;
-    };
-    size_t pos = 0;
+    DecodeCall call(d, in, n, consumed, msgs, n_msgs, err_msg);
+    if (call.refused()) return NX_ERR_INVALID_ARG;
+    // :328-330 in.skipBytes(in.readableBytes()); after an error: this handle's own state
+    if (d->closed || d->corrupted) return call.skip_all();
+    MsgList& ml = call.ml();
+    size_t& pos = call.rd;
     if (!d->have_header) {  // :101-119
-        if (n < 4) return NX_OK;
+        if (n < 4) return call.finish(NX_OK);
         uint32_t level = 0;
         const int32_t st = stream_header(in, 4, &level);
-        if (st != NX_OK) return fail(st);
+        if (st != NX_OK) return bzip2_corrupt(d, call, st);
         d->have_header = true;
         d->level = level;
         d->crc = 0;
@@ -1790,63 +1708,58 @@ extern "C" int32_t nx_bzip2_decoder_decode(nx_bzip2_decoder* d, const uint8_t* i
         d->seen_after = 0;
         pos = 4;
     }
-    *consumed = pos;
     constexpr size_t kMaxCumulation = 0x7fffffffu;
     const size_t rem = n - pos < kMaxCumulation ? n - pos : kMaxCumulation;
-    if (8ull * rem < d->bit_used + 80ull) return NX_OK;  // not even a magic and a CRC
+    if (8ull * rem < d->bit_used + 80ull) return call.finish(NX_OK);  // not even a magic and a CRC
     Gpu& g = d->g;
     // the scan, and its list back: what stands in the received bytes decides whether anything is attempted
     const uint32_t scan_cap = (uint32_t)(rem / 6 + 2);
-    if (!g.din.ensure(rem + 16) || !g.aux1.ensure(8ull * scan_cap + 64) || !g.in_off.ensure(64) || !g.status.ensure(64)) return NX_ERR_HIP;
-    struct Geom {
-        uint64_t in_off, out_off;
-        uint32_t in_len, out_cap;
-        SplitStart start;
-    } geom = {0, 0, (uint32_t)rem, 0, {d->bit_used, d->crc, d->level, d->seen_after, 0}};
-    if (!g.h2d(g.din.p, in + pos, rem) || !g.h2d(g.in_off.p, &geom, sizeof geom)) return NX_ERR_HIP;
-    const uint8_t* dgeom = g.in_off.as<uint8_t>();
-    uint32_t* dscan = g.status.as<uint32_t>();  // first, count, status
-    int32_t r = nx_bzip2_scan_batch(g.din.as<uint8_t>(), reinterpret_cast<const uint64_t*>(dgeom),
-                                    reinterpret_cast<const uint32_t*>(dgeom + 16), 1, scan_cap, g.aux1.as<uint64_t>(), dscan, dscan + 1,
-                                    reinterpret_cast<int32_t*>(dscan + 2), g.s);
-    if (r != NX_OK) return r;
-    uint32_t scan[3] = {0, 0, 0};
-    if (!g.d2h(scan, dscan, 12) || !g.sync()) return NX_ERR_HIP;
-    if ((int32_t)scan[2] != NX_OK) return NX_ERR_INTERNAL;  // (six bytes a magic: scan_cap always suffices for distinct magics)
-    const uint32_t count = scan[1];
+    const ParamBlock<Bzip2Geom> G(g, g.in_off);
+    const ParamBlock<Bzip2Scan> S0(g, g.status);
+    if (!g.din.ensure(rem + 16) || !g.aux1.ensure(8ull * scan_cap + 64) || !G.ensure() || !S0.ensure()) return call.finish(NX_ERR_HIP);
+    Bzip2Geom geom = {0, 0, (uint32_t)rem, 0, {d->bit_used, d->crc, d->level, d->seen_after, 0}};
+    if (!g.h2d(g.din.p, in + pos, rem) || !G.upload(geom)) return call.finish(NX_ERR_HIP);
+    int32_t r = nx_bzip2_scan_batch(g.din.as<uint8_t>(), G.field(&Bzip2Geom::in_off), G.field(&Bzip2Geom::in_len), 1, scan_cap,
+                                    g.aux1.as<uint64_t>(), S0.field(&Bzip2Scan::first), S0.field(&Bzip2Scan::count),
+                                    S0.field(&Bzip2Scan::status), g.s);
+    if (r != NX_OK) return call.finish(r);
+    Bzip2Scan scan = {0, 0, 0};
+    if (!S0.download(scan, &Bzip2Scan::first) || !g.sync()) return call.finish(NX_ERR_HIP);
+    if (scan.status != NX_OK) return call.finish(NX_ERR_INTERNAL);  // (six bytes a magic: scan_cap always suffices for distinct magics)
+    const uint32_t count = scan.count;
     std::vector<uint64_t> cand(count);
-    if (count && (!g.d2h(cand.data(), g.aux1.p, 8ull * count) || !g.sync())) return NX_ERR_HIP;
+    if (count && (!g.d2h(cand.data(), g.aux1.p, 8ull * count) || !g.sync())) return call.finish(NX_ERR_HIP);
     uint32_t head = 0;
     while (head < count && (cand[head] & kCandPos) < d->bit_used) head += 1;
     const bool at_head = head < count && (cand[head] & kCandPos) == d->bit_used;
     if (!at_head) {
         // neither magic where the next block must stand: "bad block header" once its 48 bits are all there
         // (the reference looks after ten bytes, :122-140)
-        return fail(NX_ERR_BZIP2_BLOCK_HEADER);
+        return bzip2_corrupt(d, call, NX_ERR_BZIP2_BLOCK_HEADER);
     }
-    if (!(cand[head] & kCandEnd) && count - 1u - head <= d->seen_after) return NX_OK;  // the block is still arriving
+    if (!(cand[head] & kCandEnd) && count - 1u - head <= d->seen_after) return call.finish(NX_OK);  // the block is still arriving
     // one decode sequence over the chain head and every candidate; the output slot grows if the blocks need it
     uint64_t cap = (uint64_t)count * d->level * kBaseBlock + 65536;
     SplitLists S;
     const size_t lists_bytes = split_lists_layout(S, nullptr, 1, count, true);
-    if (!g.aux0.ensure(lists_bytes) || !g.out_len.ensure(64)) return NX_ERR_HIP;
+    const ParamBlock<Bzip2Result> R(g, g.out_len);
+    if (!g.aux0.ensure(lists_bytes) || !R.ensure()) return call.finish(NX_ERR_HIP);
     split_lists_layout(S, g.aux0.p, 1, count, true);
-    const size_t back_off = (size_t)(reinterpret_cast<uint8_t*>(S.first) - static_cast<uint8_t*>(g.aux0.p));
+    const size_t back_off = split_lists_back_offset(S);  // what comes back starts at the items' `first` words
     const size_t back_bytes = lists_bytes - back_off;
     SplitLists H;  // the same layout over the host copy
     const SplitItem* I = nullptr;
     for (int attempt = 0;; ++attempt) {
         if (cap > 0xffffffffull) cap = 0xffffffffull;
         geom.out_cap = (uint32_t)cap;
-        if (!g.dout.ensure(cap) || !g.h2d(g.in_off.p, &geom, sizeof geom)) return NX_ERR_HIP;
-        uint32_t* dres = g.out_len.as<uint32_t>();  // out_len, consumed, status, blocks
-        r = decode_split_launch(g.din.as<uint8_t>(), reinterpret_cast<const uint64_t*>(dgeom), reinterpret_cast<const uint32_t*>(dgeom + 16),
-                                g.dout.as<uint8_t>(), reinterpret_cast<const uint64_t*>(dgeom + 8),
-                                reinterpret_cast<const uint32_t*>(dgeom + 20), dres, dres + 1, reinterpret_cast<int32_t*>(dres + 2), 1, count,
-                                dres + 3, reinterpret_cast<const SplitStart*>(dgeom + 24), g.aux0.p, g.s);
-        if (r != NX_OK) return r;
+        if (!g.dout.ensure(cap) || !G.upload(geom)) return call.finish(NX_ERR_HIP);
+        r = decode_split_launch(g.din.as<uint8_t>(), G.field(&Bzip2Geom::in_off), G.field(&Bzip2Geom::in_len), g.dout.as<uint8_t>(),
+                                G.field(&Bzip2Geom::out_off), G.field(&Bzip2Geom::out_cap), R.field(&Bzip2Result::out_len),
+                                R.field(&Bzip2Result::consumed), R.field(&Bzip2Result::status), 1, count, R.field(&Bzip2Result::blocks),
+                                G.field(&Bzip2Geom::start), g.aux0.p, g.s);
+        if (r != NX_OK) return call.finish(r);
         d->lists.resize(lists_bytes);
-        if (!g.d2h(d->lists.data() + back_off, static_cast<uint8_t*>(g.aux0.p) + back_off, back_bytes) || !g.sync()) return NX_ERR_HIP;
+        if (!g.d2h(d->lists.data() + back_off, g.aux0.as<uint8_t>() + back_off, back_bytes) || !g.sync()) return call.finish(NX_ERR_HIP);
         d->launches += 1;
         split_lists_layout(H, d->lists.data(), 1, count, true);
         I = H.items;
@@ -1881,24 +1794,19 @@ extern "C" int32_t nx_bzip2_decoder_decode(nx_bzip2_decoder* d, const uint8_t* i
     d->attempted += members + (front_answer ? 1u : 0u);
     d->emitted += pieces.size();
     d->back.resize(total);
-    if (total && (!g.d2h(d->back.data(), g.dout.p, total) || !g.sync())) return NX_ERR_HIP;
+    if (total && (!g.d2h(d->back.data(), g.dout.p, total) || !g.sync())) return call.finish(NX_ERR_HIP);
     for (const Piece& p : pieces) ml.msgs.push_back({d->back.data() + p.off, p.len});
-    if (bad != NX_OK) return fail(bad);
+    if (bad != NX_OK) return bzip2_corrupt(d, call, bad);
     if (I->status == NX_OK) {  // the end marker, stream CRC checked: EOF (:126-135); what follows is skipped
         d->closed = true;
-        *msgs = ml.msgs.data();
-        *n_msgs = ml.msgs.size();
-        *consumed = n;
-        return NX_OK;
+        return call.skip_all();
     }
-    if (I->status != NX_ERR_BZIP2_TRUNCATED) return fail(I->status);
+    if (I->status != NX_ERR_BZIP2_TRUNCATED) return bzip2_corrupt(d, call, I->status);
     // wait, as the reference waits: stop at the byte that holds the waiting block's first bit
     if (I->tail_attempted) d->seen_after = count - 1u - I->cursor;
     else if (!pieces.empty()) d->seen_after = 0;
     d->crc = crc;
     d->bit_used = (uint32_t)(next_bit & 7u);
-    *consumed = pos + (size_t)(next_bit >> 3);
-    *msgs = ml.msgs.data();
-    *n_msgs = ml.msgs.size();
-    return NX_OK;
+    pos += (size_t)(next_bit >> 3);
+    return call.finish(NX_OK);
 }

@@ -1,5 +1,5 @@
-// handles.hpp — device context, the synchronous encoders' launch staging (EncodeItems) and the Snappy handler
-// handles shared by the synchronous handler layer (handlers.cpp) and the asynchronous cross-channel batcher
+// handles.hpp — device context, the synchronous handles' launch staging (EncodeItems, DecodeItems, ParamBlock)
+// and the Snappy handler handles shared by the synchronous handler layer (handlers.cpp) and the asynchronous cross-channel batcher
 // (batcher.cpp).  Private to the library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 #include "../../include/netty_amd.h"
+#include "decode_call.hpp"
 #include "encode_items.hpp"
 #include "nx_common.hpp"
 #include "workspace.hpp"
@@ -164,6 +165,109 @@ struct EncodeItems : ItemTable {
     }
 };
 
+// One decode launch of a synchronous handle with item lists (SnappyFrameDecoder; the FastLZ, LZF and LZ4
+// decoders): the items to decode, each with its slot of dout, and a second list of jobs (Snappy's raw chunks
+// to CRC, the LZ decoders' blocks to checksum), as DecodeLayout lays them out.  stage() sizes every array,
+// then uploads: the input bytes, in_off, out_off, in_len, the codec's per-item words (the lengths the LZ
+// blocks must decode to, into out_len; Snappy's expected CRCs or FastLZ's readable bytes, into aux0), then
+// the jobs where they stand apart.  fetch() brings back what the kernels report per item and per job, and
+// syncs.  How the decoded bytes come back is the codec's: Snappy copies each chunk's own bytes (copy_item),
+// the LZ decoders their slots in one piece (fetch's `slots`).
+struct DecodeItems : ItemTable {
+    Gpu& g;
+    const bool jobs_behind_items;
+    std::vector<uint64_t> job_off;
+    std::vector<uint32_t> job_len;
+    std::vector<uint32_t> len, used, job_val;  // fetch(): bytes produced and input used per item (Snappy); a value per job
+    std::vector<int32_t> st;                   // fetch(): each item's status
+    DecodeItems(Gpu& gpu, bool behind) : g(gpu), jobs_behind_items(behind) {}
+    void add_job(uint64_t off, uint32_t n) {
+        job_off.push_back(off);
+        job_len.push_back(n);
+    }
+    uint32_t jobs() const { return (uint32_t)job_len.size(); }
+    DecodeLayout layout() const { return {jobs_behind_items, size(), jobs()}; }
+    // expected_len and item_word: a value per item or nullptr (that array is then neither sized nor uploaded)
+    int32_t stage(const uint8_t* src, size_t n, const std::vector<uint32_t>* expected_len, const std::vector<uint32_t>* item_word) {
+        const DecodeLayout L = layout();
+        const size_t k = L.k, m = L.m, listed = L.listed();
+        if (!g.din.ensure(n + 1) || !g.dout.ensure(out_bytes + 16) || !g.in_off.ensure(8 * listed + 8) || !g.out_off.ensure(8 * k + 8) ||
+            !g.in_len.ensure(4 * listed + 4) || !g.out_len.ensure(4 * k + 4) || !g.status.ensure(4 * k + 4) ||
+            !g.aux0.ensure(item_word ? 4 * k + (jobs_behind_items ? 4 : 0) : 0) || !g.aux1.ensure(L.aux1_bytes()))
+            return NX_ERR_HIP;
+        std::vector<uint64_t> off_all;  // jobs behind the items: one upload of each array holds both lists
+        std::vector<uint32_t> len_all;
+        if (jobs_behind_items && m) {
+            off_all = in_off;
+            off_all.insert(off_all.end(), job_off.begin(), job_off.end());
+            len_all = in_len;
+            len_all.insert(len_all.end(), job_len.begin(), job_len.end());
+        }
+        const uint64_t* h_off = off_all.empty() ? in_off.data() : off_all.data();
+        const uint32_t* h_len = len_all.empty() ? in_len.data() : len_all.data();
+        bool ok = g.h2d(g.din.p, src, n) && g.h2d(g.in_off.p, h_off, 8 * listed) && g.h2d(g.out_off.p, out_off.data(), 8 * k) &&
+                  g.h2d(g.in_len.p, h_len, 4 * listed) && (!expected_len || g.h2d(g.out_len.p, expected_len->data(), 4 * k)) &&
+                  (!item_word || g.h2d(g.aux0.p, item_word->data(), 4 * k));
+        if (!jobs_behind_items) ok = ok && g.h2d(d_job_off(), job_off.data(), 8 * m) && g.h2d(d_job_len(), job_len.data(), 4 * m);
+        return ok ? NX_OK : NX_ERR_HIP;
+    }
+    // a kernel's parameters, in the types it takes them
+    const uint8_t* d_in() const { return g.din.as<uint8_t>(); }
+    const uint64_t* d_in_off() const { return g.in_off.as<uint64_t>(); }
+    const uint32_t* d_in_len() const { return g.in_len.as<uint32_t>(); }
+    uint8_t* d_out() const { return g.dout.as<uint8_t>(); }
+    const uint64_t* d_out_off() const { return g.out_off.as<uint64_t>(); }
+    uint32_t* d_out_len() const { return g.out_len.as<uint32_t>(); }
+    uint32_t* d_item_word() const { return g.aux0.as<uint32_t>(); }
+    uint32_t* d_used() const { return g.status.as<uint32_t>(); }  // Snappy: the input each item used
+    int32_t* d_status() const { return jobs_behind_items ? g.aux1.as<int32_t>() : g.status.as<int32_t>(); }
+    // the second list from job `from` on
+    uint64_t* d_job_off(uint32_t from = 0) const {
+        return (jobs_behind_items ? g.in_off.as<uint64_t>() : g.aux1.as<uint64_t>()) + layout().job_off_at() + from;
+    }
+    uint32_t* d_job_len(uint32_t from = 0) const {
+        return (jobs_behind_items ? g.in_len.as<uint32_t>() : g.aux1.as<uint32_t>()) + layout().job_len_at() + from;
+    }
+    uint32_t* d_job_val(uint32_t from = 0) const { return g.aux1.as<uint32_t>() + layout().job_val_at() + from; }
+    // Snappy: each item's length, used input and status; the LZ decoders: each item's status, then the slots
+    // in one piece into `slots`.  Then the jobs' values, and the sync.
+    bool fetch(uint8_t* slots = nullptr) {
+        const size_t k = size(), m = jobs();
+        st = std::vector<int32_t>(k);
+        job_val = std::vector<uint32_t>(m);
+        bool ok = true;
+        if (jobs_behind_items) {
+            len = std::vector<uint32_t>(k);
+            used = std::vector<uint32_t>(k);
+            ok = g.d2h(len.data(), g.out_len.p, 4 * k) && g.d2h(used.data(), d_used(), 4 * k);
+        }
+        return ok && g.d2h(st.data(), d_status(), 4 * k) && (!slots || g.d2h(slots, g.dout.p, out_bytes)) &&
+               g.d2h(job_val.data(), d_job_val(), 4 * m) && g.sync();
+    }
+    // an item's own bytes (not its slot) to dst; the caller syncs once after its last item
+    bool copy_item(uint32_t i, uint8_t* dst) { return g.d2h(dst, d_out() + out_off[i], len[i]); }
+};
+
+// A device copy of one plain struct T inside a DevBuf of the handle: a single item's launch arguments and
+// results.  field() hands a kernel the device address of a member, in the member's type.
+template <class T>
+struct ParamBlock {
+    Gpu& g;
+    DevBuf& buf;
+    ParamBlock(Gpu& gpu, DevBuf& b) : g(gpu), buf(b) {}
+    bool ensure() const { return buf.ensure(sizeof(T)); }
+    bool upload(const T& v, size_t bytes_in = sizeof(T)) const { return g.h2d(buf.p, &v, bytes_in); }
+    template <class M>
+    bool download(T& v, M T::*from_field) const {  // the block from that member to its end
+        const size_t at = field_offset(from_field);
+        return g.d2h(reinterpret_cast<uint8_t*>(&v) + at, buf.as<uint8_t>() + at, sizeof(T) - at);
+    }
+    template <class M>
+    M* field(M T::*member) const {
+        return static_cast<M*>(static_cast<void*>(buf.as<uint8_t>() + field_offset(member)));
+    }
+};
+
 // new H holding the device workspace of kind k, or nullptr
 template <class H>
 H* make_handle(WsKind k) {
@@ -173,17 +277,6 @@ H* make_handle(WsKind k) {
     return nullptr;
 }
 #pragma GCC visibility pop
-
-struct MsgList {
-    std::vector<nx_msg> msgs;
-    std::vector<std::vector<uint8_t>> owned;  // decoded payloads (stable storage)
-    std::string err;
-    void clear() {
-        msgs.clear();
-        owned.clear();
-        err.clear();
-    }
-};
 
 inline constexpr uint8_t kStreamStart[10] = {0xff, 0x06, 0x00, 0x00, 0x73, 0x4e, 0x61, 0x50, 0x70, 0x59};
 

@@ -226,3 +226,42 @@ def test_null_out_pointer_is_invalid_arg(oracle, dec, text, codec):
         args = full[:k] + [None] + full[k + 1:]
         assert d.fn(d.h, s, len(s), *args, C.byref(err)) == NX_ERR_INVALID_ARG
     assert d.decode(s) == (0, len(s), [text[0], text[1]], None)  # the refused calls changed nothing
+
+
+ENTRY_POINTS = {  # every synchronous decoder's decode(): its handle and one good stream of `data`
+    "snappy": (lambda H: H.SnappyFrameDecoder(True), lambda o, d: o.snappy_frame_encode(d)[0]),
+    "fastlz": (lambda H: H.FastLzFrameDecoder(True), lambda o, d: o.fastlz_frame_encode(d, 0, True)),
+    "lzf": (lambda H: H.LzfDecoder(), lambda o, d: o.lzf_frame_encode(d)),
+    "lz4": (lambda H: H.Lz4FrameDecoder(True), lambda o, d: o.lz4_frame_encode(d)),
+    "zstd": (lambda H: H.ZstdDecoder(0), lambda o, d: __import__("pyarrow").Codec("zstd").compress(d).to_pybytes()),
+    "zlib": (lambda H: H.JdkZlibDecoder(), lambda o, d: __import__("zlib").compress(d)),
+    "bzip2": (lambda H: H.Bzip2Decoder(), lambda o, d: __import__("bz2").compress(d, 1)),
+}
+
+
+@pytest.mark.parametrize("name", sorted(ENTRY_POINTS))
+def test_null_arguments_of_every_decoder(L, oracle, text, name):
+    """Null consumed, msgs or n_msgs: NX_ERR_INVALID_ARG and nothing changes; null err_msg is accepted, and the
+    handle that refused three calls then decodes a good stream as a fresh handle does."""
+    from netty_amd import _lib, handlers as H
+    make, enc = ENTRY_POINTS[name]
+    s = enc(oracle, text[0] + text[1])
+
+    def decode(d, err_arg):
+        consumed, n, msgs = C.c_size_t(12345), C.c_size_t(12345), C.POINTER(_lib.NxMsg)()
+        rc = getattr(L, d._decode_fn)(d._h, s, len(s), C.byref(consumed), C.byref(msgs), C.byref(n), err_arg)
+        return rc, consumed.value, [C.string_at(msgs[i].data, msgs[i].len) for i in range(n.value)]
+
+    d, fresh = make(H), make(H)
+    try:
+        consumed, n, msgs, err = C.c_size_t(0), C.c_size_t(0), C.POINTER(_lib.NxMsg)(), C.c_char_p()
+        full = [C.byref(consumed), C.byref(msgs), C.byref(n)]
+        for k in range(3):
+            args = full[:k] + [None] + full[k + 1:]
+            assert getattr(L, d._decode_fn)(d._h, s, len(s), *args, C.byref(err)) == NX_ERR_INVALID_ARG
+        want = decode(fresh, C.byref(err))
+        assert want[:2] == (0, len(s)) and b"".join(want[2]) == text[0] + text[1] and err.value is None
+        assert decode(d, None) == want
+    finally:
+        d.close()
+        fresh.close()
