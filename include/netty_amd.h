@@ -79,6 +79,7 @@ int32_t nx_snappy_encode_batch(const uint8_t* in, const uint64_t* in_off, const 
 #define NX_WS_ZSTD_DEC 8
 #define NX_WS_BZIP2_DEC 9
 #define NX_WS_BZIP2_ENC 10
+#define NX_WS_LZMA_ENC 11
 int32_t nx_snappy_encoder_reserve(uint32_t max_chunks, void* stream);
 /* The same with a bound (round 6): max_bytes caps the Snappy table workspace for good (0: no cap; 128
  * KiB per lane, whole blocks of 256 lanes above 16 384): batches of any size then run on those lanes
@@ -261,6 +262,48 @@ size_t nx_zstd_max_compressed_length(size_t n);
 int32_t nx_zstd_encode_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
                              const uint64_t* out_off, uint32_t* out_len, int32_t* status, uint32_t n, int32_t level,
                              void* stream);
+
+/*
+ * LZMA streams (LzmaFrameEncoder.java:177-186: every encode() writes one complete, independent stream).  Item i,
+ * of any length up to 256 MiB (0 included), becomes in out[out_off[i] ..): the properties byte
+ * (pb * 5 + lp) * 9 + lc, dict_size and in_len[i] as 4 and 8 little-endian bytes, the LZMA payload of the item
+ * coded from a freshly initialised model, the end marker if end_marker != 0 (the length field still holds the
+ * real length), and the range coder's five flush bytes; an empty item is 18 bytes.  The header is the reference's
+ * byte for byte; the payload is this encoder's own (lzma-java's optimal parser is not restated): a greedy parse,
+ * minimum match 4, the four rep distances tried first, matches up to 273 bytes at distances up to
+ * min(position, dict_size) (csrc/lzma_encode_core.hpp states the rule).  Standard decoders decode it to the item
+ * and it ends exactly where the stream ends.
+ *   out_len[i] on entry = the capacity of item i's slot in bytes (this call has no out_cap array: the
+ *                argument list is nx_zstd_encode_batch's), on return the stream's size (0 on an error);
+ *   status[i]  = NX_OK, NX_ERR_LZMA_ENCODE_FULL (the stream does not fit the slot; nothing is written past
+ *                it) or NX_ERR_INVALID_ARG (an item over 256 MiB).
+ * nx_lzma_max_compressed_length(n) = 13 + n + n / 3 + 128 is the LZMA SDK's documented allowance, not a
+ * proven bound, which is why the kernel checks every byte (DESIGN.md has the worst expansion measured).
+ * The call fails before any launch with NX_ERR_LZMA_PROPS for lc outside 0-8, lp or pb outside 0-4 or
+ * lc + lp > 4 (the kernel keeps the model in LDS; nx_lzma_encode_host takes every lc, lp) and with
+ * NX_ERR_LZMA_DICT_SIZE for dict_size < 0.
+ * Two launches per sub-batch: a matcher, one lane per item over 512 KiB of NX_WS_LZMA_ENC hash table, and a
+ * coder, one wave per item.  The call reads in_len back to lay out the items' sequence areas (16 + 8 * (n / 2
+ * + 2) bytes of a per-device arena each), so it synchronises `stream` once before its first launch.
+ */
+size_t nx_lzma_max_compressed_length(size_t n);
+int32_t nx_lzma_encode_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                             const uint64_t* out_off, uint32_t* out_len, int32_t* status, uint32_t n, int32_t lc, int32_t lp,
+                             int32_t pb, int32_t dict_size, int32_t end_marker, void* stream);
+/* What nx_lzma_encode_host's coder did: packets by kind, the carries the range coder propagated into bytes
+ * already shifted out, the longest run of pending 0xFF bytes, and the longest such run a carry went through. */
+typedef struct nx_lzma_encode_stats {
+    uint64_t literals, matched_literals, matches, short_reps, reps[4], carries, max_pending_ff, max_carry_ff;
+} nx_lzma_encode_stats;
+/*
+ * One item encoded on the host, single-threaded, by the functions the kernels run (csrc/lzma_encode_core.hpp):
+ * the same bytes, for every lc, lp, pb the constructor accepts (lc + lp > 4 included).  Returns the stream's
+ * size, or NX_ERR_LZMA_PROPS, NX_ERR_LZMA_DICT_SIZE, NX_ERR_LZMA_ENCODE_FULL (it does not fit out_cap; nothing
+ * is written past it) or NX_ERR_INVALID_ARG.  stats may be NULL.  The CPU check of the format core, the GPU
+ * tests' second opinion, and the path of a handle whose lc + lp > 4.
+ */
+int64_t nx_lzma_encode_host(const uint8_t* in, size_t n, int32_t lc, int32_t lp, int32_t pb, int32_t dict_size,
+                            int32_t end_marker, uint8_t* out, size_t out_cap, nx_lzma_encode_stats* stats);
 
 /*
  * Replaces Zstd.decompress as ZstdDecoder.java calls it through zstd-jni (ZSTD_decompress on one frame),
@@ -774,6 +817,27 @@ size_t nx_lz4_frame_max_encoded_length(size_t n, int32_t block_size);
 int64_t nx_lz4_frame_encoder_encode(nx_lz4_frame_encoder* e, const uint8_t* in, size_t n, uint8_t* out, size_t out_cap);
 int64_t nx_lz4_frame_encoder_flush(nx_lz4_frame_encoder* e, uint8_t* out, size_t out_cap);
 int64_t nx_lz4_frame_encoder_close(nx_lz4_frame_encoder* e, uint8_t* out, size_t out_cap);
+
+/*
+ * LzmaFrameEncoder(lc, lp, pb, dictionarySize, endMarkerMode, numFastBytes)  LzmaFrameEncoder.java:97-213.  The
+ * reference's defaults are 3, 0, 2, 65536, false, 32.  _new returns NULL for an argument the constructor refuses
+ * (nx_lzma_frame_encoder_check says which: NX_ERR_LZMA_PROPS, _DICT_SIZE or _FAST_BYTES) or without a device.
+ * num_fast_bytes is checked (5-273) and does not change the bytes: it steers lzma-java's optimal parser, which
+ * this encoder does not restate.  lc + lp > 4 is accepted, as the reference does with a logged warning; such a
+ * handle encodes through nx_lzma_encode_host (no current decoder library reads its streams).
+ * _encode: one complete stream per call (an empty write gives 18 bytes), nothing kept between calls and
+ * nothing written at close.  nx_lzma_frame_max_encoded_length(n) bytes of out always suffice as far as
+ * nx_lzma_max_compressed_length is an allowance; a stream that does not fit out_cap returns
+ * NX_ERR_LZMA_ENCODE_FULL.  _error: the last failure's message.
+ */
+typedef struct nx_lzma_frame_encoder nx_lzma_frame_encoder;
+int32_t nx_lzma_frame_encoder_check(int32_t lc, int32_t lp, int32_t pb, int32_t dict_size, int32_t num_fast_bytes);
+nx_lzma_frame_encoder* nx_lzma_frame_encoder_new(int32_t lc, int32_t lp, int32_t pb, int32_t dict_size, int32_t end_marker,
+                                                 int32_t num_fast_bytes);
+void nx_lzma_frame_encoder_free(nx_lzma_frame_encoder* e);
+const char* nx_lzma_frame_encoder_error(nx_lzma_frame_encoder* e);
+size_t nx_lzma_frame_max_encoded_length(size_t n);
+int64_t nx_lzma_frame_encoder_encode(nx_lzma_frame_encoder* e, const uint8_t* in, size_t n, uint8_t* out, size_t out_cap);
 
 /*
  * ZstdEncoder.  nx_zstd_encoder_new(level, block_size, max_encode_size) restates the constructor's three

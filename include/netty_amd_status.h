@@ -141,6 +141,16 @@
 /* This library's own (nx_bzip2_scan_batch, nx_bzip2_decode_batch_split): the item holds more block and
  * end-of-stream magics than the call's max_blocks leaves room for. */
 #define NX_ERR_BZIP2_DECODE_BLOCKS        (-128)
+/* LZMA stream encoding (nx_lzma_encode_batch, nx_lzma_encode_host, LzmaFrameEncoder). */
+/* LzmaFrameEncoder.java:139-147  "lc: %d (expected: 0-8)", "lp: %d (expected: 0-4)", "pb: %d (expected: 0-4)" (each an
+ * IllegalArgumentException); from nx_lzma_encode_batch also lc + lp > 4, which the kernel's model does not hold */
+#define NX_ERR_LZMA_PROPS                 (-140)
+/* :157-159  "dictionarySize: %d (expected: 0+)" */
+#define NX_ERR_LZMA_DICT_SIZE             (-141)
+/* :160-164  "numFastBytes: %d (expected: 5-273)" */
+#define NX_ERR_LZMA_FAST_BYTES            (-142)
+/* This library's own: the stream does not fit the output slot. */
+#define NX_ERR_LZMA_ENCODE_FULL           (-143)
 
 /* Device frame scan (nx_snappy_frame_scan_batch), one code per SnappyFrameDecoder throw site: */
 /* :116-118  "Unexpected length of stream identifier: %d" */

@@ -24,6 +24,7 @@ from .handlers import (  # noqa: F401
     Lz4FrameEncoder,
     LzfDecoder,
     LzfEncoder,
+    LzmaFrameEncoder,
     SnappyFrameDecoder,
     SnappyFrameEncoder,
     SnappyFramedDecoder,

@@ -22,6 +22,11 @@ sz = C.c_size_t
 i64 = C.c_int64
 
 
+class LzmaEncodeStats(C.Structure):  # nx_lzma_encode_stats
+    _fields_ = [("literals", C.c_uint64), ("matched_literals", C.c_uint64), ("matches", C.c_uint64), ("short_reps", C.c_uint64),
+                ("reps", C.c_uint64 * 4), ("carries", C.c_uint64), ("max_pending_ff", C.c_uint64), ("max_carry_ff", C.c_uint64)]
+
+
 class NxMsg(C.Structure):
     _fields_ = [("data", C.POINTER(C.c_uint8)), ("len", C.c_size_t)]
 
@@ -96,6 +101,15 @@ _SIGS = {
     "nx_bzip2_encoder_close": (i64, [vp, vp, sz]),
     "nx_bzip2_encoder_is_closed": (i32, [vp]),
     "nx_bzip2_encoder_launches": (u64, [vp]),
+    "nx_lzma_max_compressed_length": (sz, [sz]),
+    "nx_lzma_encode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, i32, i32, i32, i32, i32, vp]),
+    "nx_lzma_encode_host": (i64, [C.c_char_p, sz, i32, i32, i32, i32, i32, vp, sz, vp]),
+    "nx_lzma_frame_encoder_check": (i32, [i32, i32, i32, i32, i32]),
+    "nx_lzma_frame_encoder_new": (vp, [i32, i32, i32, i32, i32, i32]),
+    "nx_lzma_frame_encoder_free": (None, [vp]),
+    "nx_lzma_frame_encoder_error": (C.c_char_p, [vp]),
+    "nx_lzma_frame_max_encoded_length": (sz, [sz]),
+    "nx_lzma_frame_encoder_encode": (i64, [vp, C.c_char_p, sz, vp, sz]),
     "nx_inflate_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]),
     "nx_lzf_encode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, vp]),
     "nx_lzf_decode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, vp]),

@@ -25,7 +25,7 @@ def _chk(rc, what):
 
 
 # Shared device workspaces (include/netty_amd.h NX_WS_*; csrc/workspace.hpp)
-WS_SNAPPY_ENC, WS_LZ4_ENC, WS_FASTLZ_ENC, WS_LZF_ENC, WS_DEC_RECORDS, WS_LZ4HC_ENC, WS_DEFLATE_ENC, WS_ZSTD_ENC, WS_ZSTD_DEC, WS_BZIP2_DEC, WS_BZIP2_ENC = range(11)
+WS_SNAPPY_ENC, WS_LZ4_ENC, WS_FASTLZ_ENC, WS_LZF_ENC, WS_DEC_RECORDS, WS_LZ4HC_ENC, WS_DEFLATE_ENC, WS_ZSTD_ENC, WS_ZSTD_DEC, WS_BZIP2_DEC, WS_BZIP2_ENC, WS_LZMA_ENC = range(12)
 
 
 def workspace_info(kind: int) -> tuple[int, int]:
@@ -531,6 +531,49 @@ def bzip2_encode_host(data: bytes, level: int = 9, out_cap=None):
     ol = C.c_size_t(0)
     st = _lib.load().nx_bzip2_encode_host(data, len(data), int(level), C.cast(buf, C.c_void_p), cap, C.byref(ol))
     return st, buf.raw[:ol.value]
+
+
+def lzma_max_compressed_length(n: int) -> int:
+    """nx_lzma_max_compressed_length: 13 + n + n / 3 + 128, the LZMA SDK's allowance (not a proven bound)."""
+    return _lib.load().nx_lzma_max_compressed_length(int(n))
+
+
+def lzma_encode(inp, in_off, in_len, out, out_off, out_cap, lc: int = 3, lp: int = 0, pb: int = 2, dict_size: int = 65536,
+                end_marker: bool = False):
+    """One LZMA stream per item (nx_lzma_encode_batch): item i = inp[in_off[i] : + in_len[i]] becomes what
+    LzmaFrameEncoder writes for one encode(in), header and payload, in out[out_off[i] : + out_cap[i]].  Returns
+    (out_len, status): the stream's size and 0 or NX_ERR_LZMA_ENCODE_FULL (-143) per item.  out_cap is copied
+    into out_len, which the call takes as capacities.  lc + lp > 4 raises (NX_ERR_LZMA_PROPS); the call reads
+    in_len back, so it synchronises the current stream."""
+    n = in_len.numel()
+    dev = inp.device
+    out_len = out_cap.to(device=dev, dtype=torch.int32, copy=True)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    _chk(_lib.load().nx_lzma_encode_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_len), _ptr(status),
+                                          n, int(lc), int(lp), int(pb), int(dict_size), int(bool(end_marker)), _stream()),
+         "nx_lzma_encode_batch")
+    return out_len, status
+
+
+def lzma_encode_host(data: bytes, lc: int = 3, lp: int = 0, pb: int = 2, dict_size: int = 65536, end_marker: bool = False,
+                     out_cap=None, stats: bool = False, guard: int = 0):
+    """nx_lzma_encode_host on host bytes: (status, stream) of one item, by the kernels' format functions on the
+    CPU, for every lc, lp, pb; out_cap defaults to lzma_max_compressed_length.  stats=True appends the
+    nx_lzma_encode_stats as a dict; guard > 0 appends the `guard` bytes behind out_cap (0xA5 before the call)."""
+    import ctypes as C
+    data = bytes(data)
+    cap = lzma_max_compressed_length(len(data)) if out_cap is None else int(out_cap)
+    buf = C.create_string_buffer(b"\xa5" * (cap + guard + 1), cap + guard + 1)
+    S = _lib.LzmaEncodeStats()
+    r = _lib.load().nx_lzma_encode_host(data, len(data), int(lc), int(lp), int(pb), int(dict_size), int(bool(end_marker)),
+                                        C.cast(buf, C.c_void_p), cap, C.byref(S) if stats else None)
+    res = [0 if r >= 0 else int(r), buf.raw[:r] if r >= 0 else b""]
+    if stats:
+        res.append({"literals": S.literals, "matched_literals": S.matched_literals, "matches": S.matches, "short_reps": S.short_reps,
+                    "reps": list(S.reps), "carries": S.carries, "max_pending_ff": S.max_pending_ff, "max_carry_ff": S.max_carry_ff})
+    if guard:
+        res.append(buf.raw[cap:cap + guard])
+    return tuple(res)
 
 
 INFLATE_STATE_BYTES = 512

@@ -344,6 +344,14 @@ struct nx_zstd_encoder {
     std::vector<uint8_t> buf;           // the block buffer (:49,136-143), grown on demand
 };
 
+// LzmaFrameEncoder (handlers.cpp): the constructor's settings; no state between writes.
+struct nx_lzma_frame_encoder {
+    nx::h::Gpu g;
+    int32_t lc = 3, lp = 0, pb = 2, dict_size = 65536, num_fast_bytes = 32;
+    bool end_marker = false;
+    std::string err;  // the last failure's message
+};
+
 // Bzip2Encoder (handlers.cpp): the planner's state and the raw bytes of the open block on the host, the bits
 // that do not fill a 32-bit word and the stream CRC between launches.
 struct nx_bzip2_encoder {

@@ -43,6 +43,10 @@ extern "C" const char* nx_status_string(int32_t s) {
         case NX_ERR_BZIP2_ENCODE_FULL: return "the bzip2 stream does not fit the output slot";
         case NX_ERR_BZIP2_ENCODE_BLOCKS: return "the bzip2 stream's blocks fall beyond max_blocks";
         case NX_ERR_BZIP2_DECODE_BLOCKS: return "the bzip2 stream's candidate blocks fall beyond max_blocks";
+        case NX_ERR_LZMA_PROPS: return "lc (expected: 0-8), lp (expected: 0-4), pb (expected: 0-4); on the GPU lc + lp (expected: 0-4)";
+        case NX_ERR_LZMA_DICT_SIZE: return "dictionarySize (expected: 0+)";
+        case NX_ERR_LZMA_FAST_BYTES: return "numFastBytes (expected: 5-273)";
+        case NX_ERR_LZMA_ENCODE_FULL: return "the LZMA stream does not fit the output slot";
         case NX_ERR_LZ4_ENCODE_FINISHED: return "encode finished and not enough space to write remaining data";
         case NX_ERR_SNAPPY_PREAMBLE_TOO_LONG: return "Preamble is greater than 4 bytes";
         case NX_ERR_SNAPPY_OFFSET_ZERO: return "Offset is less than minimum permissible value";

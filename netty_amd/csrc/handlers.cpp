@@ -843,6 +843,64 @@ extern "C" int64_t nx_zstd_encoder_flush(nx_zstd_encoder* e, uint8_t* out, size_
     return w;
 }
 
+// ------------------------------------------------------------------ LzmaFrameEncoder
+// LzmaFrameEncoder.java:177-186: every encode() is one complete stream (header, payload from a fresh model).
+extern "C" int32_t nx_lzma_frame_encoder_check(int32_t lc, int32_t lp, int32_t pb, int32_t dict_size, int32_t num_fast_bytes) {
+    if (lc < 0 || lc > 8 || lp < 0 || lp > 4 || pb < 0 || pb > 4) return NX_ERR_LZMA_PROPS;  // :139-147
+    if (dict_size < 0) return NX_ERR_LZMA_DICT_SIZE;                                        // :157-159
+    if (num_fast_bytes < 5 || num_fast_bytes > 273) return NX_ERR_LZMA_FAST_BYTES;          // :160-164
+    return NX_OK;
+}
+
+extern "C" nx_lzma_frame_encoder* nx_lzma_frame_encoder_new(int32_t lc, int32_t lp, int32_t pb, int32_t dict_size, int32_t end_marker,
+                                                            int32_t num_fast_bytes) {
+    if (nx_lzma_frame_encoder_check(lc, lp, pb, dict_size, num_fast_bytes) != NX_OK) return nullptr;
+    auto* e = new nx_lzma_frame_encoder();
+    // a write is one item: one table slot.  (lc + lp > 4 encodes on the host, and holds nothing.)
+    if (lc + lp <= 4) {
+        if (!e->g.ok || nx::ws_hold(nx::WsKind::LzmaEnc, e->g.dev, 1u, e->g.s) != NX_OK) {
+            delete e;
+            return nullptr;
+        }
+        e->g.held |= 1u << (int)nx::WsKind::LzmaEnc;
+    }
+    e->lc = lc;
+    e->lp = lp;
+    e->pb = pb;
+    e->dict_size = dict_size;
+    e->end_marker = end_marker != 0;
+    e->num_fast_bytes = num_fast_bytes;
+    return e;
+}
+extern "C" void nx_lzma_frame_encoder_free(nx_lzma_frame_encoder* e) { delete e; }
+extern "C" const char* nx_lzma_frame_encoder_error(nx_lzma_frame_encoder* e) { return last_error(e); }
+extern "C" size_t nx_lzma_frame_max_encoded_length(size_t n) { return nx_lzma_max_compressed_length(n); }
+
+extern "C" int64_t nx_lzma_frame_encoder_encode(nx_lzma_frame_encoder* e, const uint8_t* in, size_t n, uint8_t* out, size_t out_cap) {
+    const nx::NoGrowScope no_grow;
+    if (!e || (!in && n) || (!out && out_cap) || n > 0x7FFFFFFFull) return NX_ERR_INVALID_ARG;
+    auto fail = [&](int64_t r) {
+        if (r < 0) e->err = r == NX_ERR_LZMA_ENCODE_FULL ? "the LZMA stream does not fit the output buffer" : nx_status_string((int32_t)r);
+        return r;
+    };
+    if (e->lc + e->lp > 4)
+        return fail(nx_lzma_encode_host(in, n, e->lc, e->lp, e->pb, e->dict_size, e->end_marker, out, out_cap, nullptr));
+    const size_t bound = nx_lzma_max_compressed_length(n);
+    const uint32_t cap = (uint32_t)(out_cap < bound ? out_cap : bound);  // the slot the kernel may write
+    EncodeItems it(e->g);
+    it.add(0, (uint32_t)n, (bound + 15) / 16 * 16);
+    int32_t r = it.stage(in, n);
+    if (r != NX_OK) return fail(r);
+    if (!e->g.h2d(e->g.out_len.p, &cap, 4)) return fail(NX_ERR_HIP);
+    r = nx_lzma_encode_batch(it.d_in(), it.d_in_off(), it.d_in_len(), it.d_out(), it.d_out_off(), it.d_out_len(), it.d_status(), 1u, e->lc,
+                             e->lp, e->pb, e->dict_size, e->end_marker, e->g.s);
+    if (r != NX_OK) return fail(r);
+    if (!it.fetch(true)) return fail(NX_ERR_HIP);
+    if (it.st[0] != NX_OK) return fail(it.st[0]);
+    if (!it.copy_item(0, out) || !e->g.sync()) return fail(NX_ERR_HIP);
+    return (int64_t)it.len[0];
+}
+
 // ------------------------------------------------------------------ Bzip2Encoder
 // Bzip2Encoder.java:105-228 over nx_bzip2_encode_batch_split.  The planner runs on the host over every write
 // (nx_bzip2_plan_resume_host), the open block's input stays in host memory, and a write that closes k blocks

@@ -340,6 +340,48 @@ class ZstdEncoder(_Encoder):
         return self._ret(_lib.load().nx_zstd_encoder_flush(self._h, out, cap), out)
 
 
+class LzmaFrameEncoder(_Encoder):
+    """LzmaFrameEncoder.java:97-213 over the GPU LZMA encoder.  Every encode() returns one complete stream: the
+    13 header bytes (properties, dictionary size, the exact length) and the payload coded from a fresh model;
+    an empty write gives 18 bytes.  Nothing is kept between writes and close() writes nothing.  The
+    reference's shorter constructors, LzmaFrameEncoder(), (lc, lp, pb), (dictionarySize) and (lc, lp, pb,
+    dictionarySize), are the keyword defaults.  num_fast_bytes is checked and does not change the bytes (it
+    steers lzma-java's optimal parser; this encoder parses greedily).  lc + lp > 4 is accepted as the reference
+    accepts it (it logs a warning: current decoder libraries refuse such streams) and is encoded on the host by
+    the same format code, since the kernel keeps the model in LDS."""
+
+    _free = "nx_lzma_frame_encoder_free"
+    MIN_FAST_BYTES, MAX_FAST_BYTES = 5, 273  # LzmaFrameEncoder.java:45-50
+
+    def __init__(self, lc: int = 3, lp: int = 0, pb: int = 2, dictionary_size: int = 65536, end_marker_mode: bool = False,
+                 num_fast_bytes: int = 32):
+        if lc < 0 or lc > 8:  # :139-141
+            raise ValueError(f"lc: {lc} (expected: 0-8)")
+        if lp < 0 or lp > 4:  # :142-144
+            raise ValueError(f"lp: {lp} (expected: 0-4)")
+        if pb < 0 or pb > 4:  # :145-147
+            raise ValueError(f"pb: {pb} (expected: 0-4)")
+        if dictionary_size < 0:  # :157-159
+            raise ValueError(f"dictionarySize: {dictionary_size} (expected: 0+)")
+        if num_fast_bytes < self.MIN_FAST_BYTES or num_fast_bytes > self.MAX_FAST_BYTES:  # :160-164
+            raise ValueError(f"numFastBytes: {num_fast_bytes} (expected: {self.MIN_FAST_BYTES}-{self.MAX_FAST_BYTES})")
+        self.lc, self.lp, self.pb = int(lc), int(lp), int(pb)
+        self.dictionary_size = int(dictionary_size)
+        self.end_marker_mode = bool(end_marker_mode)
+        self.num_fast_bytes = int(num_fast_bytes)
+        self._h = _new(_lib.load().nx_lzma_frame_encoder_new(self.lc, self.lp, self.pb, self.dictionary_size, int(self.end_marker_mode),
+                                                             self.num_fast_bytes), "LzmaFrameEncoder")
+
+    def encode(self, data: bytes) -> bytes:
+        cap = _lib.load().nx_lzma_frame_max_encoded_length(len(data))
+        out = (C.c_uint8 * cap)()
+        r = _lib.load().nx_lzma_frame_encoder_encode(self._h, data, len(data), out, cap)
+        if r < 0:
+            err = _lib.load().nx_lzma_frame_encoder_error(self._h)
+            raise CompressionException(err.decode() if err else _lib.status_string(r))
+        return bytes(out[:r])
+
+
 class Bzip2Encoder(_Encoder):
     """Bzip2Encoder.java:96-228 over the GPU bzip2 encoder's split path: one stream over any number of writes,
     the same bytes however the writes slice the input.  The first encode() writes "BZh" and the level digit;
