@@ -80,6 +80,7 @@ int32_t nx_snappy_encode_batch(const uint8_t* in, const uint64_t* in_off, const 
 #define NX_WS_BZIP2_DEC 9
 #define NX_WS_BZIP2_ENC 10
 #define NX_WS_LZMA_ENC 11
+#define NX_WS_BROTLI_ENC 12
 int32_t nx_snappy_encoder_reserve(uint32_t max_chunks, void* stream);
 /* The same with a bound (round 6): max_bytes caps the Snappy table workspace for good (0: no cap; 128
  * KiB per lane, whole blocks of 256 lanes above 16 384): batches of any size then run on those lanes
@@ -304,6 +305,45 @@ typedef struct nx_lzma_encode_stats {
  */
 int64_t nx_lzma_encode_host(const uint8_t* in, size_t n, int32_t lc, int32_t lp, int32_t pb, int32_t dict_size,
                             int32_t end_marker, uint8_t* out, size_t out_cap, nx_lzma_encode_stats* stats);
+
+/*
+ * Brotli streams (RFC 7932), what BrotliEncoder writes for a channel whose whole input is item i.  Item i, of any
+ * length up to 256 MiB (0 included), becomes in out[out_off[i] ..): the WBITS header for lgwin, meta-blocks of at
+ * most 65 536 input bytes, and the empty last meta-block; an empty item is the header and that block.  The bytes
+ * are this encoder's own (libbrotli's parsers are not restated): a greedy parse, minimum match 4, copies of up to
+ * 65 536 bytes at distances up to min(position, (1 << lgwin) - 16), no reference to the static dictionary; one
+ * literal, one command and one distance prefix code per meta-block, the last four distances and the implicit
+ * last-distance commands used; a meta-block whose compressed form would not be smaller is written uncompressed
+ * (csrc/brotli_encode_core.hpp states the subset and the rule).  Standard decoders decode the stream to the item
+ * and it ends exactly where the stream ends.
+ *   out_len[i] on entry = the capacity of item i's slot in bytes (the argument list is nx_lzma_encode_batch's),
+ *                on return the stream's size (0 on an error);
+ *   status[i]  = NX_OK, NX_ERR_BROTLI_ENCODE_FULL (the stream does not fit the slot; nothing is written past
+ *                it) or NX_ERR_INVALID_ARG (an item over 256 MiB).
+ * nx_brotli_max_compressed_length(n) = n + 4 * ceil(n / 65536) + 3 is a proven bound (the header derives it from
+ * the uncompressed fallback); the kernel checks every byte against the slot all the same.
+ * lgwin: 10-24, or -1 for 22; anything else fails before any launch with NX_ERR_BROTLI_LGWIN.
+ * Two launches per sub-batch: a matcher, one lane per item over 512 KiB of NX_WS_BROTLI_ENC hash table, and an
+ * emitter, one wave per item.  The call reads in_len back to lay out the items' sequence areas (16 + 8 * (n / 4
+ * + (n >> 23) + 2) bytes of a per-device arena each, rounded up to 16), so it synchronises `stream` once before its first launch.
+ */
+size_t nx_brotli_max_compressed_length(size_t n);
+int32_t nx_brotli_encode_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                               const uint64_t* out_off, uint32_t* out_len, int32_t* status, uint32_t n, int32_t lgwin, void* stream);
+/* What nx_brotli_encode_host wrote: meta-blocks by kind, commands and literals of the compressed ones, copies
+ * coded as one of the last four distances with a distance symbol (ring) or as the last distance without one
+ * (implicit), copies cut at a meta-block boundary, prefix codes by kind (simple_codes[k]: NSYM = k + 1), the
+ * codes whose Huffman lengths passed the limit of 15 before limiting, and the deepest such length. */
+typedef struct nx_brotli_encode_stats {
+    uint64_t compressed_blocks, uncompressed_blocks, commands, literals, ring_copies, implicit_copies, split_copies, simple_codes[4],
+        complex_codes, limited_codes, max_depth_unlimited;
+} nx_brotli_encode_stats;
+/*
+ * One item encoded on the host, single-threaded, by the functions the kernels run (csrc/brotli_encode_core.hpp):
+ * the same bytes.  Returns the stream's size, or NX_ERR_BROTLI_LGWIN, NX_ERR_BROTLI_ENCODE_FULL (it does not fit
+ * out_cap; nothing is written past it) or NX_ERR_INVALID_ARG.  stats may be NULL.
+ */
+int64_t nx_brotli_encode_host(const uint8_t* in, size_t n, int32_t lgwin, uint8_t* out, size_t out_cap, nx_brotli_encode_stats* stats);
 
 /*
  * Replaces Zstd.decompress as ZstdDecoder.java calls it through zstd-jni (ZSTD_decompress on one frame),
@@ -838,6 +878,32 @@ void nx_lzma_frame_encoder_free(nx_lzma_frame_encoder* e);
 const char* nx_lzma_frame_encoder_error(nx_lzma_frame_encoder* e);
 size_t nx_lzma_frame_max_encoded_length(size_t n);
 int64_t nx_lzma_frame_encoder_encode(nx_lzma_frame_encoder* e, const uint8_t* in, size_t n, uint8_t* out, size_t out_cap);
+
+/*
+ * BrotliEncoder(parameters)  BrotliEncoder.java:47-230: one Brotli stream per channel, every write compressed and
+ * flushed.  quality -1 or 0-11, lgwin -1 or 10-24 and mode 0 (GENERIC), 1 (TEXT) or 2 (FONT) are what brotli4j's
+ * Encoder.Parameters accepts; BrotliOptions.DEFAULT is 4, -1, TEXT.  _new returns NULL for a value outside them
+ * (nx_brotli_encoder_check says which: NX_ERR_BROTLI_QUALITY, _LGWIN or _MODE) or without a device.  quality and
+ * mode are checked and do not change the bytes: they steer libbrotli's parsers, which this encoder does not
+ * restate.
+ * _encode: an empty write returns 0 and changes nothing (:125-127).  Any other returns whole bytes: the WBITS
+ * header if this is the first, the write's meta-blocks, and libbrotli's flush marker (the empty metadata
+ * meta-block), so any prefix of writes followed by the byte 0x03 is a complete stream.  Copies do not reach into
+ * earlier writes.  nx_brotli_encoder_max_encoded_length(n) bytes of out always suffice; a write that does not
+ * fit out_cap returns NX_ERR_BROTLI_ENCODE_FULL and leaves the handle as it was.
+ * _close: the empty last meta-block (0x03), after the header if nothing was ever written; a second close
+ * returns 0.  _encode after _close returns 0 and no error (the reference's writer is gone by then and
+ * allocateBuffer answers an empty buffer, :136-139).  _error: the last failure's message.
+ */
+typedef struct nx_brotli_encoder nx_brotli_encoder;
+int32_t nx_brotli_encoder_check(int32_t quality, int32_t lgwin, int32_t mode);
+nx_brotli_encoder* nx_brotli_encoder_new(int32_t quality, int32_t lgwin, int32_t mode);
+void nx_brotli_encoder_free(nx_brotli_encoder* e);
+const char* nx_brotli_encoder_error(nx_brotli_encoder* e);
+size_t nx_brotli_encoder_max_encoded_length(size_t n);
+int64_t nx_brotli_encoder_encode(nx_brotli_encoder* e, const uint8_t* in, size_t n, uint8_t* out, size_t out_cap);
+int64_t nx_brotli_encoder_close(nx_brotli_encoder* e, uint8_t* out, size_t out_cap);
+int32_t nx_brotli_encoder_is_closed(nx_brotli_encoder* e);
 
 /*
  * ZstdEncoder.  nx_zstd_encoder_new(level, block_size, max_encode_size) restates the constructor's three

@@ -151,6 +151,16 @@
 #define NX_ERR_LZMA_FAST_BYTES            (-142)
 /* This library's own: the stream does not fit the output slot. */
 #define NX_ERR_LZMA_ENCODE_FULL           (-143)
+/* Brotli stream encoding (nx_brotli_encode_batch, nx_brotli_encode_host, BrotliEncoder); the ranges are the ones
+ * brotli4j's Encoder.Parameters accepts (setQuality, setWindow, setMode). */
+/* "quality should be in range [0, 11], or -1" */
+#define NX_ERR_BROTLI_QUALITY             (-150)
+/* "lgwin should be in range [10, 24], or -1" */
+#define NX_ERR_BROTLI_LGWIN               (-151)
+/* mode: GENERIC (0), TEXT (1) or FONT (2) */
+#define NX_ERR_BROTLI_MODE                (-152)
+/* This library's own: the stream does not fit the output slot. */
+#define NX_ERR_BROTLI_ENCODE_FULL         (-153)
 
 /* Device frame scan (nx_snappy_frame_scan_batch), one code per SnappyFrameDecoder throw site: */
 /* :116-118  "Unexpected length of stream identifier: %d" */

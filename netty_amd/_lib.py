@@ -27,6 +27,12 @@ class LzmaEncodeStats(C.Structure):  # nx_lzma_encode_stats
                 ("reps", C.c_uint64 * 4), ("carries", C.c_uint64), ("max_pending_ff", C.c_uint64), ("max_carry_ff", C.c_uint64)]
 
 
+class BrotliEncodeStats(C.Structure):  # nx_brotli_encode_stats
+    _fields_ = [("compressed_blocks", C.c_uint64), ("uncompressed_blocks", C.c_uint64), ("commands", C.c_uint64), ("literals", C.c_uint64),
+                ("ring_copies", C.c_uint64), ("implicit_copies", C.c_uint64), ("split_copies", C.c_uint64), ("simple_codes", C.c_uint64 * 4),
+                ("complex_codes", C.c_uint64), ("limited_codes", C.c_uint64), ("max_depth_unlimited", C.c_uint64)]
+
+
 class NxMsg(C.Structure):
     _fields_ = [("data", C.POINTER(C.c_uint8)), ("len", C.c_size_t)]
 
@@ -110,6 +116,17 @@ _SIGS = {
     "nx_lzma_frame_encoder_error": (C.c_char_p, [vp]),
     "nx_lzma_frame_max_encoded_length": (sz, [sz]),
     "nx_lzma_frame_encoder_encode": (i64, [vp, C.c_char_p, sz, vp, sz]),
+    "nx_brotli_max_compressed_length": (sz, [sz]),
+    "nx_brotli_encode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, i32, vp]),
+    "nx_brotli_encode_host": (i64, [C.c_char_p, sz, i32, vp, sz, vp]),
+    "nx_brotli_encoder_check": (i32, [i32, i32, i32]),
+    "nx_brotli_encoder_new": (vp, [i32, i32, i32]),
+    "nx_brotli_encoder_free": (None, [vp]),
+    "nx_brotli_encoder_error": (C.c_char_p, [vp]),
+    "nx_brotli_encoder_max_encoded_length": (sz, [sz]),
+    "nx_brotli_encoder_encode": (i64, [vp, C.c_char_p, sz, vp, sz]),
+    "nx_brotli_encoder_close": (i64, [vp, vp, sz]),
+    "nx_brotli_encoder_is_closed": (i32, [vp]),
     "nx_inflate_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]),
     "nx_lzf_encode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, vp]),
     "nx_lzf_decode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, vp]),

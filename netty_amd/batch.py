@@ -25,7 +25,7 @@ def _chk(rc, what):
 
 
 # Shared device workspaces (include/netty_amd.h NX_WS_*; csrc/workspace.hpp)
-WS_SNAPPY_ENC, WS_LZ4_ENC, WS_FASTLZ_ENC, WS_LZF_ENC, WS_DEC_RECORDS, WS_LZ4HC_ENC, WS_DEFLATE_ENC, WS_ZSTD_ENC, WS_ZSTD_DEC, WS_BZIP2_DEC, WS_BZIP2_ENC, WS_LZMA_ENC = range(12)
+WS_SNAPPY_ENC, WS_LZ4_ENC, WS_FASTLZ_ENC, WS_LZF_ENC, WS_DEC_RECORDS, WS_LZ4HC_ENC, WS_DEFLATE_ENC, WS_ZSTD_ENC, WS_ZSTD_DEC, WS_BZIP2_DEC, WS_BZIP2_ENC, WS_LZMA_ENC, WS_BROTLI_ENC = range(13)
 
 
 def workspace_info(kind: int) -> tuple[int, int]:
@@ -571,6 +571,45 @@ def lzma_encode_host(data: bytes, lc: int = 3, lp: int = 0, pb: int = 2, dict_si
     if stats:
         res.append({"literals": S.literals, "matched_literals": S.matched_literals, "matches": S.matches, "short_reps": S.short_reps,
                     "reps": list(S.reps), "carries": S.carries, "max_pending_ff": S.max_pending_ff, "max_carry_ff": S.max_carry_ff})
+    if guard:
+        res.append(buf.raw[cap:cap + guard])
+    return tuple(res)
+
+
+def brotli_max_compressed_length(n: int) -> int:
+    """nx_brotli_max_compressed_length: n + 4 * ceil(n / 65536) + 3, a proven bound (csrc/brotli_encode_core.hpp)."""
+    return _lib.load().nx_brotli_max_compressed_length(int(n))
+
+
+def brotli_encode(inp, in_off, in_len, out, out_off, out_cap, lgwin: int = -1):
+    """One Brotli stream per item (nx_brotli_encode_batch): item i = inp[in_off[i] : + in_len[i]] becomes a complete
+    RFC 7932 stream in out[out_off[i] : + out_cap[i]].  Returns (out_len, status): the stream's size and 0 or
+    NX_ERR_BROTLI_ENCODE_FULL (-153) per item.  out_cap is copied into out_len, which the call takes as
+    capacities.  lgwin outside -1 and 10-24 raises; the call reads in_len back, so it synchronises the current
+    stream."""
+    n = in_len.numel()
+    dev = inp.device
+    out_len = out_cap.to(device=dev, dtype=torch.int32, copy=True)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    _chk(_lib.load().nx_brotli_encode_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_len), _ptr(status),
+                                            n, int(lgwin), _stream()),
+         "nx_brotli_encode_batch")
+    return out_len, status
+
+
+def brotli_encode_host(data: bytes, lgwin: int = -1, out_cap=None, stats: bool = False, guard: int = 0):
+    """nx_brotli_encode_host on host bytes: (status, stream) of one item, by the kernels' format functions on the
+    CPU; out_cap defaults to brotli_max_compressed_length.  stats=True appends the nx_brotli_encode_stats as a
+    dict; guard > 0 appends the `guard` bytes behind out_cap (0xA5 before the call)."""
+    import ctypes as C
+    data = bytes(data)
+    cap = brotli_max_compressed_length(len(data)) if out_cap is None else int(out_cap)
+    buf = C.create_string_buffer(b"\xa5" * (cap + guard + 1), cap + guard + 1)
+    S = _lib.BrotliEncodeStats()
+    r = _lib.load().nx_brotli_encode_host(data, len(data), int(lgwin), C.cast(buf, C.c_void_p), cap, C.byref(S) if stats else None)
+    res = [0 if r >= 0 else int(r), buf.raw[:r] if r >= 0 else b""]
+    if stats:
+        res.append({k: (list(getattr(S, k)) if k == "simple_codes" else getattr(S, k)) for k, _ in S._fields_})
     if guard:
         res.append(buf.raw[cap:cap + guard])
     return tuple(res)

@@ -352,6 +352,20 @@ struct nx_lzma_frame_encoder {
     std::string err;  // the last failure's message
 };
 
+// BrotliEncoder (handlers.cpp): the constructor's settings, "header written" and "closed".  No distance is kept:
+// the encoder's ring starts empty in every write (brotli_encode_core.hpp).
+struct nx_brotli_encoder {
+    nx::h::Gpu g;
+    int32_t quality = 4, lgwin = 22, mode = 1;
+    bool started = false, closed = false;
+    std::string err;  // the last failure's message
+};
+namespace nx {
+// brotli.hip: nx_brotli_encode_batch with the flags of brotli_encode_core.hpp (header or not, last block or flush marker)
+int32_t brotli_encode_items(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
+                            uint32_t* out_len, int32_t* status, uint32_t n, int32_t lgwin, uint32_t flags, void* stream);
+}  // namespace nx
+
 // Bzip2Encoder (handlers.cpp): the planner's state and the raw bytes of the open block on the host, the bits
 // that do not fill a 32-bit word and the stream CRC between launches.
 struct nx_bzip2_encoder {

@@ -47,6 +47,10 @@ extern "C" const char* nx_status_string(int32_t s) {
         case NX_ERR_LZMA_DICT_SIZE: return "dictionarySize (expected: 0+)";
         case NX_ERR_LZMA_FAST_BYTES: return "numFastBytes (expected: 5-273)";
         case NX_ERR_LZMA_ENCODE_FULL: return "the LZMA stream does not fit the output slot";
+        case NX_ERR_BROTLI_QUALITY: return "quality should be in range [0, 11], or -1";
+        case NX_ERR_BROTLI_LGWIN: return "lgwin should be in range [10, 24], or -1";
+        case NX_ERR_BROTLI_MODE: return "mode should be GENERIC, TEXT or FONT";
+        case NX_ERR_BROTLI_ENCODE_FULL: return "the Brotli stream does not fit the output slot";
         case NX_ERR_LZ4_ENCODE_FINISHED: return "encode finished and not enough space to write remaining data";
         case NX_ERR_SNAPPY_PREAMBLE_TOO_LONG: return "Preamble is greater than 4 bytes";
         case NX_ERR_SNAPPY_OFFSET_ZERO: return "Offset is less than minimum permissible value";

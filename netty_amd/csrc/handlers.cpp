@@ -42,6 +42,7 @@
 #include "frame_parse.hpp"
 #include "handles.hpp"
 #include "alt_frames.hpp"
+#include "brotli_encode_core.hpp"
 #include "bzip2_decode_split.hpp"
 
 extern "C" int32_t nx_snappy_decode_batch(const uint8_t*, const uint64_t*, const uint32_t*, uint8_t*, const uint64_t*,
@@ -899,6 +900,78 @@ extern "C" int64_t nx_lzma_frame_encoder_encode(nx_lzma_frame_encoder* e, const 
     if (it.st[0] != NX_OK) return fail(it.st[0]);
     if (!it.copy_item(0, out) || !e->g.sync()) return fail(NX_ERR_HIP);
     return (int64_t)it.len[0];
+}
+
+// ------------------------------------------------------------------ BrotliEncoder
+// BrotliEncoder.java:47-230: one stream per channel, every write compressed and flushed (Writer.write, :205-216).
+extern "C" int32_t nx_brotli_encoder_check(int32_t quality, int32_t lgwin, int32_t mode) {
+    if (quality < -1 || quality > 11) return NX_ERR_BROTLI_QUALITY;
+    if (lgwin != -1 && (lgwin < 10 || lgwin > 24)) return NX_ERR_BROTLI_LGWIN;
+    if (mode < 0 || mode > 2) return NX_ERR_BROTLI_MODE;
+    return NX_OK;
+}
+
+extern "C" nx_brotli_encoder* nx_brotli_encoder_new(int32_t quality, int32_t lgwin, int32_t mode) {
+    if (nx_brotli_encoder_check(quality, lgwin, mode) != NX_OK) return nullptr;
+    auto* e = new nx_brotli_encoder();
+    // a write is one item: one table slot
+    if (!e->g.ok || nx::ws_hold(nx::WsKind::BrotliEnc, e->g.dev, 1u, e->g.s) != NX_OK) {
+        delete e;
+        return nullptr;
+    }
+    e->g.held |= 1u << (int)nx::WsKind::BrotliEnc;
+    e->quality = quality;
+    e->lgwin = lgwin == -1 ? 22 : lgwin;
+    e->mode = mode;
+    return e;
+}
+extern "C" void nx_brotli_encoder_free(nx_brotli_encoder* e) { delete e; }
+extern "C" const char* nx_brotli_encoder_error(nx_brotli_encoder* e) { return last_error(e); }
+extern "C" int32_t nx_brotli_encoder_is_closed(nx_brotli_encoder* e) { return e && e->closed ? 1 : 0; }
+// a write: the header (under a byte), the bound, which has room for the flush marker's bits, and one byte to spare
+extern "C" size_t nx_brotli_encoder_max_encoded_length(size_t n) { return 1u + nx_brotli_max_compressed_length(n) + 1u; }
+
+extern "C" int64_t nx_brotli_encoder_encode(nx_brotli_encoder* e, const uint8_t* in, size_t n, uint8_t* out, size_t out_cap) {
+    const nx::NoGrowScope no_grow;
+    if (!e || (!in && n) || (!out && out_cap) || n > (256u << 20)) return NX_ERR_INVALID_ARG;
+    if (n == 0 || e->closed) return 0;  // :125-127 an unreadable message; :136-139 no writer any more
+    auto fail = [&](int64_t r) {
+        if (r < 0) e->err = r == NX_ERR_BROTLI_ENCODE_FULL ? "the Brotli write does not fit the output buffer" : nx_status_string((int32_t)r);
+        return r;
+    };
+    const size_t bound = nx_brotli_encoder_max_encoded_length(n);
+    const uint32_t cap = (uint32_t)(out_cap < bound ? out_cap : bound);  // the slot the kernel may write
+    EncodeItems it(e->g);
+    it.add(0, (uint32_t)n, (bound + 15) / 16 * 16);
+    int32_t r = it.stage(in, n);
+    if (r != NX_OK) return fail(r);
+    if (!e->g.h2d(e->g.out_len.p, &cap, 4)) return fail(NX_ERR_HIP);
+    r = nx::brotli_encode_items(it.d_in(), it.d_in_off(), it.d_in_len(), it.d_out(), it.d_out_off(), it.d_out_len(), it.d_status(), 1u,
+                                e->lgwin, (e->started ? 0u : nx::brotli::kFlagHeader) | nx::brotli::kFlagFlush, e->g.s);
+    if (r != NX_OK) return fail(r);
+    if (!it.fetch(true)) return fail(NX_ERR_HIP);
+    if (it.st[0] != NX_OK) return fail(it.st[0]);
+    if (!it.copy_item(0, out) || !e->g.sync()) return fail(NX_ERR_HIP);
+    e->started = true;
+    return (int64_t)it.len[0];
+}
+
+extern "C" int64_t nx_brotli_encoder_close(nx_brotli_encoder* e, uint8_t* out, size_t out_cap) {
+    if (!e || (!out && out_cap)) return NX_ERR_INVALID_ARG;
+    if (e->closed) return 0;
+    int64_t r = 1;
+    if (e->started) {
+        if (out_cap < 1u) r = NX_ERR_BROTLI_ENCODE_FULL;
+        else out[0] = 0x03;  // ISLAST 1, ISLASTEMPTY 1 on a byte boundary, which every write ends on
+    } else {
+        r = nx_brotli_encode_host(nullptr, 0, e->lgwin, out, out_cap, nullptr);  // the header and the last block
+    }
+    if (r < 0) {
+        e->err = nx_status_string((int32_t)r);
+        return r;
+    }
+    e->closed = true;
+    return r;
 }
 
 // ------------------------------------------------------------------ Bzip2Encoder

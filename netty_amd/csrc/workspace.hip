@@ -252,6 +252,7 @@ extern "C" int32_t nx_workspaces_trim(void) {
             W.cap = 0;  // a reserve's cap lasts until its workspace is freed
             const hipError_t e = nx::ws_drop(W);
             if (k == (int)nx::WsKind::LzmaEnc) nx::lzma_arena_drop(dev);
+            if (k == (int)nx::WsKind::BrotliEnc) nx::brotli_arena_drop(dev);
             if (e != hipSuccess) r = nx_hip_fail(e, __FILE__, __LINE__ + k * 1000);  // line + 1000 * kind under NX_HIP_DEBUG
         }
     }

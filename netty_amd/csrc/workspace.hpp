@@ -20,7 +20,7 @@
 
 namespace nx {
 
-enum class WsKind : int { SnappyEnc = 0, Lz4Enc, FastLzEnc, LzfEnc, DecRecords, Lz4HcEnc, DeflateEnc, ZstdEnc, ZstdDec, Bzip2Dec, Bzip2Enc, LzmaEnc, Count };
+enum class WsKind : int { SnappyEnc = 0, Lz4Enc, FastLzEnc, LzfEnc, DecRecords, Lz4HcEnc, DeflateEnc, ZstdEnc, ZstdDec, Bzip2Dec, Bzip2Enc, LzmaEnc, BrotliEnc, Count };
 
 // Table geometry per encoder kind (entry bytes, log2 entries per table, waves per CU of its launch);
 // each codec static_asserts its own constants against this.
@@ -47,6 +47,7 @@ struct WsSpec {
 // kBzip2EncGroupsPerCu workgroups per CU.
 // LzmaEnc: 512 KiB per item in flight (65 536 stamped hash entries of the matcher; lzma.hip), one item per slot and
 // launch pair as ZstdEnc; the items' sequence words live in an arena of their own, sized per call from the lengths.
+// BrotliEnc: the same geometry for the Brotli matcher (brotli.hip), with a sequence arena of its own.
 #ifndef NX_LZ4_WPCU  // build options for A/B runs of the alt encoders' occupancy (scripts/build_lib_variant.sh; LZ4 at 20: level)
 #define NX_LZ4_WPCU 16
 #endif
@@ -56,7 +57,7 @@ struct WsSpec {
 #ifndef NX_LZF_WPCU  // LZF: 16 waves per CU measured level with 8 (profiles/r06/s4), so the smaller workspace stays
 #define NX_LZF_WPCU 8
 #endif
-constexpr WsSpec kWsSpec[] = {{8, 14, 20}, {8, 13, NX_LZ4_WPCU}, {8, 13, NX_FLZ_WPCU}, {8, 14, NX_LZF_WPCU}, {0, 0, 0}, {8, 15, 2}, {8, 14, 16}, {8, 16, 16}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {8, 16, 16}};
+constexpr WsSpec kWsSpec[] = {{8, 14, 20}, {8, 13, NX_LZ4_WPCU}, {8, 13, NX_FLZ_WPCU}, {8, 14, NX_LZF_WPCU}, {0, 0, 0}, {8, 15, 2}, {8, 14, 16}, {8, 16, 16}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {8, 16, 16}, {8, 16, 16}};
 static_assert(sizeof(kWsSpec) / sizeof(kWsSpec[0]) == (size_t)WsKind::Count, "one spec per kind");
 constexpr size_t kDecSlotBytes = 16384u * 4u + 8u;  // records of one frame + its count and length
 #ifndef NX_DEC_MAX_FRAMES  // build option for A/B runs (scripts/build_lib_variant.sh)
@@ -113,6 +114,8 @@ LaneGrid ws_grid(WsKind k, uint32_t n, int cus, size_t have);
 
 // lzma.hip: free the device's sequence arena (the caller holds the LzmaEnc workspace's lock and has waited for its users)
 void lzma_arena_drop(int dev);
+// brotli.hip: the same for the Brotli encoder's arena under the BrotliEnc workspace
+void brotli_arena_drop(int dev);
 
 struct NoGrowScope {
     NoGrowScope();

@@ -382,6 +382,48 @@ class LzmaFrameEncoder(_Encoder):
         return bytes(out[:r])
 
 
+class BrotliEncoder(_Encoder):
+    """BrotliEncoder.java:47-230 over the GPU Brotli encoder: one stream per channel, every write compressed and
+    flushed.  encode() of an empty message returns b"" and changes nothing; any other returns whole bytes that
+    end in libbrotli's flush marker (the first begin with the WBITS header), so the writes so far plus b"\\x03"
+    are always a complete stream.  finish_encode() (the handler's close) returns the last block (after the header, if
+    nothing was written), a second one b"", and encode() after it b"" as the reference's allocateBuffer does.  quality (-1, 0-11),
+    window (-1, 10-24) and mode are brotli4j's Encoder.Parameters with BrotliOptions.DEFAULT as defaults; quality
+    and mode are checked and do not change the bytes (this encoder parses greedily).  Copies do not reach into
+    earlier writes."""
+
+    _free = "nx_brotli_encoder_free"
+    GENERIC, TEXT, FONT = 0, 1, 2  # Encoder.Mode
+
+    def __init__(self, quality: int = 4, window: int = -1, mode: int = 1):
+        if quality < -1 or quality > 11:
+            raise ValueError("quality should be in range [0, 11], or -1")
+        if window != -1 and (window < 10 or window > 24):
+            raise ValueError("lgwin should be in range [10, 24], or -1")
+        if mode not in (self.GENERIC, self.TEXT, self.FONT):
+            raise ValueError("mode should be GENERIC, TEXT or FONT")
+        self.quality, self.window, self.mode = int(quality), int(window), int(mode)
+        self._h = _new(_lib.load().nx_brotli_encoder_new(self.quality, self.window, self.mode), "BrotliEncoder")
+
+    def _ret_or_raise(self, r, out):
+        if r < 0:
+            err = _lib.load().nx_brotli_encoder_error(self._h)
+            raise CompressionException(err.decode() if err else _lib.status_string(r))
+        return bytes(out[:r])
+
+    def encode(self, data: bytes) -> bytes:
+        cap = _lib.load().nx_brotli_encoder_max_encoded_length(len(data))
+        out = (C.c_uint8 * cap)()
+        return self._ret_or_raise(_lib.load().nx_brotli_encoder_encode(self._h, data, len(data), out, cap), out)
+
+    def finish_encode(self) -> bytes:
+        out = (C.c_uint8 * 8)()
+        return self._ret_or_raise(_lib.load().nx_brotli_encoder_close(self._h, out, 8), out)
+
+    def is_closed(self) -> bool:
+        return bool(_lib.load().nx_brotli_encoder_is_closed(self._h))
+
+
 class Bzip2Encoder(_Encoder):
     """Bzip2Encoder.java:96-228 over the GPU bzip2 encoder's split path: one stream over any number of writes,
     the same bytes however the writes slice the input.  The first encode() writes "BZh" and the level digit;
