@@ -7,7 +7,7 @@
 // rule, the walker and the meta-block encoder are in brotli_encode_core.hpp, which nx_brotli_encode_host runs
 // on the CPU; the kernels must write the host's bytes, and the GPU tests compare them.
 //
-//   pass 1, k_brotli_match, one lane per item on the lane grid of the other alt encoders: match_item over a
+//   pass 1, k_seq_match<Match> (seq_stage.hpp), one lane per item on the lane grid of the other alt encoders: match_item over a
 //     stamped hash table of 65 536 entries (stamp << 32 | position) in the item's workspace slot.  It writes
 //     one 64-bit word per sequence (literal run, copy length, distance) to the item's area of the sequence
 //     arena.  Literal bytes stay in the input, where pass 2 reads them.
@@ -29,15 +29,15 @@
 //     here by kernel-only code (next_chunk and the scan, sort and emit rounds) and checked byte for byte against
 //     the host's scan_block, sort_symbols and step_command by tests/test_gpu_brotli_encode.py.
 //
-// The sequence arena is one allocation per device beside the NX_WS_BROTLI_ENC tables: an item of n bytes takes
-// 16 + 8 * seq_cap(n) bytes of it.  The host reads in_len back, lays the areas out and cuts the batch into
-// launch pairs whose items fit the table slots and kArenaMax bytes of arena; a call therefore synchronises its
-// stream once, before its first launch.
+// The sequence arena is the side allocation of the NX_WS_BROTLI_ENC workspace, freed whenever its tables are: an
+// item of n bytes takes 16 + 8 * seq_cap(n) bytes of it.  The host reads in_len back, lays the areas out and cuts
+// the batch into launch pairs whose items fit the table slots and kWsAreaMax bytes of arena (WsAreaCut,
+// workspace.hpp); a call therefore synchronises its stream once, before its first launch.
 #include <algorithm>
-#include <vector>
 #include "alt_frames.hpp"
 #include "brotli_encode_core.hpp"
 #include "nx_common.hpp"
+#include "seq_stage.hpp"
 #include "workspace.hpp"
 
 namespace nx {
@@ -45,53 +45,29 @@ namespace brotli {
 
 constexpr uint32_t kMaxItem = 256u << 20;
 constexpr uint32_t kSlotBytes = 8u << kHashLog;
-constexpr uint32_t kStageBytes = 2048, kLine = 128, kCtrlBytes = 32;
+constexpr uint32_t kStageBytes = 2048, kLine = kSeqLine, kCtrlBytes = 32;
 constexpr uint32_t kWorkBytes = (uint32_t)((sizeof(Work) + 15u) & ~(size_t)15);
 constexpr uint32_t kLdsBytes = kStageBytes + kCtrlBytes + kWorkBytes;
 static_assert(kLdsBytes <= 20480u, "eight waves of a CU share 160 KiB");
-__host__ __device__ inline size_t area_bytes(size_t n) { return (16u + 8u * seq_cap(n) + 15u) & ~(size_t)15; }
 
-// ---------------------------------------------------------------------------------------- pass 1
-template <bool SPREAD>
-__global__ void __launch_bounds__(256) k_brotli_match(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
-                                                      const uint32_t* __restrict__ in_len, uint32_t n, uint8_t* __restrict__ tables,
-                                                      uint32_t stamp, uint8_t* __restrict__ arena, const uint64_t* __restrict__ aoff,
-                                                      uint32_t lgwin) {
-    uint32_t tid, nthreads;
-    if (!chunk_slot<SPREAD>(tid, nthreads)) return;
-    if (tid >= n) return;  // one item per slot: its sequences stay in the arena for pass 2
-    const uint32_t len = in_len[tid];
-    uint64_t* area = reinterpret_cast<uint64_t*>(arena + aoff[tid]);
-    uint32_t ns = ~0u;
-    if (len <= kMaxItem)
-        ns = match_item(in + in_off[tid], len, lgwin, reinterpret_cast<uint64_t*>(tables + (size_t)tid * kSlotBytes), stamp, area + 2,
-                        seq_cap(len));
-    area[0] = ns;
-}
-
-// ---------------------------------------------------------------------------------------- pass 2
-// The item's output.  Positions count from `origin`, the 128-byte line holding the slot's first byte.  The LDS
-// ring is a bit ring: byte `p` of the output lives at ring[p & (kStageBytes - 1)] from the moment any of its
-// bits is known until its line is stored, and every ring byte at or beyond `at` that no bit has reached is
-// zero (the ring is cleared per item and again behind every stored piece), so lanes may OR bits in.  Lane 0's
-// own bytes (the core's header and code descriptions) are stored whole at `at`.  A round adds at most
-// kChunkBytes to under a line left from the round before, so the ring (2 KiB) is never passed; the direct store
-// below is the guard for that, not a path.
-struct StageSink {
-    uint8_t* ring;
-    uint8_t* origin;
-    uint32_t at, flushed, end;  // end: the slot's capacity as a position
-    bool full;
-    __device__ __forceinline__ void put(uint8_t b) {
-        if (at >= end) {
-            full = true;
-            return;
-        }
-        if (at - flushed < kStageBytes) ring[at & (kStageBytes - 1u)] = b;
-        else origin[at] = b;
-        ++at;
+// pass 1: k_seq_match's codec; its parameter is lgwin
+struct Match {
+    static constexpr uint32_t kMaxItem = brotli::kMaxItem, kSlotBytes = brotli::kSlotBytes;
+    static __device__ __forceinline__ size_t seq_cap(size_t n) { return brotli::seq_cap(n); }
+    static __device__ __forceinline__ uint32_t match_item(const uint8_t* in, uint32_t n, uint32_t lgwin, uint64_t* table, uint32_t stamp,
+                                                          uint64_t* seq, size_t cap) {
+        return brotli::match_item(in, n, lgwin, table, stamp, seq, cap);
     }
 };
+
+// ---------------------------------------------------------------------------------------- pass 2
+// The item's output.  The LDS ring (seq_stage.hpp) is a bit ring here: byte `p` of the output lives at
+// ring[p & (kStageBytes - 1)] from the moment any of its bits is known until its line is stored, and every ring
+// byte at or beyond `at` that no bit has reached is zero (the ring is cleared per item and again behind every
+// stored piece), so lanes may OR bits in.  Lane 0's own bytes (the core's header and code descriptions) are
+// stored whole at `at`.  A round adds at most kChunkBytes to under a line left from the round before, so the
+// ring (2 KiB) is never passed; the sink's direct store is the guard for that, not a path.
+using Sink = StageSink<kStageBytes>;
 
 // A chunk of a meta-block's commands, cut by lane 0 for the wave: up to 64 records with at most kChunkLits
 // literals between them.  A record is the bits before its literals (the command symbol and the insert and copy
@@ -116,7 +92,7 @@ static_assert(sizeof(Recs) <= sizeof(Work::node_w) && offsetof(Work, node_w) % 1
 
 // Lane 0: the next chunk of the meta-block from walker w and ring r (the scan's or the emitter's) into R; emit:
 // with the bits, which need the block's codes; else the scan, which adds up the extra bits.  Returns the records.
-__device__ __forceinline__ uint32_t next_chunk(Encoder<StageSink>& E, Walk& w, Ring& r, bool emit, Recs* R) {
+__device__ __forceinline__ uint32_t next_chunk(Encoder<Sink>& E, Walk& w, Ring& r, bool emit, Recs* R) {
     const Work* W = E.W;
     uint32_t cnt = 0, lits = 0;
     while (cnt < 64u) {
@@ -185,24 +161,6 @@ __device__ __forceinline__ void or_bits64(uint32_t* ringw, uint32_t bit, uint64_
     or_bits(ringw, bit + lo, (uint32_t)(v >> 32), nb - lo);
 }
 
-// All lanes: store the ring's bytes [from, to) (to - from <= kStageBytes), 16 bytes a lane where a piece is whole,
-// and clear them in the ring.
-__device__ __forceinline__ void flush_ring(uint8_t* ring, uint8_t* origin, uint32_t from, uint32_t to, uint32_t lane) {
-    for (uint32_t c = (from & ~15u) + lane * 16u; c < to; c += 64u * 16u) {
-        const uint32_t lo = c < from ? from : c, hi = c + 16u < to ? c + 16u : to;
-        if (hi - lo == 16u) {
-            uint4* piece = reinterpret_cast<uint4*>(ring + (c & (kStageBytes - 1u)));
-            *reinterpret_cast<uint4*>(origin + c) = *piece;
-            *piece = make_uint4(0, 0, 0, 0);
-        } else {
-            for (uint32_t b = lo; b < hi; ++b) {
-                origin[b] = ring[b & (kStageBytes - 1u)];
-                ring[b & (kStageBytes - 1u)] = 0;
-            }
-        }
-    }
-}
-
 enum : uint32_t { kModeNone = 0, kModeClear, kModeScan, kModeSort, kModeEmit, kModeRaw };
 
 __global__ void __launch_bounds__(64) k_brotli_emit(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
@@ -232,8 +190,8 @@ __global__ void __launch_bounds__(64) k_brotli_emit(const uint8_t* __restrict__ 
         uint8_t* dst = out + out_off[c];
         const uint32_t lead = (uint32_t)((uintptr_t)dst & (kLine - 1u));
         uint8_t* origin = dst - lead;
-        const StageSink sink = {ring, origin, lead, lead, lead + cap, false};
-        Encoder<StageSink> E;
+        const Sink sink = {ring, origin, lead, lead, lead + cap, false};
+        Encoder<Sink> E;
         for (uint32_t i = lane; i < kStageBytes / 4u; i += 64u) ringw[i] = 0;
         if (lane == 0u) E.init(work, sink, nullptr, src, len, area + 2, ns, lgwin, flags);
         __syncthreads();
@@ -244,7 +202,7 @@ __global__ void __launch_bounds__(64) k_brotli_emit(const uint8_t* __restrict__ 
             // lane 0: what this round is
             if (lane == 0u) {
                 uint32_t mode = kModeNone, cnt = 0;
-                if (E.state == Encoder<StageSink>::kBlock) {
+                if (E.state == Encoder<Sink>::kBlock) {
                     if (!scanning) {
                         E.open_block();
                         scanning = 1;
@@ -267,11 +225,11 @@ __global__ void __launch_bounds__(64) k_brotli_emit(const uint8_t* __restrict__ 
                         }
                     }
                     cnt = mode == kModeSort ? scanning - 2u : cnt;
-                } else if (E.state == Encoder<StageSink>::kCommands) {
+                } else if (E.state == Encoder<Sink>::kCommands) {
                     cnt = next_chunk(E, E.w, E.r, true, R);
                     mode = kModeEmit;
                     or_bits(ringw, E.out.at * 8u, (uint32_t)E.acc, E.nacc);  // the bits of the byte that is not whole yet
-                } else if (E.state == Encoder<StageSink>::kRaw) {
+                } else if (E.state == Encoder<Sink>::kRaw) {
                     const uint32_t left = E.mb_end - E.raw_at, room = E.out.end - E.out.at;
                     cnt = left < kRawRound ? left : kRawRound;
                     if (cnt > room) {
@@ -367,14 +325,14 @@ __global__ void __launch_bounds__(64) k_brotli_emit(const uint8_t* __restrict__ 
                         E.out.at = nat;
                         E.nacc = end_bit & 7u;
                         E.acc = E.nacc ? (ring[nat & (kStageBytes - 1u)] & ((1u << E.nacc) - 1u)) : 0u;
-                        if (!E.in_cmd && E.w.ip == E.mb_end) E.state = E.w.ip < E.n ? Encoder<StageSink>::kBlock : Encoder<StageSink>::kFinish;
+                        if (!E.in_cmd && E.w.ip == E.mb_end) E.state = E.w.ip < E.n ? Encoder<Sink>::kBlock : Encoder<Sink>::kFinish;
                     }
                 } else if (mode == kModeRaw) {
                     E.out.at += cnt;
                     E.raw_at += cnt;
                     if (E.raw_at == E.mb_end) {
                         E.w = E.w_end;  // the ring of distances keeps what it held
-                        E.state = E.w.ip < E.n ? Encoder<StageSink>::kBlock : Encoder<StageSink>::kFinish;
+                        E.state = E.w.ip < E.n ? Encoder<Sink>::kBlock : Encoder<Sink>::kFinish;
                     }
                 }
                 ctrl[0] = E.out.at;
@@ -384,47 +342,26 @@ __global__ void __launch_bounds__(64) k_brotli_emit(const uint8_t* __restrict__ 
             at = ctrl[0];
             fl = ctrl[1];
             // whole lines leave, and the rest with the last round; a byte that is not whole stays behind `at`
-            const bool over = at - flushed >= kStageBytes;  // never: see StageSink
+            const bool over = at - flushed >= kStageBytes;  // never: see Sink
             const uint32_t staged_end = over ? flushed + kStageBytes : at;
             const uint32_t to = fl || over ? staged_end : (staged_end & ~(kLine - 1u));
             if (to > flushed) {
-                flush_ring(ring, origin, flushed, to, lane);
+                flush_ring<kStageBytes, true>(ring, origin, flushed, to, lane);
                 flushed = over ? at : to;
             }
             if (lane == 0u) E.out.flushed = flushed;
             __syncthreads();
         }
-        if (lane == 0u) {
-            const bool ok = fl == 1u;
-            out_len[c] = ok ? at - lead : 0u;
-            status[c] = ok ? NX_OK : (fl & 2u) ? NX_ERR_BROTLI_ENCODE_FULL : NX_ERR_INTERNAL;
-        }
+        if (lane == 0u) seq_item_end(out_len, status, c, fl, at - lead, NX_ERR_BROTLI_ENCODE_FULL);
         __syncthreads();
     }
 }
 
-// The sequence arena of a device: grown under the NX_WS_BROTLI_ENC lease, dropped with that workspace.
-struct Arena {
-    uint8_t* p = nullptr;
-    size_t bytes = 0;
-};
-static Arena g_arena[64];
-
 }  // namespace brotli
 
-void brotli_arena_drop(int dev) {
-    brotli::Arena& A = brotli::g_arena[dev < 0 || dev >= 64 ? 0 : dev];
-    if (A.p) (void)hipFree(A.p);
-    A.p = nullptr;
-    A.bytes = 0;
-}
-
 namespace {
-constexpr uint32_t kMaxStamp = 0xFFFFFFF0u;
-// Most table slots the standalone entry grows the workspace to (8 GiB); a larger batch runs in sub-batches.
-constexpr size_t kMaxSlots = 16384;
-// Most arena bytes the sequence areas of one launch pair take, unless one item alone takes more.
-constexpr size_t kArenaMax = (size_t)4 << 30;
+// Stamps are 32 bits; at most 16 384 table slots (8 GiB) for a standalone call, a larger batch runs in sub-batches.
+constexpr WsPairSpec kPair = {WsKind::BrotliEnc, 0xFFFFFFF0u, 16384};
 constexpr WsSpec kSpec = kWsSpec[(int)WsKind::BrotliEnc];
 static_assert(((size_t)kSpec.entry_bytes << kSpec.lg) == brotli::kSlotBytes, "brotli slot geometry");
 }  // namespace
@@ -439,74 +376,21 @@ int32_t brotli_encode_items(const uint8_t* in, const uint64_t* in_off, const uin
     if (n == 0) return NX_OK;
     if (!in_off || !in_len || !out || !out_off || !out_len || !status) return NX_ERR_INVALID_ARG;
     const hipStream_t st = (hipStream_t)stream;
-    int dev = 0, cus = 256;
-    NX_HIP_CHECK(hipGetDevice(&dev));
-    NX_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    WsLease lease(WsKind::BrotliEnc, dev, st);
-    const size_t want = ws_want(WsKind::BrotliEnc, n, cus);
-    NX_HIP_CHECK(lease.acquire(want < kMaxSlots ? want : kMaxSlots));
-    SharedWs& W = lease.ws();
-    uint8_t* ws = static_cast<uint8_t*>(W.p);
-    // the lengths, on the host: the stream has waited for the workspace's earlier users, so after this
-    // synchronisation nothing reads the arena any more
-    std::vector<uint32_t> len(n);
-    NX_HIP_CHECK(hipMemcpyAsync(len.data(), in_len, (size_t)n * 4u, hipMemcpyDefault, st));
-    NX_HIP_CHECK(hipStreamSynchronize(st));
-    // launch pairs: as many items as the grid has slots, cut where the areas pass kArenaMax
-    struct Pair {
-        uint32_t base, m;
-        LaneGrid g;
-    };
-    std::vector<Pair> pairs;
-    std::vector<uint64_t> aoff(n);
-    const size_t head = ((size_t)n * 8u + 127u) & ~(size_t)127;
-    size_t need = 0;
-    for (uint32_t base = 0; base < n;) {
-        const uint32_t left = n - base;
-        const LaneGrid g = ws_grid(WsKind::BrotliEnc, left, cus, W.slots < kMaxSlots ? W.slots : kMaxSlots);
-        const uint32_t most = (uint32_t)(left < g.slots ? left : g.slots);
-        size_t used = 0;
-        uint32_t m = 0;
-        for (; m < most; ++m) {
-            const size_t a = area_bytes(len[base + m] <= kMaxItem ? len[base + m] : 0u);
-            if (m && used + a > kArenaMax) break;
-            aoff[base + m] = head + used;
-            used += a;
-        }
-        need = std::max(need, used);
-        pairs.push_back({base, m, g});
-        base += m;
-    }
-    Arena& A = g_arena[dev < 0 || dev >= 64 ? 0 : dev];
-    if (A.bytes < head + need) {
-        brotli_arena_drop(dev);
-        NX_HIP_CHECK(hipMalloc(&A.p, head + need));
-        A.bytes = head + need;
-    }
-    NX_HIP_CHECK(hipMemcpy(A.p, aoff.data(), (size_t)n * 8u, hipMemcpyHostToDevice));
-    const uint64_t* d_aoff = reinterpret_cast<const uint64_t*>(A.p);
+    WsAreaCut cut = {in_len, [](uint32_t len) { return area_bytes(seq_cap(len <= kMaxItem ? len : 0u)); }};
     // as many waves per CU as Work areas fit the 160 KiB of LDS, at most 8 (two per SIMD)
     const unsigned per_cu = std::min<unsigned>(8u, (160u << 10) / kLdsBytes);
-    for (const Pair& pr : pairs) {
-        const uint32_t base = pr.base, m = pr.m;
-        if (W.stamp + 1u >= kMaxStamp) {
-            NX_HIP_CHECK(hipMemsetAsync(W.p, 0, W.slots * (size_t)kSlotBytes, st));
-            W.stamp = 0;
-        }
-        W.stamp += 1u;
-        if (pr.g.spread)
-            hipLaunchKernelGGL(k_brotli_match<true>, dim3(pr.g.grid), dim3(pr.g.block), 0, st, in, in_off + base, in_len + base, m, ws,
-                               W.stamp, A.p, d_aoff + base, (uint32_t)lgwin);
-        else
-            hipLaunchKernelGGL(k_brotli_match<false>, dim3(pr.g.grid), dim3(pr.g.block), 0, st, in, in_off + base, in_len + base, m, ws,
-                               W.stamp, A.p, d_aoff + base, (uint32_t)lgwin);
-        NX_HIP_CHECK(hipGetLastError());
-        const unsigned waves = (unsigned)cus * per_cu;
-        hipLaunchKernelGGL(k_brotli_emit, dim3(m < waves ? m : waves), dim3(64), kLdsBytes, st, in, in_off + base, in_len + base, out,
-                           out_off + base, out_len + base, status + base, m, A.p, d_aoff + base, (uint32_t)lgwin, flags);
-        NX_HIP_CHECK(hipGetLastError());
-    }
-    return NX_OK;
+    return ws_pair_launch(
+        kPair, n, st, per_cu, &cut, true,
+        [&](uint32_t base, uint32_t m, const LaneGrid& g, SharedWs& W, uint32_t stamp) {
+            auto* k = g.spread ? k_seq_match<Match, true> : k_seq_match<Match, false>;
+            hipLaunchKernelGGL(k, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base, in_len + base, m, static_cast<uint8_t*>(W.p), stamp,
+                               static_cast<uint8_t*>(W.side), cut.d_aoff(W) + base, (uint32_t)lgwin);
+        },
+        [&](uint32_t base, uint32_t m, unsigned waves, SharedWs& W) {
+            hipLaunchKernelGGL(k_brotli_emit, dim3(waves), dim3(64), kLdsBytes, st, in, in_off + base, in_len + base, out, out_off + base,
+                               out_len + base, status + base, m, static_cast<const uint8_t*>(W.side), cut.d_aoff(W) + base, (uint32_t)lgwin,
+                               flags);
+        });
 }
 }  // namespace nx
 

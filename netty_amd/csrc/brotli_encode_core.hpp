@@ -52,24 +52,14 @@
 // shorter than 2 bytes becomes a literal, and a meta-block that ends in literals ends with a command whose
 // copy part (code 0) the decoder ignores.
 #pragma once
-#include <stdint.h>
-#include <stddef.h>
-#include <string.h>
-
-#ifndef NX_HD
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define NX_HD __host__ __device__ inline
-#else
-#define NX_HD inline
-#endif
-#endif
+#include "lz_seq_core.hpp"
 
 namespace nx {
 namespace brotli {
+using namespace lzseq;
 
-constexpr uint32_t kMbMax = 65536, kMinMatch = 4, kMaxCopy = 65536;
-constexpr uint32_t kHashLog = 16;
-constexpr uint32_t kRunBits = 23, kRunMax = (1u << kRunBits) - 1u, kLenBits = 17;
+constexpr uint32_t kMbMax = 65536, kMinMatch = kHashBytes, kMaxCopy = 65536;
+constexpr uint32_t kLenBits = 17;
 constexpr uint32_t kLit = 0, kCmd = 256, kDist = 960, kSyms = 1024;  // the three alphabets side by side
 constexpr uint32_t kNumCmd = 704, kNumDist = 64;
 constexpr uint32_t kFlagHeader = 1u, kFlagFlush = 2u;  // write the WBITS header; end in the flush marker, not the last block
@@ -104,35 +94,14 @@ struct Work {
     uint32_t unlimited;               // the deepest length of the last build before limiting
 };
 
-NX_HD uint32_t rd32(const uint8_t* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef uint32_t __attribute__((aligned(1))) u32u;
-    return *reinterpret_cast<const u32u*>(p);
-#else
-    uint32_t v;
-    memcpy(&v, p, 4);
-    return v;
-#endif
-}
-
-NX_HD uint32_t common_len(const uint8_t* a, const uint8_t* b, uint32_t maxlen) {
-    uint32_t l = 0;
-    while (l + 4u <= maxlen) {
-        const uint32_t x = rd32(a + l) ^ rd32(b + l);
-        if (x) return l + ((x & 0xFFu) ? 0u : (x & 0xFF00u) ? 1u : (x & 0xFF0000u) ? 2u : 3u);
-        l += 4u;
-    }
-    while (l < maxlen && a[l] == b[l]) ++l;
-    return l;
-}
-
 NX_HD uint32_t log2_floor(uint32_t v) { return 31u - (uint32_t)__builtin_clz(v); }
 
 // The item's sequences into seq[0, cap) by the rule in the header comment; table: 2^kHashLog entries
 // (stamp << 32 | position), an entry counts only with this call's stamp.  Returns the sequences written,
 // or ~0 if cap would be passed (seq_cap(n) never is).
 NX_HD uint32_t match_item(const uint8_t* in, uint32_t n, uint32_t lgwin, uint64_t* table, uint32_t stamp, uint64_t* seq, size_t cap) {
-    uint32_t ns = 0, ip = 0, run = 0;
+    SeqWriter out = {seq, cap, 0, 0};
+    uint32_t ip = 0;
     const uint64_t stag = (uint64_t)stamp << 32;
     const uint32_t far = max_distance(lgwin);
     while (ip < n) {
@@ -140,32 +109,22 @@ NX_HD uint32_t match_item(const uint8_t* in, uint32_t n, uint32_t lgwin, uint64_
         uint32_t len = 0, dist = 0;
         if (left >= kMinMatch) {
             const uint32_t w = rd32(in + ip);
-            const uint32_t h = (w * 2654435761u) >> (32u - kHashLog);
-            const uint64_t e = table[h];
-            table[h] = stag | ip;
-            const uint32_t cand = (uint32_t)e;
-            if ((e >> 32) == stamp && cand < ip && ip - cand <= far && rd32(in + cand) == w) {
+            const uint32_t cand = probe(table, stag, stamp, w, ip);
+            if (cand != kNone && ip - cand <= far && rd32(in + cand) == w) {
                 len = common_len(in + ip, in + cand, maxlen);
                 dist = ip - cand;
             }
         }
         if (len == 0u) {
             ++ip;
-            if (++run == kRunMax) {
-                if (ns >= cap) return ~0u;
-                seq[ns++] = run;
-                run = 0;
-            }
+            if (!out.literal()) return ~0u;
             continue;
         }
-        if (ns >= cap) return ~0u;
-        seq[ns++] = (uint64_t)run | ((uint64_t)len << kRunBits) | ((uint64_t)dist << (kRunBits + kLenBits));
-        run = 0;
-        const uint32_t end = ip + len;
-        for (uint32_t q = ip + 1u; q < end && q + kMinMatch <= n; ++q) table[(rd32(in + q) * 2654435761u) >> (32u - kHashLog)] = stag | q;
-        ip = end;
+        if (!out.match(((uint64_t)len << kRunBits) | ((uint64_t)dist << (kRunBits + kLenBits)))) return ~0u;
+        insert_span(table, stag, in, ip + 1u, ip + len, n);
+        ip += len;
     }
-    return ns;  // the literals after the last sequence are implied by n
+    return out.ns;  // the literals after the last sequence are implied by n
 }
 
 // ------------------------------------------------------------------------------------------ commands

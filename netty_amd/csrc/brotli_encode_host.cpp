@@ -2,27 +2,15 @@
 // nx_brotli_encode_host, a single-threaded encode of one item from the functions of brotli_encode_core.hpp:
 // the matcher, the walker and the meta-block encoder the kernels run, so the bytes are the GPU's.  It is the
 // CPU check of the format core and the GPU tests' second opinion.
-#include <stdlib.h>
 #include <string.h>
 #include <memory>
 #include <vector>
 #include "../../include/netty_amd.h"
 #include "brotli_encode_core.hpp"
+#include "encode_host.hpp"
 
-namespace {
 using namespace nx::brotli;
-
-struct HostSink {
-    uint8_t* out;
-    size_t cap, at;
-    bool full;
-    void put(uint8_t b) {
-        if (at < cap) out[at] = b;
-        else full = true;
-        ++at;
-    }
-};
-}  // namespace
+using nx::HostSink;
 
 extern "C" size_t nx_brotli_max_compressed_length(size_t n) { return max_stream_bytes(n); }
 
@@ -34,19 +22,17 @@ extern "C" int64_t nx_brotli_encode_host(const uint8_t* in, size_t n, int32_t lg
     static_assert(sizeof(nx_brotli_encode_stats) == sizeof(Stats), "stats layout");
     Stats st;
     memset(&st, 0, sizeof(st));
-    std::unique_ptr<uint64_t, decltype(&free)> table(static_cast<uint64_t*>(calloc((size_t)1 << kHashLog, 8)), &free);
     std::unique_ptr<Work> work(new Work());
     std::vector<uint64_t> seq(seq_cap(n));
-    if (!table) return NX_ERR_INTERNAL;
-    const uint32_t ns = match_item(in, (uint32_t)n, (uint32_t)lgwin, table.get(), 1u, seq.data(), seq.size());
-    if (ns == ~0u) return NX_ERR_INTERNAL;
+    uint32_t ns = 0;
+    if (!nx::host_match(seq, &ns, [&](uint64_t* table, uint32_t stamp, uint64_t* s, size_t cap) {
+            return match_item(in, (uint32_t)n, (uint32_t)lgwin, table, stamp, s, cap);
+        }))
+        return NX_ERR_INTERNAL;
     const HostSink sink = {out, out_cap, 0, false};
     Encoder<HostSink> E;
     E.init(work.get(), sink, &st, in, (uint32_t)n, seq.data(), ns, (uint32_t)lgwin, kFlagHeader);
-    for (uint64_t left = max_steps((uint32_t)n, ns); !E.done && !E.out.full; --left) {
-        if (left == 0u) return NX_ERR_INTERNAL;
-        E.step();
-    }
+    if (!nx::host_steps(E, E.out, max_steps((uint32_t)n, ns))) return NX_ERR_INTERNAL;
     if (stats) memcpy(stats, &st, sizeof(st));
     return E.out.full ? (int64_t)NX_ERR_BROTLI_ENCODE_FULL : (int64_t)E.out.at;
 }

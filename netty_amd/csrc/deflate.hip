@@ -547,7 +547,7 @@ __global__ void __launch_bounds__(64) k_deflate_emit_prefix(const uint8_t* __res
 }  // namespace nx
 
 namespace {
-constexpr uint32_t kMaxStamp = 0xFFFFu;
+constexpr nx::WsPairSpec kPair = {nx::WsKind::DeflateEnc, 0xFFFFu, 0};  // 16-bit stamps, as many slots as the grid asks for
 constexpr nx::WsSpec kSpec = nx::kWsSpec[(int)nx::WsKind::DeflateEnc];
 static_assert(((size_t)kSpec.entry_bytes << kSpec.lg) == nx::deflate::kSlotBytes, "deflate slot geometry");
 static_assert(nx::deflate::kTokCap * 2u + 8u + nx::deflate::kTokOff <= nx::deflate::kSlotBytes, "deflate token area");
@@ -573,52 +573,29 @@ int32_t deflate_encode(const uint8_t* in, const uint64_t* in_off, const uint32_t
     if (n == 0) return NX_OK;
     if (!in || !in_off || !in_len || !out || !out_off || !out_len || !status) return NX_ERR_INVALID_ARG;
     const hipStream_t st = (hipStream_t)stream;
-    int dev = 0, cus = 256;
-    NX_HIP_CHECK(hipGetDevice(&dev));
-    NX_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    nx::WsLease lease(nx::WsKind::DeflateEnc, dev, st);
-    NX_HIP_CHECK(lease.acquire(nx::ws_want(nx::WsKind::DeflateEnc, n, cus)));
-    nx::SharedWs& W = lease.ws();
-    uint8_t* ws = static_cast<uint8_t*>(W.p);
-    // a slot holds one chunk's tokens from pass 1 to pass 2: sub-batches of at most the slots
-    for (size_t base = 0; base < n;) {
-        const uint32_t left = (uint32_t)(n - base);
-        const nx::LaneGrid g = nx::ws_grid(nx::WsKind::DeflateEnc, left, cus, W.slots);
-        const uint32_t m = (uint32_t)(left < g.slots ? left : g.slots);
-        const uint32_t* pre = prefix_len ? prefix_len + base : nullptr;
-        if (level != 0) {
-            if (W.stamp + 1u >= kMaxStamp) {
-                NX_HIP_CHECK(hipMemsetAsync(W.p, 0, W.slots * (size_t)nx::deflate::kSlotBytes, st));
-                W.stamp = 0;
-            }
-            W.stamp += 1u;
-            if (pre) {
-                if (g.spread)
-                    hipLaunchKernelGGL(nx::deflate::k_deflate_match_prefix<true>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base,
-                                       in_len + base, pre, m, ws, W.stamp);
-                else
-                    hipLaunchKernelGGL(nx::deflate::k_deflate_match_prefix<false>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base,
-                                       in_len + base, pre, m, ws, W.stamp);
-            } else if (g.spread) {
-                hipLaunchKernelGGL(nx::deflate::k_deflate_match<true>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base,
-                                   in_len + base, m, ws, W.stamp);
+    using namespace nx::deflate;
+    // a slot holds one chunk's tokens from pass 1 to pass 2; level 0 stores, and runs no matcher
+    return nx::ws_pair_launch(
+        kPair, n, st, 16u, nullptr, level != 0,
+        [&](uint32_t base, uint32_t m, const nx::LaneGrid& g, nx::SharedWs& W, uint32_t stamp) {
+            uint8_t* ws = static_cast<uint8_t*>(W.p);
+            if (prefix_len) {
+                auto* k = g.spread ? k_deflate_match_prefix<true> : k_deflate_match_prefix<false>;
+                hipLaunchKernelGGL(k, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base, in_len + base, prefix_len + base, m, ws, stamp);
             } else {
-                hipLaunchKernelGGL(nx::deflate::k_deflate_match<false>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base,
-                                   in_len + base, m, ws, W.stamp);
+                auto* k = g.spread ? k_deflate_match<true> : k_deflate_match<false>;
+                hipLaunchKernelGGL(k, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base, in_len + base, m, ws, stamp);
             }
-            NX_HIP_CHECK(hipGetLastError());
-        }
-        const unsigned waves = (unsigned)cus * 16u;
-        if (pre)
-            hipLaunchKernelGGL(nx::deflate::k_deflate_emit_prefix, dim3(m < waves ? m : waves), dim3(64), 0, st, in, in_off + base,
-                               in_len + base, pre, out, out_off + base, out_len + base, status + base, m, ws, level == 0 ? 1u : 0u);
-        else
-            hipLaunchKernelGGL(nx::deflate::k_deflate_emit, dim3(m < waves ? m : waves), dim3(64), 0, st, in, in_off + base,
-                               in_len + base, out, out_off + base, out_len + base, status + base, m, ws, level == 0 ? 1u : 0u);
-        NX_HIP_CHECK(hipGetLastError());
-        base += m;
-    }
-    return NX_OK;
+        },
+        [&](uint32_t base, uint32_t m, unsigned waves, nx::SharedWs& W) {
+            uint8_t* ws = static_cast<uint8_t*>(W.p);
+            if (prefix_len)
+                hipLaunchKernelGGL(k_deflate_emit_prefix, dim3(waves), dim3(64), 0, st, in, in_off + base, in_len + base, prefix_len + base,
+                                   out, out_off + base, out_len + base, status + base, m, ws, level == 0 ? 1u : 0u);
+            else
+                hipLaunchKernelGGL(k_deflate_emit, dim3(waves), dim3(64), 0, st, in, in_off + base, in_len + base, out, out_off + base,
+                                   out_len + base, status + base, m, ws, level == 0 ? 1u : 0u);
+        });
 }
 }  // namespace
 

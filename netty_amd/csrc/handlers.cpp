@@ -886,20 +886,10 @@ extern "C" int64_t nx_lzma_frame_encoder_encode(nx_lzma_frame_encoder* e, const 
     };
     if (e->lc + e->lp > 4)
         return fail(nx_lzma_encode_host(in, n, e->lc, e->lp, e->pb, e->dict_size, e->end_marker, out, out_cap, nullptr));
-    const size_t bound = nx_lzma_max_compressed_length(n);
-    const uint32_t cap = (uint32_t)(out_cap < bound ? out_cap : bound);  // the slot the kernel may write
-    EncodeItems it(e->g);
-    it.add(0, (uint32_t)n, (bound + 15) / 16 * 16);
-    int32_t r = it.stage(in, n);
-    if (r != NX_OK) return fail(r);
-    if (!e->g.h2d(e->g.out_len.p, &cap, 4)) return fail(NX_ERR_HIP);
-    r = nx_lzma_encode_batch(it.d_in(), it.d_in_off(), it.d_in_len(), it.d_out(), it.d_out_off(), it.d_out_len(), it.d_status(), 1u, e->lc,
-                             e->lp, e->pb, e->dict_size, e->end_marker, e->g.s);
-    if (r != NX_OK) return fail(r);
-    if (!it.fetch(true)) return fail(NX_ERR_HIP);
-    if (it.st[0] != NX_OK) return fail(it.st[0]);
-    if (!it.copy_item(0, out) || !e->g.sync()) return fail(NX_ERR_HIP);
-    return (int64_t)it.len[0];
+    return fail(EncodeItems(e->g).encode_one(in, n, nx_lzma_max_compressed_length(n), out, out_cap, [&](EncodeItems& it) {
+        return nx_lzma_encode_batch(it.d_in(), it.d_in_off(), it.d_in_len(), it.d_out(), it.d_out_off(), it.d_out_len(), it.d_status(), 1u,
+                                    e->lc, e->lp, e->pb, e->dict_size, e->end_marker, e->g.s);
+    }));
 }
 
 // ------------------------------------------------------------------ BrotliEncoder
@@ -939,21 +929,12 @@ extern "C" int64_t nx_brotli_encoder_encode(nx_brotli_encoder* e, const uint8_t*
         if (r < 0) e->err = r == NX_ERR_BROTLI_ENCODE_FULL ? "the Brotli write does not fit the output buffer" : nx_status_string((int32_t)r);
         return r;
     };
-    const size_t bound = nx_brotli_encoder_max_encoded_length(n);
-    const uint32_t cap = (uint32_t)(out_cap < bound ? out_cap : bound);  // the slot the kernel may write
-    EncodeItems it(e->g);
-    it.add(0, (uint32_t)n, (bound + 15) / 16 * 16);
-    int32_t r = it.stage(in, n);
-    if (r != NX_OK) return fail(r);
-    if (!e->g.h2d(e->g.out_len.p, &cap, 4)) return fail(NX_ERR_HIP);
-    r = nx::brotli_encode_items(it.d_in(), it.d_in_off(), it.d_in_len(), it.d_out(), it.d_out_off(), it.d_out_len(), it.d_status(), 1u,
-                                e->lgwin, (e->started ? 0u : nx::brotli::kFlagHeader) | nx::brotli::kFlagFlush, e->g.s);
-    if (r != NX_OK) return fail(r);
-    if (!it.fetch(true)) return fail(NX_ERR_HIP);
-    if (it.st[0] != NX_OK) return fail(it.st[0]);
-    if (!it.copy_item(0, out) || !e->g.sync()) return fail(NX_ERR_HIP);
-    e->started = true;
-    return (int64_t)it.len[0];
+    const int64_t w = EncodeItems(e->g).encode_one(in, n, nx_brotli_encoder_max_encoded_length(n), out, out_cap, [&](EncodeItems& it) {
+        return nx::brotli_encode_items(it.d_in(), it.d_in_off(), it.d_in_len(), it.d_out(), it.d_out_off(), it.d_out_len(), it.d_status(), 1u,
+                                       e->lgwin, (e->started ? 0u : nx::brotli::kFlagHeader) | nx::brotli::kFlagFlush, e->g.s);
+    });
+    if (w >= 0) e->started = true;
+    return fail(w);
 }
 
 extern "C" int64_t nx_brotli_encoder_close(nx_brotli_encoder* e, uint8_t* out, size_t out_cap) {

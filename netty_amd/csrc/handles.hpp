@@ -142,6 +142,23 @@ struct EncodeItems : ItemTable {
     // Gather 1: an item's bytes (and nothing else of its slot) straight to their place in the caller's
     // buffer.  The caller syncs once after its last item.
     bool copy_item(uint32_t i, uint8_t* dst) { return g.d2h(dst, d_out() + out_off[i], len[i]); }
+    // A whole call of one item whose batch call takes capacities in out_len (LZMA, Brotli): in[0, n) into a slot
+    // of `bound` bytes, of which the kernel may write min(out_cap, bound); call(*this) is the batch call; the
+    // item's bytes to out, synced.  Returns their number, or the call's or the item's status.
+    template <class Call>
+    int64_t encode_one(const uint8_t* in, size_t n, size_t bound, uint8_t* out, size_t out_cap, Call&& call) {
+        const uint32_t cap = (uint32_t)(out_cap < bound ? out_cap : bound);
+        add(0, (uint32_t)n, (bound + 15) / 16 * 16);
+        int32_t r = stage(in, n);
+        if (r != NX_OK) return r;
+        if (!g.h2d(g.out_len.p, &cap, 4)) return NX_ERR_HIP;
+        r = call(*this);
+        if (r != NX_OK) return r;
+        if (!fetch(true)) return NX_ERR_HIP;
+        if (st[0] != NX_OK) return st[0];
+        if (!copy_item(0, out) || !g.sync()) return NX_ERR_HIP;
+        return (int64_t)len[0];
+    }
     // ... every item, one behind the other from out + *op (advanced); synced
     bool copy_packed(uint8_t* out, size_t* op) {
         bool ok = true;

@@ -8,7 +8,7 @@
 // matcher's rule and the packet coders are in lzma_encode_core.hpp, which nx_lzma_encode_host runs on the
 // CPU: the kernels write the host's bytes.
 //
-//   pass 1, k_lzma_match, one lane per item on the lane grid of the other alt encoders: match_item over
+//   pass 1, k_seq_match<Match> (seq_stage.hpp), one lane per item on the lane grid of the other alt encoders: match_item over
 //     a stamped hash table of 65 536 entries (stamp << 32 | position; positions are 32-bit, an item is not
 //     limited to 64 KiB) in the item's workspace slot.  It writes one 64-bit word per sequence (literal run,
 //     length, distance) to the item's area of the sequence arena.  Literal bytes are not packed beside
@@ -21,14 +21,15 @@
 //     pieces of whole 128-byte lines.  (Why the packet step is not spread over the lanes: DESIGN.md "LZMA encode".)
 //     Every output byte is checked against the slot's capacity before it is staged or stored.
 //
-// The sequence arena is one allocation per device beside the NX_WS_LZMA_ENC tables: an item of n bytes
-// takes 16 + 8 * seq_cap(n) bytes of it (a sequence covers at least two bytes).  The host reads in_len
-// back, lays the areas out and cuts the batch into launch pairs whose items fit the table slots and
-// kArenaMax bytes of arena; a call therefore synchronises its stream once, before its first launch.
+// The sequence arena is the side allocation of the NX_WS_LZMA_ENC workspace, freed whenever its tables are:
+// an item of n bytes takes 16 + 8 * seq_cap(n) bytes of it (a sequence covers at least two bytes).  The host
+// reads in_len back, lays the areas out and cuts the batch into launch pairs whose items fit the table slots
+// and kWsAreaMax bytes of arena (WsAreaCut, workspace.hpp); a call therefore synchronises its stream once,
+// before its first launch.
 #include <algorithm>
-#include <vector>
 #include "lzma_encode_core.hpp"
 #include "nx_common.hpp"
+#include "seq_stage.hpp"
 #include "workspace.hpp"
 
 namespace nx {
@@ -36,59 +37,22 @@ namespace lzma {
 
 constexpr uint32_t kMaxItem = 256u << 20;
 constexpr uint32_t kSlotBytes = 8u << kHashLog;
-constexpr uint32_t kStageBytes = 1024, kLine = 128, kCtrlBytes = 16;
-__host__ __device__ inline size_t area_bytes(size_t n) { return (16u + 8u * seq_cap(n) + 15u) & ~(size_t)15; }
+constexpr uint32_t kStageBytes = 1024, kLine = kSeqLine, kCtrlBytes = 16;
 inline uint32_t code_lds_bytes(uint32_t lc, uint32_t lp) { return kStageBytes + kCtrlBytes + 2u * model_probs(lc, lp); }
 
-// ---------------------------------------------------------------------------------------- pass 1
-template <bool SPREAD>
-__global__ void __launch_bounds__(256) k_lzma_match(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
-                                                    const uint32_t* __restrict__ in_len, uint32_t n, uint8_t* __restrict__ tables,
-                                                    uint32_t stamp, uint8_t* __restrict__ arena, const uint64_t* __restrict__ aoff,
-                                                    uint32_t dict_size) {
-    uint32_t tid, nthreads;
-    if (!chunk_slot<SPREAD>(tid, nthreads)) return;
-    if (tid >= n) return;  // one item per slot: its sequences stay in the arena for pass 2
-    const uint32_t len = in_len[tid];
-    uint64_t* area = reinterpret_cast<uint64_t*>(arena + aoff[tid]);
-    uint32_t ns = ~0u;
-    if (len <= kMaxItem)
-        ns = match_item(in + in_off[tid], len, dict_size, reinterpret_cast<uint64_t*>(tables + (size_t)tid * kSlotBytes), stamp, area + 2,
-                        seq_cap(len));
-    area[0] = ns;
-}
-
-// ---------------------------------------------------------------------------------------- pass 2
-// The item's output bytes.  Positions count from `origin`, the 128-byte line holding the slot's first byte;
-// bytes [flushed, at) that lie within kStageBytes of `flushed` are in the LDS ring, everything below
-// `flushed` and any byte beyond the ring (a long run of pending 0xFF bytes leaving at once) is in global memory.
-struct StageSink {
-    uint8_t* ring;
-    uint8_t* origin;
-    uint32_t at, flushed, end;  // end: the slot's capacity as a position
-    bool full;
-    __device__ __forceinline__ void put(uint8_t b) {
-        if (at >= end) {
-            full = true;
-            return;
-        }
-        if (at - flushed < kStageBytes) ring[at & (kStageBytes - 1u)] = b;
-        else origin[at] = b;
-        ++at;
+// pass 1: k_seq_match's codec; its parameter is the dictionary size
+struct Match {
+    static constexpr uint32_t kMaxItem = lzma::kMaxItem, kSlotBytes = lzma::kSlotBytes;
+    static __device__ __forceinline__ size_t seq_cap(size_t n) { return lzma::seq_cap(n); }
+    static __device__ __forceinline__ uint32_t match_item(const uint8_t* in, uint32_t n, uint32_t dict_size, uint64_t* table, uint32_t stamp,
+                                                          uint64_t* seq, size_t cap) {
+        return lzma::match_item(in, n, dict_size, table, stamp, seq, cap);
     }
 };
 
-// All lanes: store the ring's bytes [from, to) (to - from <= kStageBytes), 16 bytes a lane where a piece is whole.
-__device__ __forceinline__ void flush_ring(const uint8_t* ring, uint8_t* origin, uint32_t from, uint32_t to, uint32_t lane) {
-    for (uint32_t c = (from & ~15u) + lane * 16u; c < to; c += 64u * 16u) {
-        const uint32_t lo = c < from ? from : c, hi = c + 16u < to ? c + 16u : to;
-        if (hi - lo == 16u) {
-            *reinterpret_cast<uint4*>(origin + c) = *reinterpret_cast<const uint4*>(ring + (c & (kStageBytes - 1u)));
-        } else {
-            for (uint32_t b = lo; b < hi; ++b) origin[b] = ring[b & (kStageBytes - 1u)];
-        }
-    }
-}
+// ---------------------------------------------------------------------------------------- pass 2
+// The ring (seq_stage.hpp) holds 1 KiB; a byte beyond it is a long run of pending 0xFF bytes leaving at once.
+using Sink = StageSink<kStageBytes>;
 
 __global__ void __launch_bounds__(64) k_lzma_code(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                   const uint32_t* __restrict__ in_len, uint8_t* __restrict__ out,
@@ -117,8 +81,8 @@ __global__ void __launch_bounds__(64) k_lzma_code(const uint8_t* __restrict__ in
         uint8_t* dst = out + out_off[c];
         const uint32_t lead = (uint32_t)((uintptr_t)dst & (kLine - 1u));
         uint8_t* origin = dst - lead;
-        StageSink sink = {ring, origin, lead, lead, lead + cap, false};
-        Coder<StageSink> C;
+        Sink sink = {ring, origin, lead, lead, lead + cap, false};
+        Coder<Sink> C;
         uint64_t steps = max_steps(len, ns);
         if (lane == 0u) {
             C.init(probs, &sink, nullptr, in + in_off[c], len, area + 2, ns, P);
@@ -146,44 +110,23 @@ __global__ void __launch_bounds__(64) k_lzma_code(const uint8_t* __restrict__ in
             const uint32_t staged_end = over ? flushed + kStageBytes : at;
             const uint32_t to = flags || over ? staged_end : (staged_end & ~(kLine - 1u));
             if (to > flushed) {
-                flush_ring(ring, origin, flushed, to, lane);
+                flush_ring<kStageBytes, false>(ring, origin, flushed, to, lane);
                 flushed = over ? at : to;
             }
             if (lane == 0u) sink.flushed = flushed;
             __syncthreads();
         }
-        if (lane == 0u) {
-            const bool ok = flags == 1u;
-            out_len[c] = ok ? at - lead : 0u;
-            status[c] = ok ? NX_OK : (flags & 2u) ? NX_ERR_LZMA_ENCODE_FULL : NX_ERR_INTERNAL;
-        }
+        if (lane == 0u) seq_item_end(out_len, status, c, flags, at - lead, NX_ERR_LZMA_ENCODE_FULL);
         __syncthreads();
     }
 }
 
-// The sequence arena of a device: grown under the NX_WS_LZMA_ENC lease, dropped with that workspace.
-struct Arena {
-    uint8_t* p = nullptr;
-    size_t bytes = 0;
-};
-static Arena g_arena[64];
-
 }  // namespace lzma
-
-void lzma_arena_drop(int dev) {
-    lzma::Arena& A = lzma::g_arena[dev < 0 || dev >= 64 ? 0 : dev];
-    if (A.p) (void)hipFree(A.p);
-    A.p = nullptr;
-    A.bytes = 0;
-}
 }  // namespace nx
 
 namespace {
-constexpr uint32_t kMaxStamp = 0xFFFFFFF0u;
-// Most table slots the standalone entry grows the workspace to (8 GiB); a larger batch runs in sub-batches.
-constexpr size_t kMaxSlots = 16384;
-// Most arena bytes the sequence areas of one launch pair take, unless one item alone takes more.
-constexpr size_t kArenaMax = (size_t)4 << 30;
+// Stamps are 32 bits; at most 16 384 table slots (8 GiB) for a standalone call, a larger batch runs in sub-batches.
+constexpr nx::WsPairSpec kPair = {nx::WsKind::LzmaEnc, 0xFFFFFFF0u, 16384};
 constexpr nx::WsSpec kSpec = nx::kWsSpec[(int)nx::WsKind::LzmaEnc];
 static_assert(((size_t)kSpec.entry_bytes << kSpec.lg) == nx::lzma::kSlotBytes, "lzma slot geometry");
 }  // namespace
@@ -199,74 +142,20 @@ extern "C" int32_t nx_lzma_encode_batch(const uint8_t* in, const uint64_t* in_of
     if (n == 0) return NX_OK;
     if (!in_off || !in_len || !out || !out_off || !out_len || !status) return NX_ERR_INVALID_ARG;
     const hipStream_t st = (hipStream_t)stream;
-    int dev = 0, cus = 256;
-    NX_HIP_CHECK(hipGetDevice(&dev));
-    NX_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    nx::WsLease lease(nx::WsKind::LzmaEnc, dev, st);
-    const size_t want = nx::ws_want(nx::WsKind::LzmaEnc, n, cus);
-    NX_HIP_CHECK(lease.acquire(want < kMaxSlots ? want : kMaxSlots));
-    nx::SharedWs& W = lease.ws();
-    uint8_t* ws = static_cast<uint8_t*>(W.p);
-    // the lengths, on the host: the stream has waited for the workspace's earlier users, so after this
-    // synchronisation nothing reads the arena any more
-    std::vector<uint32_t> len(n);
-    NX_HIP_CHECK(hipMemcpyAsync(len.data(), in_len, (size_t)n * 4u, hipMemcpyDefault, st));
-    NX_HIP_CHECK(hipStreamSynchronize(st));
-    // launch pairs: as many items as the grid has slots, cut where the areas pass kArenaMax
-    struct Pair {
-        uint32_t base, m;
-        nx::LaneGrid g;
-    };
-    std::vector<Pair> pairs;
-    std::vector<uint64_t> aoff(n);
-    const size_t head = ((size_t)n * 8u + 127u) & ~(size_t)127;
-    size_t need = 0;
-    for (uint32_t base = 0; base < n;) {
-        const uint32_t left = n - base;
-        const nx::LaneGrid g = nx::ws_grid(nx::WsKind::LzmaEnc, left, cus, W.slots < kMaxSlots ? W.slots : kMaxSlots);
-        const uint32_t most = (uint32_t)(left < g.slots ? left : g.slots);
-        size_t used = 0;
-        uint32_t m = 0;
-        for (; m < most; ++m) {
-            const size_t a = area_bytes(len[base + m] <= kMaxItem ? len[base + m] : 0u);
-            if (m && used + a > kArenaMax) break;
-            aoff[base + m] = head + used;
-            used += a;
-        }
-        need = std::max(need, used);
-        pairs.push_back({base, m, g});
-        base += m;
-    }
-    Arena& A = g_arena[dev < 0 || dev >= 64 ? 0 : dev];
-    if (A.bytes < head + need) {
-        nx::lzma_arena_drop(dev);
-        NX_HIP_CHECK(hipMalloc(&A.p, head + need));
-        A.bytes = head + need;
-    }
-    NX_HIP_CHECK(hipMemcpy(A.p, aoff.data(), (size_t)n * 8u, hipMemcpyHostToDevice));
-    const uint64_t* d_aoff = reinterpret_cast<const uint64_t*>(A.p);
+    nx::WsAreaCut cut = {in_len, [](uint32_t len) { return area_bytes(seq_cap(len <= kMaxItem ? len : 0u)); }};
     const Params P = {(uint32_t)lc, (uint32_t)lp, (uint32_t)pb, (uint32_t)dict_size, end_marker ? 1u : 0u};
     const uint32_t lds = code_lds_bytes(P.lc, P.lp);
     // as many waves per CU as models fit the 160 KiB of LDS, at most 8 (two per SIMD)
     const unsigned per_cu = std::min<unsigned>(8u, (160u << 10) / lds);
-    for (const Pair& pr : pairs) {
-        const uint32_t base = pr.base, m = pr.m;
-        if (W.stamp + 1u >= kMaxStamp) {
-            NX_HIP_CHECK(hipMemsetAsync(W.p, 0, W.slots * (size_t)kSlotBytes, st));
-            W.stamp = 0;
-        }
-        W.stamp += 1u;
-        if (pr.g.spread)
-            hipLaunchKernelGGL(k_lzma_match<true>, dim3(pr.g.grid), dim3(pr.g.block), 0, st, in, in_off + base, in_len + base, m, ws,
-                               W.stamp, A.p, d_aoff + base, P.dict_size);
-        else
-            hipLaunchKernelGGL(k_lzma_match<false>, dim3(pr.g.grid), dim3(pr.g.block), 0, st, in, in_off + base, in_len + base, m, ws,
-                               W.stamp, A.p, d_aoff + base, P.dict_size);
-        NX_HIP_CHECK(hipGetLastError());
-        const unsigned waves = (unsigned)cus * per_cu;
-        hipLaunchKernelGGL(k_lzma_code, dim3(m < waves ? m : waves), dim3(64), lds, st, in, in_off + base, in_len + base, out,
-                           out_off + base, out_len + base, status + base, m, A.p, d_aoff + base, P);
-        NX_HIP_CHECK(hipGetLastError());
-    }
-    return NX_OK;
+    return nx::ws_pair_launch(
+        kPair, n, st, per_cu, &cut, true,
+        [&](uint32_t base, uint32_t m, const nx::LaneGrid& g, nx::SharedWs& W, uint32_t stamp) {
+            auto* k = g.spread ? nx::k_seq_match<Match, true> : nx::k_seq_match<Match, false>;
+            hipLaunchKernelGGL(k, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base, in_len + base, m, static_cast<uint8_t*>(W.p), stamp,
+                               static_cast<uint8_t*>(W.side), cut.d_aoff(W) + base, P.dict_size);
+        },
+        [&](uint32_t base, uint32_t m, unsigned waves, nx::SharedWs& W) {
+            hipLaunchKernelGGL(k_lzma_code, dim3(waves), dim3(64), lds, st, in, in_off + base, in_len + base, out, out_off + base,
+                               out_len + base, status + base, m, static_cast<const uint8_t*>(W.side), cut.d_aoff(W) + base, P);
+        });
 }

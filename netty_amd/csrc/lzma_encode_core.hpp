@@ -28,23 +28,14 @@
 // A sequence is one 64-bit word: literal run (23 bits) | length << 23 (9 bits; 0: a run with no match after
 // it, written when a run reaches 2^23 - 1 literals) | distance << 32.
 #pragma once
-#include <stdint.h>
-#include <stddef.h>
-#include <string.h>
-
-#ifndef NX_HD
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define NX_HD __host__ __device__ inline
-#else
-#define NX_HD inline
-#endif
-#endif
+#include "lz_seq_core.hpp"
 
 namespace nx {
 namespace lzma {
+using namespace lzseq;
 
 constexpr uint32_t kHeaderBytes = 13;
-constexpr uint32_t kStates = 12, kMatchMin = 2, kMatchMax = 273, kHashMin = 4;
+constexpr uint32_t kStates = 12, kMatchMin = 2, kMatchMax = 273, kHashMin = kHashBytes;
 constexpr uint32_t kProbInit = 1024, kMoveBits = 5, kBitModelBits = 11;
 constexpr uint32_t kTopValue = 1u << 24;
 // model layout
@@ -55,10 +46,7 @@ constexpr uint32_t kIsMatch = 0, kIsRep = kIsMatch + kStates * 16u, kIsRepG0 = k
 static_assert(kLiteral == 1848u, "model layout");
 NX_HD uint32_t model_probs(uint32_t lc, uint32_t lp) { return kLiteral + (0x300u << (lc + lp)); }
 
-// matcher
-constexpr uint32_t kHashLog = 16;
-constexpr uint32_t kRunBits = 23, kRunMax = (1u << kRunBits) - 1u;
-// the most sequences an n-byte item gives: a sequence with a match covers at least two bytes, one without a
+// matcher: the most sequences an n-byte item gives: a sequence with a match covers at least two bytes, one without a
 // match kRunMax literals
 NX_HD size_t seq_cap(size_t n) { return n / 2u + (n >> kRunBits) + 2u; }
 NX_HD size_t max_stream_bytes(size_t n) { return kHeaderBytes + n + n / 3u + 128u; }
@@ -70,31 +58,6 @@ struct Params {
 struct Stats {  // nx_lzma_encode_stats
     uint64_t literals, matched_literals, matches, short_reps, reps[4], carries, max_pending_ff, max_carry_ff;
 };
-
-NX_HD uint32_t rd32(const uint8_t* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef uint32_t __attribute__((aligned(1))) u32u;
-    return *reinterpret_cast<const u32u*>(p);
-#else
-    uint32_t v;
-    memcpy(&v, p, 4);
-    return v;
-#endif
-}
-
-NX_HD uint32_t common_len(const uint8_t* a, const uint8_t* b, uint32_t maxlen) {
-    uint32_t l = 0;
-    while (l + 4u <= maxlen) {
-        const uint32_t x = rd32(a + l) ^ rd32(b + l);
-        if (x) {
-            // the first differing byte (little endian)
-            return l + ((x & 0xFFu) ? 0u : (x & 0xFF00u) ? 1u : (x & 0xFF0000u) ? 2u : 3u);
-        }
-        l += 4u;
-    }
-    while (l < maxlen && a[l] == b[l]) ++l;
-    return l;
-}
 
 NX_HD void reps_use(uint32_t* rep, uint32_t i) {  // rep[i] moves to the front
     const uint32_t d = rep[i];
@@ -114,7 +77,8 @@ NX_HD void reps_push(uint32_t* rep, uint32_t d) {
 NX_HD uint32_t match_item(const uint8_t* in, uint32_t n, uint32_t dict_size, uint64_t* table, uint32_t stamp, uint64_t* seq,
                           size_t cap) {
     uint32_t rep[4] = {0, 0, 0, 0};  // distances - 1, as the coder keeps them
-    uint32_t ns = 0, ip = 0, run = 0;
+    SeqWriter out = {seq, cap, 0, 0};
+    uint32_t ip = 0;
     const uint64_t stag = (uint64_t)stamp << 32;
     while (ip < n) {
         const uint32_t limit = ip < dict_size ? ip : dict_size;
@@ -131,11 +95,8 @@ NX_HD uint32_t match_item(const uint8_t* in, uint32_t n, uint32_t dict_size, uin
         }
         if (left >= kHashMin) {
             const uint32_t w = rd32(in + ip);
-            const uint32_t h = (w * 2654435761u) >> (32u - kHashLog);
-            const uint64_t e = table[h];
-            table[h] = stag | ip;
-            const uint32_t cand = (uint32_t)e;
-            if ((e >> 32) == stamp && cand < ip && ip - cand <= limit && rd32(in + cand) == w) {
+            const uint32_t cand = probe(table, stag, stamp, w, ip);
+            if (cand != kNone && ip - cand <= limit && rd32(in + cand) == w) {
                 mlen = common_len(in + ip, in + cand, maxlen);
                 mdist = ip - cand;
             }
@@ -155,22 +116,14 @@ NX_HD uint32_t match_item(const uint8_t* in, uint32_t n, uint32_t dict_size, uin
         }
         if (len == 0u) {
             ++ip;
-            if (++run == kRunMax) {
-                if (ns >= cap) return ~0u;
-                seq[ns++] = run;
-                run = 0;
-            }
+            if (!out.literal()) return ~0u;
             continue;
         }
-        if (ns >= cap) return ~0u;
-        seq[ns++] = (uint64_t)run | ((uint64_t)len << kRunBits) | ((uint64_t)dist << 32);
-        run = 0;
-        const uint32_t end = ip + len;
-        for (uint32_t q = ip + 1u; q < end && q + kHashMin <= n; ++q)
-            table[(rd32(in + q) * 2654435761u) >> (32u - kHashLog)] = stag | q;
-        ip = end;
+        if (!out.match(((uint64_t)len << kRunBits) | ((uint64_t)dist << 32))) return ~0u;
+        insert_span(table, stag, in, ip + 1u, ip + len, n);
+        ip += len;
     }
-    return ns;  // the literals after the last sequence are implied by n
+    return out.ns;  // the literals after the last sequence are implied by n
 }
 
 // The 13 header bytes.

@@ -2,27 +2,14 @@
 // nx_lzma_encode_host, a single-threaded encode of one item from the functions of lzma_encode_core.hpp:
 // the matcher and the packet coders the kernels run, so the bytes are the GPU's.  It is the CPU check of the
 // format core, the GPU tests' second opinion, and the path of a handle whose lc + lp > 4.
-#include <stdlib.h>
 #include <string.h>
-#include <memory>
 #include <vector>
 #include "../../include/netty_amd.h"
+#include "encode_host.hpp"
 #include "lzma_encode_core.hpp"
 
-namespace {
 using namespace nx::lzma;
-
-struct HostSink {
-    uint8_t* out;
-    size_t cap, at;
-    bool full;
-    void put(uint8_t b) {
-        if (at < cap) out[at] = b;
-        else full = true;
-        ++at;
-    }
-};
-}  // namespace
+using nx::HostSink;
 
 extern "C" size_t nx_lzma_max_compressed_length(size_t n) { return max_stream_bytes(n); }
 
@@ -43,19 +30,17 @@ extern "C" int64_t nx_lzma_encode_host(const uint8_t* in, size_t n, int32_t lc, 
     if (out_cap < kHeaderBytes) return NX_ERR_LZMA_ENCODE_FULL;
     const Params P = {(uint32_t)lc, (uint32_t)lp, (uint32_t)pb, (uint32_t)dict_size, end_marker ? 1u : 0u};
     write_header(out, P, n);
-    std::unique_ptr<uint64_t, decltype(&free)> table(static_cast<uint64_t*>(calloc((size_t)1 << kHashLog, 8)), &free);
     std::vector<uint64_t> seq(seq_cap(n));
     std::vector<uint16_t> probs(model_probs(P.lc, P.lp), (uint16_t)kProbInit);
-    if (!table) return NX_ERR_INTERNAL;
-    const uint32_t ns = match_item(in, (uint32_t)n, P.dict_size, table.get(), 1u, seq.data(), seq.size());
-    if (ns == ~0u) return NX_ERR_INTERNAL;
+    uint32_t ns = 0;
+    if (!nx::host_match(seq, &ns, [&](uint64_t* table, uint32_t stamp, uint64_t* s, size_t cap) {
+            return match_item(in, (uint32_t)n, P.dict_size, table, stamp, s, cap);
+        }))
+        return NX_ERR_INTERNAL;
     HostSink sink = {out, out_cap, kHeaderBytes, false};
     Coder<HostSink> C;
     C.init(probs.data(), &sink, &st, in, (uint32_t)n, seq.data(), ns, P);
-    for (uint64_t left = max_steps((uint32_t)n, ns); !C.done && !sink.full; --left) {
-        if (left == 0u) return NX_ERR_INTERNAL;
-        C.step();
-    }
+    if (!nx::host_steps(C, sink, max_steps((uint32_t)n, ns))) return NX_ERR_INTERNAL;
     if (stats) memcpy(stats, &st, sizeof(st));
     return sink.full ? (int64_t)NX_ERR_LZMA_ENCODE_FULL : (int64_t)sink.at;
 }

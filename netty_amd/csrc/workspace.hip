@@ -30,6 +30,9 @@ hipError_t ws_drop(SharedWs& W) {
         if (g != hipSuccess && dbg) fprintf(stderr, "netty_amd: ws_drop: hipFree(%p): %s\n", W.p, hipGetErrorString(g));
         if (e == hipSuccess) e = g;
     }
+    if (W.side) (void)hipFree(W.side);  // its readers were enqueued before the events waited for above
+    W.side = nullptr;
+    W.side_bytes = 0;
     W.p = nullptr;
     W.slots = 0;
     W.stamp = 0;
@@ -113,6 +116,40 @@ LaneGrid ws_grid(WsKind k, uint32_t n, int cus, size_t have) {
     g.slots = std::min<size_t>(std::min<size_t>(have, (size_t)cus * wpcu), n);
     g.grid = (unsigned)g.slots;
     return g;
+}
+
+hipError_t ws_side_reserve(SharedWs& W, size_t bytes) {
+    if (W.side_bytes >= bytes) return hipSuccess;
+    if (W.side) (void)hipFree(W.side);
+    W.side = nullptr;
+    W.side_bytes = 0;
+    const hipError_t e = hipMalloc(&W.side, bytes);
+    if (e == hipSuccess) W.side_bytes = bytes;
+    return e;
+}
+
+int32_t WsAreaCut::take(SharedWs& W, uint32_t n, hipStream_t st, uint32_t base, uint32_t most, uint32_t* m) {
+    const size_t head = ((size_t)n * 8u + 127u) & ~(size_t)127;
+    if (base == 0u) {
+        len.resize(n);
+        aoff.resize(n);
+        NX_HIP_CHECK(hipMemcpyAsync(len.data(), in_len, (size_t)n * 4u, hipMemcpyDefault, st));
+        NX_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    size_t used = 0;
+    uint32_t k = 0;
+    for (; k < most; ++k) {
+        const size_t a = area(len[base + k]);
+        if (k && used + a > kWsAreaMax) break;
+        aoff[base + k] = head + used;
+        used += a;
+    }
+    need = std::max(need, used);
+    *m = k;
+    if (base + k < n) return NX_OK;
+    NX_HIP_CHECK(ws_side_reserve(W, head + need));
+    NX_HIP_CHECK(hipMemcpy(W.side, aoff.data(), (size_t)n * 8u, hipMemcpyHostToDevice));
+    return NX_OK;
 }
 
 NoGrowScope::NoGrowScope() : prev(t_no_grow) { t_no_grow = true; }
@@ -251,8 +288,6 @@ extern "C" int32_t nx_workspaces_trim(void) {
         if (W.owners == 0) {
             W.cap = 0;  // a reserve's cap lasts until its workspace is freed
             const hipError_t e = nx::ws_drop(W);
-            if (k == (int)nx::WsKind::LzmaEnc) nx::lzma_arena_drop(dev);
-            if (k == (int)nx::WsKind::BrotliEnc) nx::brotli_arena_drop(dev);
             if (e != hipSuccess) r = nx_hip_fail(e, __FILE__, __LINE__ + k * 1000);  // line + 1000 * kind under NX_HIP_DEBUG
         }
     }

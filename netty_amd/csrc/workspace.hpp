@@ -46,8 +46,9 @@ struct WsSpec {
 // level L takes L consecutive units, leased by part, one stream per workgroup of the launch on at most
 // kBzip2EncGroupsPerCu workgroups per CU.
 // LzmaEnc: 512 KiB per item in flight (65 536 stamped hash entries of the matcher; lzma.hip), one item per slot and
-// launch pair as ZstdEnc; the items' sequence words live in an arena of their own, sized per call from the lengths.
-// BrotliEnc: the same geometry for the Brotli matcher (brotli.hip), with a sequence arena of its own.
+// launch pair as ZstdEnc; the items' sequence words live in the workspace's side allocation (SharedWs::side), sized
+// per call from the lengths (WsAreaCut).
+// BrotliEnc: the same geometry for the Brotli matcher (brotli.hip), with the same use of its own side allocation.
 #ifndef NX_LZ4_WPCU  // build options for A/B runs of the alt encoders' occupancy (scripts/build_lib_variant.sh; LZ4 at 20: level)
 #define NX_LZ4_WPCU 16
 #endif
@@ -92,6 +93,8 @@ struct SharedWs {
     size_t cursor = 0;              // next part lease starts here (wraps to 0)
     void* p = nullptr;
     size_t slots = 0;    // tables (lanes or waves) or frames
+    void* side = nullptr;   // a second allocation some kinds keep beside the slots (ws_side_reserve): it is used under
+    size_t side_bytes = 0;  // the lease as the slots are, and freed whenever they are
     uint32_t stamp = 0;  // encoders: last stamp used
     hipEvent_t ev = nullptr;
     hipStream_t ev_st = nullptr;  // the stream ev was last recorded on
@@ -112,10 +115,9 @@ size_t ws_want(WsKind k, uint32_t n, int cus);
 // per wave on up to cus * waves_per_cu waves.
 LaneGrid ws_grid(WsKind k, uint32_t n, int cus, size_t have);
 
-// lzma.hip: free the device's sequence arena (the caller holds the LzmaEnc workspace's lock and has waited for its users)
-void lzma_arena_drop(int dev);
-// brotli.hip: the same for the Brotli encoder's arena under the BrotliEnc workspace
-void brotli_arena_drop(int dev);
+// At least `bytes` of side allocation (the caller holds W's lease, and nothing enqueued reads the side any more):
+// kept when it is large enough, else freed and allocated anew; what it held is lost either way.
+hipError_t ws_side_reserve(SharedWs& W, size_t bytes);
 
 struct NoGrowScope {
     NoGrowScope();
@@ -173,6 +175,81 @@ int32_t ws_lane_launch(WsKind k, uint32_t max_stamp, uint32_t n, hipStream_t st,
         launch(base, m, g, W.p, W.stamp);
         NX_HIP_CHECK(hipGetLastError());
         W.stamp += iters;
+    }
+    return NX_OK;
+}
+
+// How an arena encoder's batch is cut (ws_pair_launch): an item's sequence area is area(its length) bytes of the
+// side allocation, whose first words are the items' offsets into it (d_aoff), and a launch pair takes items
+// while their areas stay within kWsAreaMax, one item at least.  The first take reads in_len back, which
+// synchronises the stream once: the stream has waited for the workspace's earlier users by then, so nothing
+// reads the side any more.  The take that reaches item n reserves the side for the largest pair and copies
+// the offsets there.
+constexpr size_t kWsAreaMax = (size_t)4 << 30;
+struct WsAreaCut {
+    const uint32_t* in_len;         // of the batch, on the device
+    size_t (*area)(uint32_t len);
+    std::vector<uint32_t> len;
+    std::vector<uint64_t> aoff;
+    size_t need = 0;
+    // how many of the items [base, base + most) the next pair takes
+    int32_t take(SharedWs& W, uint32_t n, hipStream_t st, uint32_t base, uint32_t most, uint32_t* m);
+    static const uint64_t* d_aoff(const SharedWs& W) { return static_cast<const uint64_t*>(W.side); }
+};
+
+// One batch of a two-pass encoder over kind k's slots, an item per slot from its pass 1 to its pass 2: the batch
+// runs in launch pairs of at most the grid's slots (at most max_slots of them, to which a standalone call grows
+// the workspace; 0: no such cap) and of what `cut` takes, if there is one.  A pair's matcher stamps its table
+// entries with the next stamp, and stamps stay below max_stamp between two zeroings of the slots.
+// match(base, m, grid, W, stamp) enqueues pass 1 for items [base, base + m), emit(base, m, waves, W) pass 2 on
+// min(m, CUs * emit_waves_per_cu) waves.  stamped = false: no pass 1, and the stamp stays (deflate's level 0).
+struct WsPairSpec {
+    WsKind kind;
+    uint32_t max_stamp;
+    size_t max_slots;
+};
+template <class Match, class Emit>
+int32_t ws_pair_launch(const WsPairSpec& S, uint32_t n, hipStream_t st, unsigned emit_waves_per_cu, WsAreaCut* cut, bool stamped,
+                       Match&& match, Emit&& emit) {
+    int dev = 0, cus = 256;
+    NX_HIP_CHECK(hipGetDevice(&dev));
+    NX_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    WsLease lease(S.kind, dev, st);
+    const size_t want = ws_want(S.kind, n, cus);
+    NX_HIP_CHECK(lease.acquire(S.max_slots && want > S.max_slots ? S.max_slots : want));
+    SharedWs& W = lease.ws();
+    const size_t have = S.max_slots && W.slots > S.max_slots ? S.max_slots : W.slots;
+    const size_t slot_bytes = (size_t)kWsSpec[(int)S.kind].entry_bytes << kWsSpec[(int)S.kind].lg;
+    // the pairs first: the last cut sizes the side allocation, before anything that uses it is enqueued
+    struct Pair {
+        uint32_t base, m;
+        LaneGrid g;
+    };
+    std::vector<Pair> pairs;
+    for (uint32_t base = 0; base < n;) {
+        const uint32_t left = n - base;
+        const LaneGrid g = ws_grid(S.kind, left, cus, have);
+        uint32_t m = (uint32_t)(left < g.slots ? left : g.slots);
+        if (cut) {
+            const int32_t r = cut->take(W, n, st, base, m, &m);
+            if (r != NX_OK) return r;
+        }
+        pairs.push_back({base, m, g});
+        base += m;
+    }
+    const unsigned waves = (unsigned)cus * emit_waves_per_cu;
+    for (const Pair& pr : pairs) {
+        if (stamped) {
+            if (W.stamp + 1u >= S.max_stamp) {
+                NX_HIP_CHECK(hipMemsetAsync(W.p, 0, W.slots * slot_bytes, st));
+                W.stamp = 0;
+            }
+            W.stamp += 1u;
+            match(pr.base, pr.m, pr.g, W, W.stamp);
+            NX_HIP_CHECK(hipGetLastError());
+        }
+        emit(pr.base, pr.m, pr.m < waves ? pr.m : waves, W);
+        NX_HIP_CHECK(hipGetLastError());
     }
     return NX_OK;
 }

@@ -887,10 +887,9 @@ __global__ void __launch_bounds__(64) k_zstd_emit(const uint8_t* __restrict__ in
 }  // namespace nx
 
 namespace {
-constexpr uint32_t kMaxStamp = 0xFFFFu;
-// Most slots the standalone entry grows the workspace to (16 GiB): a larger batch runs in sub-batches.
-// 32 768 lanes are where the table request rate saturates, so nothing is lost.
-constexpr size_t kMaxSlots = 32768;
+// Stamps are 16 bits.  Most slots the standalone entry grows the workspace to: 32 768 (16 GiB), a larger batch
+// runs in sub-batches; that many lanes are where the table request rate saturates, so nothing is lost.
+constexpr nx::WsPairSpec kPair = {nx::WsKind::ZstdEnc, 0xFFFFu, 32768};
 constexpr nx::WsSpec kSpec = nx::kWsSpec[(int)nx::WsKind::ZstdEnc];
 static_assert(((size_t)kSpec.entry_bytes << kSpec.lg) == nx::zstd::kSlotBytes, "zstd slot geometry");
 static_assert(nx::zstd::kSeqOff % 16u == 0 && nx::zstd::kSeqOff + nx::zstd::kSeqCap * 8u <= nx::zstd::kSlotBytes, "zstd sequence area");
@@ -912,36 +911,15 @@ extern "C" int32_t nx_zstd_encode_batch(const uint8_t* in, const uint64_t* in_of
     if (n == 0) return NX_OK;
     if (!in || !in_off || !in_len || !out || !out_off || !out_len || !status) return NX_ERR_INVALID_ARG;
     const hipStream_t st = (hipStream_t)stream;
-    int dev = 0, cus = 256;
-    NX_HIP_CHECK(hipGetDevice(&dev));
-    NX_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    nx::WsLease lease(nx::WsKind::ZstdEnc, dev, st);
-    const size_t want = nx::ws_want(nx::WsKind::ZstdEnc, n, cus);
-    NX_HIP_CHECK(lease.acquire(want < kMaxSlots ? want : kMaxSlots));
-    nx::SharedWs& W = lease.ws();
-    uint8_t* ws = static_cast<uint8_t*>(W.p);
-    // a slot holds one chunk's literals and sequences from pass 1 to pass 2: sub-batches of at most the slots
-    for (size_t base = 0; base < n;) {
-        const uint32_t left = (uint32_t)(n - base);
-        const nx::LaneGrid g = nx::ws_grid(nx::WsKind::ZstdEnc, left, cus, W.slots);
-        const uint32_t m = (uint32_t)(left < g.slots ? left : g.slots);
-        if (W.stamp + 1u >= kMaxStamp) {
-            NX_HIP_CHECK(hipMemsetAsync(W.p, 0, W.slots * (size_t)nx::zstd::kSlotBytes, st));
-            W.stamp = 0;
-        }
-        W.stamp += 1u;
-        if (g.spread)
-            hipLaunchKernelGGL(nx::zstd::k_zstd_match<true>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base, in_len + base, m, ws,
-                               W.stamp);
-        else
-            hipLaunchKernelGGL(nx::zstd::k_zstd_match<false>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base, in_len + base, m, ws,
-                               W.stamp);
-        NX_HIP_CHECK(hipGetLastError());
-        const unsigned waves = (unsigned)cus * 8u;
-        hipLaunchKernelGGL(nx::zstd::k_zstd_emit, dim3(m < waves ? m : waves), dim3(64), 0, st, in, in_off + base, in_len + base, out,
-                           out_off + base, out_len + base, status + base, m, ws);
-        NX_HIP_CHECK(hipGetLastError());
-        base += m;
-    }
-    return NX_OK;
+    // a slot holds one chunk's literals and sequences from pass 1 to pass 2
+    return nx::ws_pair_launch(
+        kPair, n, st, 8u, nullptr, true,
+        [&](uint32_t base, uint32_t m, const nx::LaneGrid& g, nx::SharedWs& W, uint32_t stamp) {
+            auto* k = g.spread ? nx::zstd::k_zstd_match<true> : nx::zstd::k_zstd_match<false>;
+            hipLaunchKernelGGL(k, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base, in_len + base, m, static_cast<uint8_t*>(W.p), stamp);
+        },
+        [&](uint32_t base, uint32_t m, unsigned waves, nx::SharedWs& W) {
+            hipLaunchKernelGGL(nx::zstd::k_zstd_emit, dim3(waves), dim3(64), 0, st, in, in_off + base, in_len + base, out, out_off + base,
+                               out_len + base, status + base, m, static_cast<uint8_t*>(W.p));
+        });
 }

@@ -109,8 +109,8 @@ def step_passes():
         res = {"step": "passes", "items": 1024}
         for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
             for row in csv.DictReader(open(f)):
-                for k in ("k_brotli_match", "k_brotli_emit"):
-                    if k in row["Name"]:
+                for k, name in (("k_brotli_match", "k_seq_match<nx::brotli"), ("k_brotli_emit", "k_brotli_emit")):
+                    if name in row["Name"]:
                         res[k + "_ms"] = round(float(row["AverageNs"]) / 1e6, 3)
                         res[k + "_calls"] = int(row["Calls"])
     print(json.dumps(res))

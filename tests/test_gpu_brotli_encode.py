@@ -103,6 +103,15 @@ def test_one_mebibyte_beside_one_byte_items(B, dev, oracle):
         assert pa.Codec("brotli").decompress(s, decompressed_size=len(c)).to_pybytes() == c
 
 
+def test_the_arena_grows_and_is_used_again(B, dev, oracle):
+    """a fresh workspace, 1-byte items, then an item that needs a larger arena, then the small call on the grown one"""
+    B.workspaces_trim()
+    small, big = [b"a", b"b", b"c"], [oracle.textgen_chunk(9, 1 << 20)]
+    for chunks in (small, big, small):
+        for c, r in zip(chunks, encode(B, dev, chunks)):
+            assert r == (0, B.brotli_encode_host(c)[1])
+
+
 def test_undersized_slots(B, dev, items, host):
     pick = [(n, d) for n, d in items if len(d) <= 30000][:27]
     caps, short = [], set()
