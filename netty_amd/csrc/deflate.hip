@@ -37,9 +37,6 @@ constexpr uint32_t kTokCap = (kSlotBytes - kTokOff - 8u) / 2u;   // after its tw
 constexpr uint32_t kMaxMatch = 258, kMaxDist = 32768;
 constexpr uint32_t kLit = 288, kDistBase = 288, kSyms = 320;     // symbol tables: 288 literal/length slots, then 32 distance slots
 
-typedef uint32_t __attribute__((aligned(1))) u32u;
-__device__ __forceinline__ uint32_t ld32(const uint8_t* p) { return *reinterpret_cast<const u32u*>(p); }
-
 // ---------------------------------------------------------------------------------------- pass 1
 //
 // PREFIX: `in` is the chunk's history followed by the chunk, one flat range of n = pre + length bytes

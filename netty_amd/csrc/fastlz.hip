@@ -34,11 +34,6 @@ __device__ __forceinline__ int32_t hashf(const uint8_t* in, int32_t o, int32_t l
     return v & HASH_MASK;
 }
 
-typedef uint32_t __attribute__((aligned(1))) u32u;
-typedef uint64_t __attribute__((aligned(1))) u64u;
-__device__ __forceinline__ uint32_t ld32(const uint8_t* p) { return *reinterpret_cast<const u32u*>(p); }
-__device__ __forceinline__ uint64_t ld64(const uint8_t* p) { return *reinterpret_cast<const u64u*>(p); }
-
 // hashFunction at o from the dword w = bytes o..o+3 (readU16's limit applied per half)
 __device__ __forceinline__ int32_t hash_w(uint32_t w, int32_t o, int32_t lim) {
     const int32_t b0 = (int32_t)(w & 0xFFu), b1 = (int32_t)((w >> 8) & 0xFFu), b2 = (int32_t)((w >> 16) & 0xFFu);
@@ -361,6 +356,9 @@ __device__ int32_t decompress(const uint8_t* __restrict__ in, int32_t inLength, 
     return op;
 }
 
+// FastLZ's own copy of the lane shell (lane_encode.hpp: k_lane_encode): as an instantiation of the
+// shared shell, with the two optional arrays as the codec's extra argument, the dense form took 100
+// SGPRs against the 102 here in either parameter order, so the kernel and its launch stay as they were.
 template <bool SPREAD>
 __global__ void __launch_bounds__(256) k_compress(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                   const uint32_t* __restrict__ in_len, uint8_t* __restrict__ out,
@@ -510,24 +508,11 @@ extern "C" int32_t nx_fastlz_compress_batch(const uint8_t* in, const uint64_t* i
     return nx::ws_lane_launch(nx::WsKind::FastLzEnc, 65535u, n, st, launch);
 }
 
-namespace {
-struct FlzDecCtx {
-    const uint8_t* in;
-    const uint64_t* in_off;
-    const uint32_t* in_len;
-    const uint32_t* in_avail;
-    uint8_t* out;
-    const uint64_t* out_off;
-    const uint32_t* lim;
-    int32_t* result;
-};
-hipError_t flz_dec_after(uint32_t base, uint32_t m, const uint32_t* olen, void* ctx, hipStream_t st) {
-    const FlzDecCtx& x = *static_cast<const FlzDecCtx*>(ctx);
+static hipError_t flz_dec_after(const nx::dec::RecCall& x, uint32_t base, uint32_t m, const uint32_t* olen, hipStream_t st) {
     hipLaunchKernelGGL(nx::flz::k_decompress_finish, dim3((m + 255) / 256), dim3(256), 0, st, x.in, x.in_off + base, x.in_len + base,
-                       x.in_avail ? x.in_avail + base : nullptr, x.out, x.out_off + base, x.lim + base, x.result + base, olen, m);
+                       x.avail ? x.avail + base : nullptr, x.out, x.out_off + base, x.lim + base, x.status + base, olen, m);
     return hipGetLastError();
 }
-}  // namespace
 
 // Blocks go through the record expander (snappy_decode.hip k_parse_fastlz + k_expand); the few it
 // does not take (malformed, reads past the block) through the lane-serial decompress().
@@ -537,9 +522,8 @@ extern "C" int32_t nx_fastlz_decompress_batch(const uint8_t* in, const uint64_t*
     NX_CLEAR_STALE_ERROR();
     if (n == 0) return NX_OK;
     if (!in || !in_off || !in_len || !out || !out_off || !out_len_limit || !result) return NX_ERR_INVALID_ARG;
-    FlzDecCtx ctx{in, in_off, in_len, in_avail, out, out_off, out_len_limit, result};
-    return nx::dec::decode_records(nx::dec::RecCodec::FastLz, in, in_off, in_len, in_avail, out_len_limit, out, out_off, result, n,
-                                   (hipStream_t)stream, flz_dec_after, &ctx);
+    return nx::dec::decode_records(nx::dec::RecCodec::FastLz, {in, in_off, in_len, in_avail, out_len_limit, out, out_off, result}, n,
+                                   (hipStream_t)stream, flz_dec_after);
 }
 
 extern "C" int32_t nx_adler32_batch(const uint8_t* in, const uint64_t* off, const uint32_t* len, uint32_t* out, uint32_t n,

@@ -16,8 +16,7 @@
 // (a stamp mismatch reads as the zeroed table), so the table is never cleared between blocks;
 // a large block zeroes its 4096 slots before and after itself, so none of its raw indices can pass
 // a later small block's stamp check.
-#include "nx_common.hpp"
-#include "workspace.hpp"
+#include "lane_encode.hpp"
 
 namespace nx {
 namespace lz4 {
@@ -25,11 +24,6 @@ namespace lz4 {
 constexpr int kMinMatch = 4, kLastLiterals = 5, kMfLimit = 12, kMinLength = 13;
 constexpr int32_t k64KLimit = 65536 + kMfLimit - 1;
 constexpr uint32_t kTableSlots = 8192;  // byU16 slots (the byU32 table uses the first 4096)
-
-typedef uint32_t __attribute__((aligned(1))) u32u;
-typedef uint64_t __attribute__((aligned(1))) u64u;
-__device__ __forceinline__ uint32_t ld32(const uint8_t* p) { return *reinterpret_cast<const u32u*>(p); }
-__device__ __forceinline__ uint64_t ld64(const uint8_t* p) { return *reinterpret_cast<const u64u*>(p); }
 
 template <bool Large>
 __device__ __forceinline__ uint32_t hash_at(const uint8_t* p) {
@@ -164,41 +158,22 @@ last_literals:
     return op + lit;
 }
 
-template <bool SPREAD>
-__global__ void __launch_bounds__(256) k_lz4_encode(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
-                                                    const uint32_t* __restrict__ in_len, uint8_t* __restrict__ out,
-                                                    const uint64_t* __restrict__ out_off, uint32_t* __restrict__ out_len,
-                                                    int32_t* __restrict__ status, uint32_t n, uint64_t* __restrict__ workspace,
-                                                    uint32_t stamp_base) {
-    uint32_t tid, nthreads;
-    if (!chunk_slot<SPREAD>(tid, nthreads)) return;
-    uint64_t* table = workspace + (size_t)tid * kTableSlots;
-    uint8_t* slot = nullptr;
-    if constexpr (!SPREAD) {
-        __shared__ __attribute__((aligned(16))) uint8_t stages[256 * kStageStride];
-        slot = &stages[threadIdx.x * kStageStride];
+// The fast compressor as a lane codec (lane_encode.hpp).  A block of k64KLimit bytes or more takes the
+// byU32 form: raw indices in a table it zeroes itself (no stamp), written as plain global bytes.
+struct Codec {
+    using Entry = uint64_t;
+    static constexpr uint32_t kEntries = kTableSlots;
+    static constexpr WsKind kKind = WsKind::Lz4Enc;
+    static constexpr uint32_t kMaxStamp = 0xFFFFu;
+    static __device__ __forceinline__ bool valid(uint32_t len) { return len <= (1u << 25); }
+    static __device__ __forceinline__ uint32_t stamp(uint32_t base, uint32_t iter) { return base + iter + 1u; }
+    static __device__ __forceinline__ bool unstaged(uint32_t len) { return (int32_t)len >= k64KLimit; }
+    template <class O>
+    static __device__ __forceinline__ uint32_t encode(const uint8_t* in, uint32_t len, O& o, Entry* table, uint32_t stamp) {
+        if (unstaged(len)) return encode_block<true>(in, (int32_t)len, o, table, 0u);
+        return encode_block<false>(in, (int32_t)len, o, table, stamp);
     }
-    uint32_t iter = 0;
-    for (uint32_t c = tid; c < n; c += nthreads, ++iter) {
-        const uint32_t len = in_len[c];
-        if (len > (1u << 25)) {
-            out_len[c] = 0;
-            status[c] = NX_ERR_INVALID_ARG;
-            continue;
-        }
-        if ((int32_t)len >= k64KLimit) {
-            GOut o{out + out_off[c]};
-            out_len[c] = encode_block<true>(in + in_off[c], (int32_t)len, o, table, 0u);
-        } else if (SPREAD) {
-            GOut o{out + out_off[c]};
-            out_len[c] = encode_block<false>(in + in_off[c], (int32_t)len, o, table, stamp_base + iter + 1u);
-        } else {
-            ByteStage o(slot, out + out_off[c]);  // dense form: whole 128-byte units (nx_common.hpp)
-            out_len[c] = encode_block<false>(in + in_off[c], (int32_t)len, o, table, stamp_base + iter + 1u);
-        }
-        status[c] = NX_OK;
-    }
-}
+};
 
 // ---------------------------------------------------------------------------------------------
 // LZ4 HC (Lz4FrameEncoder(highCompressor = true): lz4-java's highCompressor() = liblz4's
@@ -518,97 +493,39 @@ __device__ uint32_t encode_block_hc(const uint8_t* __restrict__ in, int32_t n, O
     return op + lit;
 }
 
-template <bool SPREAD>
-__global__ void __launch_bounds__(256) k_lz4hc_encode(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
-                                                      const uint32_t* __restrict__ in_len, uint8_t* __restrict__ out,
-                                                      const uint64_t* __restrict__ out_off, uint32_t* __restrict__ out_len,
-                                                      int32_t* __restrict__ status, uint32_t n, uint32_t* __restrict__ workspace,
-                                                      uint32_t stamp_base) {
-    uint32_t tid, nthreads;
-    if (!chunk_slot<SPREAD>(tid, nthreads)) return;
-    uint32_t* tabs = workspace + (size_t)tid * kHcTableWords;
-    uint8_t* slot = nullptr;
-    if constexpr (!SPREAD) {
-        __shared__ __attribute__((aligned(16))) uint8_t stages[256 * kStageStride];
-        slot = &stages[threadIdx.x * kStageStride];
+// block bases per lane between two zeroings: 65536 + (stamp + j) * kHcStride stays below 2^32 - 2^26
+constexpr uint32_t kHcMaxStamp = (uint32_t)((0xFFFFFFFFull - (1ull << 26) - 65536ull) / kHcStride);
+
+struct HcCodec {
+    using Entry = uint32_t;
+    static constexpr uint32_t kEntries = kHcTableWords;
+    static constexpr WsKind kKind = WsKind::Lz4HcEnc;
+    static constexpr uint32_t kMaxStamp = kHcMaxStamp;
+    static __device__ __forceinline__ bool valid(uint32_t len) { return len <= (1u << 25); }
+    static __device__ __forceinline__ uint32_t stamp(uint32_t base, uint32_t iter) { return 65536u + (base + iter) * kHcStride; }
+    static __device__ __forceinline__ bool unstaged(uint32_t) { return false; }
+    template <class O>
+    static __device__ __forceinline__ uint32_t encode(const uint8_t* in, uint32_t len, O& o, Entry* tabs, uint32_t B) {
+        return encode_block_hc(in, (int32_t)len, o, tabs, B);
     }
-    uint32_t iter = 0;
-    for (uint32_t c = tid; c < n; c += nthreads, ++iter) {
-        const uint32_t len = in_len[c];
-        if (len > (1u << 25)) {
-            out_len[c] = 0;
-            status[c] = NX_ERR_INVALID_ARG;
-            continue;
-        }
-        const uint32_t B = 65536u + (stamp_base + iter) * kHcStride;
-        if (SPREAD) {
-            GOut o{out + out_off[c]};
-            out_len[c] = encode_block_hc(in + in_off[c], (int32_t)len, o, tabs, B);
-        } else {
-            ByteStage o(slot, out + out_off[c]);
-            out_len[c] = encode_block_hc(in + in_off[c], (int32_t)len, o, tabs, B);
-        }
-        status[c] = NX_OK;
-    }
-}
+};
 
 }  // namespace lz4
 }  // namespace nx
 
-namespace {
-constexpr uint32_t kMaxStamp = 0xFFFFu;
-static_assert(nx::kWsSpec[(int)nx::WsKind::Lz4Enc].entry_bytes == sizeof(uint64_t) &&
-                  (1u << nx::kWsSpec[(int)nx::WsKind::Lz4Enc].lg) == nx::lz4::kTableSlots,
-              "LZ4 table geometry");
-}  // namespace
-
 extern "C" size_t nx_lz4_max_compressed_length(size_t n) { return n + n / 255 + 16; }
-
-namespace {
-static_assert(nx::kWsSpec[(int)nx::WsKind::Lz4HcEnc].entry_bytes * (1u << nx::kWsSpec[(int)nx::WsKind::Lz4HcEnc].lg) ==
-                  nx::lz4::kHcTableWords * sizeof(uint32_t),
-              "LZ4 HC table geometry");
-// block bases per lane between two zeroings: 65536 + (stamp + j) * kHcStride stays below 2^32 - 2^26
-constexpr uint32_t kHcMaxStamp = (uint32_t)((0xFFFFFFFFull - (1ull << 26) - 65536ull) / nx::lz4::kHcStride);
-}  // namespace
 
 // Replaces LZ4Compressor.compress for lz4-java's highCompressor() (LZ4_compress_HC level 9) as
 // Lz4FrameEncoder(highCompressor = true).flushBufferedData calls it (Lz4FrameEncoder.java:123-125,
 // 161-163, 259-275); same contract as nx_lz4_encode_batch.
 extern "C" int32_t nx_lz4hc_encode_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
                                          const uint64_t* out_off, uint32_t* out_len, int32_t* status, uint32_t n, void* stream) {
-    NX_CLEAR_STALE_ERROR();
-    if (n == 0) return NX_OK;
-    if (!in || !in_off || !in_len || !out || !out_off || !out_len || !status) return NX_ERR_INVALID_ARG;
-    const hipStream_t st = (hipStream_t)stream;
-    const auto launch = [&](size_t base, uint32_t m, const nx::LaneGrid& g, void* tables, uint32_t stamp) {
-        uint32_t* ws = static_cast<uint32_t*>(tables);
-        if (g.spread)
-            hipLaunchKernelGGL(nx::lz4::k_lz4hc_encode<true>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base, in_len + base, out,
-                               out_off + base, out_len + base, status + base, m, ws, stamp);
-        else
-            hipLaunchKernelGGL(nx::lz4::k_lz4hc_encode<false>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base, in_len + base,
-                               out, out_off + base, out_len + base, status + base, m, ws, stamp);
-    };
-    return nx::ws_lane_launch(nx::WsKind::Lz4HcEnc, kHcMaxStamp, n, st, launch);
+    return nx::lane_encode_batch<nx::lz4::HcCodec>(in, in_off, in_len, out, out_off, out_len, status, n, stream);
 }
 
 // Replaces LZ4Compressor.compress as Lz4FrameEncoder.flushBufferedData calls it for one block
 // (Lz4FrameEncoder.java:259-275); in_len[i] <= 2^25 (MAX_BLOCK_SIZE, Lz4Constants.java / :175-178).
 extern "C" int32_t nx_lz4_encode_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
                                        const uint64_t* out_off, uint32_t* out_len, int32_t* status, uint32_t n, void* stream) {
-    NX_CLEAR_STALE_ERROR();
-    if (n == 0) return NX_OK;
-    if (!in || !in_off || !in_len || !out || !out_off || !out_len || !status) return NX_ERR_INVALID_ARG;
-    const hipStream_t st = (hipStream_t)stream;
-    const auto launch = [&](size_t base, uint32_t m, const nx::LaneGrid& g, void* tables, uint32_t stamp) {
-        uint64_t* ws = static_cast<uint64_t*>(tables);
-        if (g.spread)
-            hipLaunchKernelGGL(nx::lz4::k_lz4_encode<true>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base, in_len + base, out,
-                               out_off + base, out_len + base, status + base, m, ws, stamp);
-        else
-            hipLaunchKernelGGL(nx::lz4::k_lz4_encode<false>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base, in_len + base, out,
-                               out_off + base, out_len + base, status + base, m, ws, stamp);
-    };
-    return nx::ws_lane_launch(nx::WsKind::Lz4Enc, kMaxStamp, n, st, launch);
+    return nx::lane_encode_batch<nx::lz4::Codec>(in, in_off, in_len, out, out_off, out_len, status, n, stream);
 }

@@ -23,8 +23,6 @@ namespace lz4f {
 constexpr uint32_t P1 = 0x9E3779B1u, P2 = 0x85EBCA77u, P3 = 0xC2B2AE3Du, P4 = 0x27D4EB2Fu, P5 = 0x165667B1u;
 constexpr int kHeader = 21;
 
-typedef uint32_t __attribute__((aligned(1))) u32u;
-__device__ __forceinline__ uint32_t ld32(const uint8_t* p) { return *reinterpret_cast<const u32u*>(p); }
 __device__ __forceinline__ uint32_t rotl(uint32_t x, int r) { return __builtin_rotateleft32(x, r); }
 __device__ __forceinline__ uint32_t round1(uint32_t v, uint32_t w) { return rotl(v + w * P2, 13) * P1; }
 

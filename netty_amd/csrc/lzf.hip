@@ -8,7 +8,7 @@
 // orc_lzf_compress_body_ex restates it — hash ((seen * 57321) >> 9) & 16383 of the big-endian int
 // of bytes [p-1, p+2], 3-byte candidate check, MAX_OFF 8192, MAX_REF 264, matchEnd-2/-1 inserts —
 // byte for byte (PARITY UNPINNED vs the library itself: no reference bytes exist offline).
-#include "nx_common.hpp"
+#include "lane_encode.hpp"
 #include "records.hpp"
 
 namespace nx {
@@ -18,11 +18,6 @@ constexpr int HSIZE = 16384;
 constexpr int32_t MAX_OFF = 8192;
 constexpr int32_t MAX_REF = 264;
 constexpr int32_t MAX_LIT = 32;
-
-typedef uint32_t __attribute__((aligned(1))) u32u;
-typedef uint64_t __attribute__((aligned(1))) u64u;
-__device__ __forceinline__ uint32_t ld32(const uint8_t* p) { return *reinterpret_cast<const u32u*>(p); }
-__device__ __forceinline__ uint64_t ld64(const uint8_t* p) { return *reinterpret_cast<const u64u*>(p); }
 
 // ChunkEncoder.hash: Java int multiply (wraps), arithmetic shift
 __device__ __forceinline__ uint32_t jhash(int32_t h) { return (uint32_t)(((int32_t)((uint32_t)h * 57321u) >> 9) & (HSIZE - 1)); }
@@ -187,38 +182,19 @@ __device__ int32_t decode_chunk(const uint8_t* __restrict__ in, int32_t in_len, 
     return op == out_len ? NX_OK : NX_ERR_LZF_CORRUPT;
 }
 
-template <bool SPREAD>
-__global__ void __launch_bounds__(256) k_encode(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
-                                                const uint32_t* __restrict__ in_len, uint8_t* __restrict__ out,
-                                                const uint64_t* __restrict__ out_off, uint32_t* __restrict__ out_len,
-                                                int32_t* __restrict__ status, uint32_t n, uint64_t* __restrict__ ws, uint32_t stamp_base) {
-    uint32_t tid, nthreads;
-    if (!chunk_slot<SPREAD>(tid, nthreads)) return;
-    uint64_t* htab = ws + (size_t)tid * HSIZE;
-    uint8_t* slot = nullptr;
-    if constexpr (!SPREAD) {
-        __shared__ __attribute__((aligned(16))) uint8_t stages[256 * kStageStride];
-        slot = &stages[threadIdx.x * kStageStride];
+struct Codec {  // lane_encode.hpp
+    using Entry = uint64_t;
+    static constexpr uint32_t kEntries = HSIZE;
+    static constexpr WsKind kKind = WsKind::LzfEnc;
+    static constexpr uint32_t kMaxStamp = 65535u;
+    static __device__ __forceinline__ bool valid(uint32_t len) { return len <= 65535u; }
+    static __device__ __forceinline__ uint32_t stamp(uint32_t base, uint32_t iter) { return ((base + iter) % 65535u) + 1u; }
+    static __device__ __forceinline__ bool unstaged(uint32_t) { return false; }
+    template <class O>
+    static __device__ __forceinline__ uint32_t encode(const uint8_t* in, uint32_t len, O& o, Entry* htab, uint32_t stamp) {
+        return encode_chunk(in, (int32_t)len, o, htab, stamp);
     }
-    uint32_t iter = 0;
-    for (uint32_t c = tid; c < n; c += nthreads, ++iter) {
-        const uint32_t len = in_len[c];
-        if (len > 65535u) {
-            status[c] = NX_ERR_INVALID_ARG;
-            out_len[c] = 0;
-            continue;
-        }
-        const uint32_t stamp = ((stamp_base + iter) % 65535u) + 1u;
-        if (SPREAD) {
-            GOut o{out + out_off[c]};
-            out_len[c] = encode_chunk(in + in_off[c], (int32_t)len, o, htab, stamp);
-        } else {
-            ByteStage o(slot, out + out_off[c]);  // dense form: whole 128-byte units (nx_common.hpp)
-            out_len[c] = encode_chunk(in + in_off[c], (int32_t)len, o, htab, stamp);
-        }
-        status[c] = NX_OK;
-    }
-}
+};
 
 // After the record path (records.hpp): blocks it left with kNeedSerial run the lane-serial decoder,
 // which reports the status; the others decoded exactly out_len bytes (NX_OK, already set).
@@ -237,46 +213,16 @@ __global__ void __launch_bounds__(256) k_decode_finish(const uint8_t* __restrict
 }  // namespace lzf
 }  // namespace nx
 
-#include "workspace.hpp"
-static_assert(nx::kWsSpec[(int)nx::WsKind::LzfEnc].entry_bytes == sizeof(uint64_t) &&
-                  (1 << nx::kWsSpec[(int)nx::WsKind::LzfEnc].lg) == nx::lzf::HSIZE,
-              "LZF table geometry");
-
 extern "C" int32_t nx_lzf_encode_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
                                        const uint64_t* out_off, uint32_t* out_len, int32_t* status, uint32_t n, void* stream) {
-    NX_CLEAR_STALE_ERROR();
-    if (n == 0) return NX_OK;
-    if (!in || !in_off || !in_len || !out || !out_off || !out_len || !status) return NX_ERR_INVALID_ARG;
-    const hipStream_t st = (hipStream_t)stream;
-    const auto launch = [&](size_t base, uint32_t m, const nx::LaneGrid& g, void* tables, uint32_t stamp) {
-        uint64_t* ws = static_cast<uint64_t*>(tables);
-        if (g.spread)
-            hipLaunchKernelGGL(nx::lzf::k_encode<true>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base, in_len + base, out,
-                               out_off + base, out_len + base, status + base, m, ws, stamp);
-        else
-            hipLaunchKernelGGL(nx::lzf::k_encode<false>, dim3(g.grid), dim3(g.block), 0, st, in, in_off + base, in_len + base, out,
-                               out_off + base, out_len + base, status + base, m, ws, stamp);
-    };
-    return nx::ws_lane_launch(nx::WsKind::LzfEnc, 65535u, n, st, launch);
+    return nx::lane_encode_batch<nx::lzf::Codec>(in, in_off, in_len, out, out_off, out_len, status, n, stream);
 }
 
-namespace {
-struct LzfDecCtx {
-    const uint8_t* in;
-    const uint64_t* in_off;
-    const uint32_t* in_len;
-    uint8_t* out;
-    const uint64_t* out_off;
-    const uint32_t* out_len;
-    int32_t* status;
-};
-hipError_t lzf_dec_after(uint32_t base, uint32_t m, const uint32_t*, void* ctx, hipStream_t st) {
-    const LzfDecCtx& x = *static_cast<const LzfDecCtx*>(ctx);
+static hipError_t lzf_dec_after(const nx::dec::RecCall& x, uint32_t base, uint32_t m, const uint32_t*, hipStream_t st) {
     hipLaunchKernelGGL(nx::lzf::k_decode_finish, dim3((m + 255) / 256), dim3(256), 0, st, x.in, x.in_off + base, x.in_len + base, x.out,
-                       x.out_off + base, x.out_len + base, x.status + base, m);
+                       x.out_off + base, x.lim + base, x.status + base, m);
     return hipGetLastError();
 }
-}  // namespace
 
 // Blocks go through the record expander (snappy_decode.hip k_parse_lzf + k_expand); corrupt ones
 // through the lane-serial decode_chunk(), which reports them.
@@ -286,7 +232,6 @@ extern "C" int32_t nx_lzf_decode_batch(const uint8_t* in, const uint64_t* in_off
     NX_CLEAR_STALE_ERROR();
     if (n == 0) return NX_OK;
     if (!in || !in_off || !in_len || !out || !out_off || !out_len || !status) return NX_ERR_INVALID_ARG;
-    LzfDecCtx ctx{in, in_off, in_len, out, out_off, out_len, status};
-    return nx::dec::decode_records(nx::dec::RecCodec::Lzf, in, in_off, in_len, nullptr, out_len, out, out_off, status, n,
-                                   (hipStream_t)stream, lzf_dec_after, &ctx);
+    return nx::dec::decode_records(nx::dec::RecCodec::Lzf, {in, in_off, in_len, nullptr, out_len, out, out_off, status}, n,
+                                   (hipStream_t)stream, lzf_dec_after);
 }

@@ -80,6 +80,12 @@ __host__ __device__ inline uint32_t gf_x8n(uint64_t n, uint32_t poly = kCrcPoly)
     return result;
 }
 
+// Unaligned little-endian loads (the matchers' word reads).
+typedef uint32_t __attribute__((aligned(1))) u32u;
+typedef uint64_t __attribute__((aligned(1))) u64u;
+__device__ __forceinline__ uint32_t ld32(const uint8_t* p) { return *reinterpret_cast<const u32u*>(p); }
+__device__ __forceinline__ uint64_t ld64(const uint8_t* p) { return *reinterpret_cast<const u64u*>(p); }
+
 // Lane-per-chunk encoders (LZ4, FastLZ, LZF; Snappy has its own three forms): the dense form gives
 // every lane a chunk; for batches up to kSpreadMaxChunks the SPREAD form gives each wave one chunk
 // on lane 0, so the serial matchers of different chunks never share a wave's divergent control

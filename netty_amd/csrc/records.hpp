@@ -14,21 +14,30 @@ namespace dec {
 
 constexpr int32_t kNeedSerial = -1000;  // = k_parse's kNeedFused: the block goes to the lane-serial path
 
-enum class RecCodec { FastLz, Lzf };
+enum class RecCodec { FastLz, Lzf, Lz4 };
+
+// One call's arrays: block i = in[in_off[i] .. + in_len[i]), at most lim[i] output bytes (FastLZ:
+// outLength; LZF and LZ4: exactly lim[i]) to out + out_off[i]; avail (FastLZ, nullable): readable
+// bytes from the block start.
+struct RecCall {
+    const uint8_t* in;
+    const uint64_t* in_off;
+    const uint32_t* in_len;
+    const uint32_t* avail;
+    const uint32_t* lim;
+    uint8_t* out;
+    const uint64_t* out_off;
+    int32_t* status;
+};
 
 // Called once per sub-batch [base, base + m) after its expand launch, on the same stream: launches
 // the codec's finish kernel (its lane-serial decoder for status kNeedSerial blocks, the result fix-up
 // for the others).  olen[i] = bytes the parse produced for block base + i.
-using RecAfter = hipError_t (*)(uint32_t base, uint32_t m, const uint32_t* olen, void* ctx, hipStream_t st);
+using RecAfter = hipError_t (*)(const RecCall& call, uint32_t base, uint32_t m, const uint32_t* olen, hipStream_t st);
 
-// Parse + expand of n blocks: block i = in[in_off[i] .. + in_len[i]), at most lim[i] output bytes
-// (FastLZ: outLength; LZF: exactly lim[i]) to out + out_off[i]; avail (FastLZ, nullable): readable
-// bytes from the block start.  status[i] is the parse/expand status (NX_OK or kNeedSerial) when
-// `after` runs.
-int32_t decode_records(RecCodec codec, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint32_t* avail,
-                       const uint32_t* lim,
-                       uint8_t* out, const uint64_t* out_off, int32_t* status, uint32_t n, hipStream_t st, RecAfter after,
-                       void* ctx);
+// Parse + expand of the call's n blocks; status[i] is the parse/expand status (NX_OK or kNeedSerial)
+// when `after` runs.
+int32_t decode_records(RecCodec codec, const RecCall& call, uint32_t n, hipStream_t st, RecAfter after);
 
 }  // namespace dec
 }  // namespace nx

@@ -1699,6 +1699,36 @@ static hipError_t launch_expand(const uint8_t* in, const uint64_t* in_off, const
     return hipGetLastError();
 }
 
+// What every decode call sets up first: the CRC tables, the device's CU count, the wave kernels' LDS limit.
+constexpr size_t kFusedLds = nx::dec::kTabBytes + nx::dec::kWaves * sizeof(nx::dec::WaveLds);
+static_assert(kFusedLds <= 160 * 1024, "a k_decode_fused block fits a CU's LDS");
+static int32_t dec_setup(int* dev, int* cus) {
+    if (nx::crc_tables_init() != NX_OK) return NX_ERR_HIP;
+    NX_HIP_CHECK(hipGetDevice(dev));
+    NX_HIP_CHECK(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, *dev));
+    NX_HIP_CHECK(wave_kernel_attrs(kFusedLds));
+    return NX_OK;
+}
+
+// The record path's driver: leases record slots for n blocks (a part lease; a held workspace caps them)
+// and runs body(base, m, slots, cus) for every sub-batch [base, base + m) of at most that many blocks.
+template <class Body>
+static int32_t record_batches(uint32_t n, hipStream_t st, Body&& body) {
+    int dev = 0, cus = 256;
+    const int32_t r = dec_setup(&dev, &cus);
+    if (r != NX_OK) return r;
+    nx::WsLease lease(nx::WsKind::DecRecords, dev, st);
+    size_t first = 0, count = 0;
+    NX_HIP_CHECK(lease.acquire_part(nx::ws_want(nx::WsKind::DecRecords, n, cus), &first, &count));
+    const DecSlots W = dec_slots(lease.ws(), first, count);
+    const uint32_t sb = n < W.frames ? n : W.frames;
+    for (uint32_t base = 0; base < n; base += sb) {
+        const int32_t rb = body(base, n - base < sb ? n - base : sb, W, cus);
+        if (rb != NX_OK) return rb;
+    }
+    return NX_OK;
+}
+
 static int32_t decode_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out, const uint64_t* out_off,
                             const uint32_t* out_cap, uint32_t* out_len, uint32_t* consumed, int32_t* status,
                             const uint32_t* expected_masked_crc, uint32_t* crc_out, uint32_t n, void* stream, int mode) {
@@ -1706,18 +1736,9 @@ static int32_t decode_batch(const uint8_t* in, const uint64_t* in_off, const uin
     using namespace nx::dec;
     if (n == 0) return NX_OK;
     if (!in || !in_off || !in_len || !out || !out_off || !out_len || !status) return NX_ERR_INVALID_ARG;
-    if (nx::crc_tables_init() != NX_OK) return NX_ERR_HIP;
-    int dev = 0, cus = 256;
-    NX_HIP_CHECK(hipGetDevice(&dev));
-    NX_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const size_t lds = kTabBytes + kWaves * sizeof(WaveLds);
-    NX_HIP_CHECK(wave_kernel_attrs(lds));
-    unsigned blocks_per_cu = (unsigned)(160 * 1024 / lds);
-    if (blocks_per_cu < 1) blocks_per_cu = 1;
     const hipStream_t st = (hipStream_t)stream;
-    const uint64_t want = (uint64_t)cus * blocks_per_cu;
-    auto wave_grid = [&](uint32_t m) {
-        const uint64_t need = (m + kWaves - 1) / kWaves;
+    auto wave_grid = [](uint32_t m, int cus) {
+        const uint64_t want = (uint64_t)cus * (160 * 1024 / kFusedLds), need = (m + kWaves - 1) / kWaves;
         return (unsigned)(need < want ? need : want);
     };
     // Batch-size policy (round 5, profiles/r05/s1/dec_latency.log): k_parse walks a frame's tags on
@@ -1726,18 +1747,15 @@ static int32_t decode_batch(const uint8_t* in, const uint64_t* in_off, const uin
     // 7.4 / 9.1 for the pair).  The pair wins from ~34 K frames on (65 536: 16.4 vs 20.5 ms).
     const bool fused_only = mode == kDecodeFused || (mode == kDecodeAuto && n <= kFusedMaxFrames);
     if (fused_only) {
-        hipLaunchKernelGGL(k_decode_fused, dim3(wave_grid(n)), dim3(kWaves * 64), lds, st, in, in_off, in_len, out, out_off, out_cap,
-                           out_len, consumed, status, expected_masked_crc, crc_out, n, nx::crc_tables_dev(), 0, nullptr);
+        int dev = 0, cus = 256;
+        const int32_t r = dec_setup(&dev, &cus);
+        if (r != NX_OK) return r;
+        hipLaunchKernelGGL(k_decode_fused, dim3(wave_grid(n, cus)), dim3(kWaves * 64), kFusedLds, st, in, in_off, in_len, out, out_off,
+                           out_cap, out_len, consumed, status, expected_masked_crc, crc_out, n, nx::crc_tables_dev(), 0, nullptr);
         NX_HIP_CHECK(hipGetLastError());
         return NX_OK;
     }
-    nx::WsLease lease(nx::WsKind::DecRecords, dev, st);
-    size_t first = 0, count = 0;
-    NX_HIP_CHECK(lease.acquire_part(nx::ws_want(nx::WsKind::DecRecords, n, cus), &first, &count));
-    const DecSlots W = dec_slots(lease.ws(), first, count);
-    const uint32_t sb = n < W.frames ? n : W.frames;  // a held workspace caps the sub-batch
-    for (uint32_t base = 0; base < n; base += sb) {
-        const uint32_t m = n - base < sb ? n - base : sb;
+    return record_batches(n, st, [&](uint32_t base, uint32_t m, const DecSlots& W, int cus) -> int32_t {
         // W.olen[0] (unused by this path): set when any frame of the sub-batch is handed to the fallback
         NX_HIP_CHECK(hipMemsetAsync(W.olen, 0, sizeof(uint32_t), st));
         hipLaunchKernelGGL(k_parse, dim3((m + kParseBlock - 1) / kParseBlock), dim3(kParseBlock), 0, st, in, in_off + base, in_len + base,
@@ -1748,13 +1766,14 @@ static int32_t decode_batch(const uint8_t* in, const uint64_t* in_off, const uin
                                    expected_masked_crc ? expected_masked_crc + base : nullptr, crc_out ? crc_out + base : nullptr, m,
                                    cus, st));
         // frames k_parse could not slot (more than kRecCap records, or input >= 32 MiB)
-        hipLaunchKernelGGL(k_decode_fused, dim3(wave_grid(m)), dim3(kWaves * 64), lds, st, in, in_off + base, in_len + base, out,
-                           out_off + base, out_cap ? out_cap + base : nullptr, out_len + base, consumed ? consumed + base : nullptr,
-                           status + base, expected_masked_crc ? expected_masked_crc + base : nullptr,
-                           crc_out ? crc_out + base : nullptr, m, nx::crc_tables_dev(), 1, W.olen);
+        hipLaunchKernelGGL(k_decode_fused, dim3(wave_grid(m, cus)), dim3(kWaves * 64), kFusedLds, st, in, in_off + base, in_len + base,
+                           out, out_off + base, out_cap ? out_cap + base : nullptr, out_len + base,
+                           consumed ? consumed + base : nullptr, status + base,
+                           expected_masked_crc ? expected_masked_crc + base : nullptr, crc_out ? crc_out + base : nullptr, m,
+                           nx::crc_tables_dev(), 1, W.olen);
         NX_HIP_CHECK(hipGetLastError());
-    }
-    return NX_OK;
+        return NX_OK;
+    });
 }
 
 extern "C" int32_t nx_snappy_decode_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
@@ -1782,6 +1801,12 @@ extern "C" int32_t nx_snappy_decode_batch_pair(const uint8_t* in, const uint64_t
                         nx::dec::kDecodePair);
 }
 
+static hipError_t lz4_dec_after(const nx::dec::RecCall& x, uint32_t base, uint32_t m, const uint32_t*, hipStream_t st) {
+    hipLaunchKernelGGL(nx::dec::k_lz4_serial, dim3((m + 255) / 256), dim3(256), 0, st, x.in, x.in_off + base, x.in_len + base,
+                       x.lim + base, x.out, x.out_off + base, x.status + base, m);
+    return hipGetLastError();
+}
+
 // Replaces LZ4FastDecompressor.decompress as Lz4FrameDecoder.decode calls it for one
 // BLOCK_TYPE_COMPRESSED block (Lz4FrameDecoder.java:199-208): block i = in[in_off[i] .. +in_len[i])
 // must decode to exactly out_len[i] bytes at out + out_off[i].
@@ -1789,76 +1814,32 @@ extern "C" int32_t nx_lz4_decode_batch(const uint8_t* in, const uint64_t* in_off
                                        const uint64_t* out_off, const uint32_t* out_len, int32_t* status, uint32_t n,
                                        void* stream) {
     NX_CLEAR_STALE_ERROR();
-    using namespace nx::dec;
     if (n == 0) return NX_OK;
     if (!in || !in_off || !in_len || !out || !out_off || !out_len || !status) return NX_ERR_INVALID_ARG;
-    if (nx::crc_tables_init() != NX_OK) return NX_ERR_HIP;
-    int dev = 0, cus = 256;
-    NX_HIP_CHECK(hipGetDevice(&dev));
-    NX_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const size_t lds = kTabBytes + kWaves * sizeof(WaveLds);
-    NX_HIP_CHECK(wave_kernel_attrs(lds));
-    unsigned blocks_per_cu = (unsigned)(160 * 1024 / lds);
-    if (blocks_per_cu < 1) blocks_per_cu = 1;
-    const hipStream_t st = (hipStream_t)stream;
-    const uint64_t want = (uint64_t)cus * blocks_per_cu;
-    nx::WsLease lease(nx::WsKind::DecRecords, dev, st);
-    size_t first = 0, count = 0;
-    NX_HIP_CHECK(lease.acquire_part(nx::ws_want(nx::WsKind::DecRecords, n, cus), &first, &count));
-    const DecSlots Ws = dec_slots(lease.ws(), first, count);
-    const DecSlots* W = &Ws;
-    const uint32_t sb = n < W->frames ? n : W->frames;
-    for (uint32_t base = 0; base < n; base += sb) {
-        const uint32_t m = n - base < sb ? n - base : sb;
-        const uint64_t need = (m + kWaves - 1) / kWaves;
-        hipLaunchKernelGGL(k_parse_lz4, dim3((m + kParseBlock - 1) / kParseBlock), dim3(kParseBlock), 0, st, in, in_off + base,
-                           in_len + base, out_len + base, W->rec, W->nrec, W->olen, status + base, m);
-        NX_HIP_CHECK(hipGetLastError());
-        (void)need;
-        (void)want;
-        NX_HIP_CHECK(launch_expand(in, in_off + base, in_len + base, out, out_off + base, W->rec, W->nrec, W->olen, status + base, nullptr,
-                                   nullptr, m, cus, st));
-        hipLaunchKernelGGL(k_lz4_serial, dim3((m + 255) / 256), dim3(256), 0, st, in, in_off + base, in_len + base, out_len + base,
-                           out, out_off + base, status + base, m);
-        NX_HIP_CHECK(hipGetLastError());
-    }
-    return NX_OK;
+    return nx::dec::decode_records(nx::dec::RecCodec::Lz4, {in, in_off, in_len, nullptr, out_len, out, out_off, status}, n,
+                                   (hipStream_t)stream, lz4_dec_after);
 }
 
-// FastLZ / LZF blocks: codec parse -> k_expand -> the codec's finish kernel (records.hpp).
-int32_t nx::dec::decode_records(RecCodec codec, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint32_t* avail,
-                                const uint32_t* lim,
-                                uint8_t* out, const uint64_t* out_off, int32_t* status, uint32_t n, hipStream_t st, RecAfter after,
-                                void* ctx) {
+// LZ4 / FastLZ / LZF blocks: codec parse -> k_expand -> the codec's finish kernel (records.hpp).
+int32_t nx::dec::decode_records(RecCodec codec, const RecCall& x, uint32_t n, hipStream_t st, RecAfter after) {
     NX_CLEAR_STALE_ERROR();
     static_assert(kNeedSerial == kNeedFused, "one marker for the serial fallback");
     if (n == 0) return NX_OK;
-    if (nx::crc_tables_init() != NX_OK) return NX_ERR_HIP;
-    int dev = 0, cus = 256;
-    NX_HIP_CHECK(hipGetDevice(&dev));
-    NX_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const size_t lds = kTabBytes + kWaves * sizeof(WaveLds);
-    NX_HIP_CHECK(wave_kernel_attrs(lds));
-    unsigned blocks_per_cu = (unsigned)(160 * 1024 / lds);
-    if (blocks_per_cu < 1) blocks_per_cu = 1;
-    nx::WsLease lease(nx::WsKind::DecRecords, dev, st);
-    size_t first = 0, count = 0;
-    NX_HIP_CHECK(lease.acquire_part(nx::ws_want(nx::WsKind::DecRecords, n, cus), &first, &count));
-    const DecSlots W = dec_slots(lease.ws(), first, count);
-    const uint32_t sb = n < W.frames ? n : W.frames;
-    for (uint32_t base = 0; base < n; base += sb) {
-        const uint32_t m = n - base < sb ? n - base : sb;
+    return record_batches(n, st, [&](uint32_t base, uint32_t m, const DecSlots& W, int cus) -> int32_t {
         const dim3 pg((m + kParseBlock - 1) / kParseBlock), pb(kParseBlock);
         if (codec == RecCodec::FastLz)
-            hipLaunchKernelGGL(k_parse_fastlz, pg, pb, 0, st, in, in_off + base, in_len + base, avail ? avail + base : nullptr,
-                               lim + base, W.rec, W.nrec, W.olen, status + base, m);
+            hipLaunchKernelGGL(k_parse_fastlz, pg, pb, 0, st, x.in, x.in_off + base, x.in_len + base, x.avail ? x.avail + base : nullptr,
+                               x.lim + base, W.rec, W.nrec, W.olen, x.status + base, m);
+        else if (codec == RecCodec::Lzf)
+            hipLaunchKernelGGL(k_parse_lzf, pg, pb, 0, st, x.in, x.in_off + base, x.in_len + base, x.lim + base, W.rec, W.nrec, W.olen,
+                               x.status + base, m);
         else
-            hipLaunchKernelGGL(k_parse_lzf, pg, pb, 0, st, in, in_off + base, in_len + base, lim + base, W.rec, W.nrec, W.olen,
-                               status + base, m);
+            hipLaunchKernelGGL(k_parse_lz4, pg, pb, 0, st, x.in, x.in_off + base, x.in_len + base, x.lim + base, W.rec, W.nrec, W.olen,
+                               x.status + base, m);
         NX_HIP_CHECK(hipGetLastError());
-        NX_HIP_CHECK(launch_expand(in, in_off + base, in_len + base, out, out_off + base, W.rec, W.nrec, W.olen, status + base, nullptr,
-                                   nullptr, m, cus, st));
-        NX_HIP_CHECK(after(base, m, W.olen, ctx, st));
-    }
-    return NX_OK;
+        NX_HIP_CHECK(launch_expand(x.in, x.in_off + base, x.in_len + base, x.out, x.out_off + base, W.rec, W.nrec, W.olen,
+                                   x.status + base, nullptr, nullptr, m, cus, st));
+        NX_HIP_CHECK(after(x, base, m, W.olen, st));
+        return NX_OK;
+    });
 }

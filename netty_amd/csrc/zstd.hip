@@ -38,9 +38,6 @@ constexpr uint32_t kSeqOff = kLitOff + kMaxChunk;
 constexpr uint32_t kSeqCap = kMaxChunk / 4u;  // a sequence takes at least four bytes of the chunk
 constexpr uint32_t kHufMaxBits = 11;
 
-typedef uint32_t __attribute__((aligned(1))) u32u;
-__device__ __forceinline__ uint32_t ld32(const uint8_t* p) { return *reinterpret_cast<const u32u*>(p); }
-
 // ---------------------------------------------------------------------------------------- pass 1
 __device__ __forceinline__ void match_chunk(const uint8_t* __restrict__ in, uint32_t n, uint8_t* __restrict__ slot, uint32_t stamp) {
     uint64_t* table = reinterpret_cast<uint64_t*>(slot);

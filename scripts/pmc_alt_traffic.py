@@ -15,7 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 
 LEGS = ("fastlz_l1", "fastlz_l2", "lzf", "lz4")
-ENCODERS = ("nx::flz::k_compress", "nx::lzf::k_encode", "nx::lz4::k_lz4_encode")
+ENCODERS = ("nx::flz::k_compress", "nx::k_lane_encode")  # LZF and LZ4: instantiations of the lane shell
 SKIP = ("nx::k_ws_probe",)          # the encoder workspace's placement probe (a one-off before an encoder)
 STOP = ("nx::lz4f::k_xxhash32",)    # the LZ4 frame leg that follows the four block legs
 CALLS = 2  # warm-up + timed

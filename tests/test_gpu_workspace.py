@@ -92,6 +92,82 @@ def test_handle_message_beyond_its_reservation(nx, B, oracle):
     e.close()
 
 
+# One stream of 1025 blocks per decoder: 1024 small compressed blocks, then one valid block of more
+# records than a record slot holds (16384), which the record parse leaves to the lane-serial decoder.
+_SERIAL_MATCHES = 21000
+
+
+def _small(i):
+    return b"netty %04d channel pipeline " % i * 2  # 58 bytes: every codec compresses them
+
+
+def _lz4_stream(oracle):
+    blocks = [oracle.lz4_frame_encode(_small(i), close=False) for i in range(1024)]
+    assert all(b[8] & 0xF0 == 0x20 for b in blocks)  # compressed
+    # 'a', then _SERIAL_MATCHES four-byte matches at distance 1, then the five last literals
+    body = b"\x10a\x01\x00" + b"\x00\x01\x00" * (_SERIAL_MATCHES - 1) + b"\x50aaaaa"
+    n = 1 + 4 * _SERIAL_MATCHES + 5
+    last = oracle.LZ4_MAGIC + bytes([0x20 | 7]) + len(body).to_bytes(4, "little") + n.to_bytes(4, "little") + bytes(4)
+    return b"".join(blocks) + last + body, n
+
+
+def _fastlz_stream(oracle):
+    blocks = [oracle.fastlz_frame_encode(_small(i)) for i in range(1024)]
+    assert all(b[3] == 0x01 for b in blocks)  # compressed, no checksum
+    body = bytes([0, ord("a")]) + bytes([1 << 5, 0]) * _SERIAL_MATCHES  # test_gpu_fastlz_lzf._fastlz_many_matches
+    n = 1 + 3 * _SERIAL_MATCHES
+    return b"".join(blocks) + b"FLZ\x01" + len(body).to_bytes(2, "big") + n.to_bytes(2, "big") + body, n
+
+
+def _lzf_stream(oracle):
+    blocks = [oracle.lzf_frame_encode(_small(i)) for i in range(1024)]
+    assert all(b[:3] == b"ZV\x01" for b in blocks)  # compressed
+    body = bytes([0, ord("a")]) + bytes([0x20, 0]) * _SERIAL_MATCHES  # as test_lzf_decode_record_path_edges
+    n = 1 + 3 * _SERIAL_MATCHES
+    return b"".join(blocks) + b"ZV\x01" + len(body).to_bytes(2, "big") + n.to_bytes(2, "big") + body, n
+
+
+@pytest.mark.parametrize("codec", ["lz4", "fastlz", "lzf"])
+def test_decoder_call_beyond_its_record_slots(nx, B, oracle, codec):
+    """A decoder handle holds 1024 record slots; one call with 1025 blocks runs in sub-batches of 1024
+    and 1 without growing them.  The lone block of the second sub-batch is one the record parse leaves
+    to the codec's lane-serial decoder, so that runs with base 1024.  The oracle's messages, in order."""
+    from oracle import frame_decoders as F
+    _collect(B)
+    stream, n_last = {"lz4": _lz4_stream, "fastlz": _fastlz_stream, "lzf": _lzf_stream}[codec](oracle)
+    want, err = F.run({"lz4": lambda: F.Lz4FrameDecoder(False), "fastlz": lambda: F.FastLzFrameDecoder(False),
+                       "lzf": F.LzfDecoder}[codec](), [stream])
+    assert err is None and len(want) == 1025 and want[0] == _small(0) and want[-1] == b"a" * n_last
+    d = {"lz4": lambda: nx.Lz4FrameDecoder(False), "fastlz": lambda: nx.FastLzFrameDecoder(False), "lzf": nx.LzfDecoder}[codec]()
+    held, _ = B.workspace_info(B.WS_DEC_RECORDS)
+    assert d.channel_read(stream) == want
+    assert B.workspace_info(B.WS_DEC_RECORDS)[0] == held
+    d.close()
+
+
+@pytest.mark.parametrize("codec", ["lzf", "fastlz", "lz4", "lz4hc"])
+def test_encoder_message_beyond_its_table_slots(nx, B, oracle, codec):
+    """An encoder handle holds 1024 table slots; a message of 1025 units runs on that grid without
+    growing it, so one wave encodes two units in turn (the second with the next stamp), and its bytes
+    equal the oracle's.  A unit is the largest chunk of LZF and FastLZ, the smallest block of LZ4."""
+    _collect(B)
+    unit = 64 if codec.startswith("lz4") else 65535
+    msg = b"".join(oracle.textgen_chunk(900 + i, unit) for i in range(1025))
+    if codec == "lzf":
+        e, kind, want = nx.LzfEncoder(), B.WS_LZF_ENC, oracle.lzf_frame_encode(msg)
+    elif codec == "fastlz":
+        e, kind, want = nx.FastLzFrameEncoder(), B.WS_FASTLZ_ENC, oracle.fastlz_frame_encode(msg)
+    else:
+        high = codec == "lz4hc"
+        e, kind = nx.Lz4FrameEncoder(unit, high_compressor=high), B.WS_LZ4HC_ENC if high else B.WS_LZ4_ENC
+        want = oracle.lz4_frame_encode(msg, block_size=unit, close=False, high=high)
+    held, _ = B.workspace_info(kind)
+    assert held > 0
+    assert e.encode(msg) == want
+    assert B.workspace_info(kind)[0] == held
+    e.close()
+
+
 def test_batcher_large_flushes_on_all_streams_one_workspace(nx, B, oracle):
     """Eight flushes of 16 500 encoder slices each (two on each of the batcher's four streams, all in
     flight together) and two 16 500-chunk decoder jobs: the workspaces reserved by nx_batcher_reserve
