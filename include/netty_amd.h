@@ -81,6 +81,7 @@ int32_t nx_snappy_encode_batch(const uint8_t* in, const uint64_t* in_off, const 
 #define NX_WS_BZIP2_ENC 10
 #define NX_WS_LZMA_ENC 11
 #define NX_WS_BROTLI_ENC 12
+#define NX_WS_BROTLI_DEC 13
 int32_t nx_snappy_encoder_reserve(uint32_t max_chunks, void* stream);
 /* The same with a bound (round 6): max_bytes caps the Snappy table workspace for good (0: no cap; 128
  * KiB per lane, whole blocks of 256 lanes above 16 384): batches of any size then run on those lanes
@@ -344,6 +345,74 @@ typedef struct nx_brotli_encode_stats {
  * out_cap; nothing is written past it) or NX_ERR_INVALID_ARG.  stats may be NULL.
  */
 int64_t nx_brotli_encode_host(const uint8_t* in, size_t n, int32_t lgwin, uint8_t* out, size_t out_cap, nx_brotli_encode_stats* stats);
+
+/*
+ * Replaces BrotliDecoder.java:76-149 (a loop over brotli4j's DecoderJNI.Wrapper, that is libbrotli's
+ * BrotliDecoderDecompressStream) for n independent, complete Brotli streams (RFC 7932).  Item i is the stream that
+ * starts at in[in_off[i]]; bytes after its end inside in_len[i] are left alone (BrotliDecoder skips what follows
+ * DONE).  Its bytes go to out[out_off[i] .. + out_cap[i]) and nothing is ever written outside that range.
+ *   consumed[i] = the stream's size, through the byte that holds the last bit of the ISLAST meta-block, whose
+ *                 remaining bits must be zero (0 on an error);
+ *   out_len[i]  = the decoded size; on an error, what was written before it: the meta-blocks and commands
+ *                 completed before the failing one, and of a failing command with more than 1024 literals the
+ *                 1024-byte pieces of them handed over before the error was met (an uncompressed meta-block that
+ *                 does not fit or is cut short writes nothing, nor does the piece or copy that fails);
+ *   status[i]   = NX_OK or one NX_ERR_BROTLI_* code (netty_amd_status.h), one per format error of libbrotli's
+ *     decoder with the same meaning: EXUBERANT_NIBBLE, RESERVED, EXUBERANT_META_NIBBLE, SIMPLE_HUFFMAN_ALPHABET,
+ *     SIMPLE_HUFFMAN_SAME, CL_SPACE, HUFFMAN_SPACE, CONTEXT_MAP_REPEAT, BLOCK_LENGTH_1, BLOCK_LENGTH_2, TRANSFORM,
+ *     DICTIONARY, WINDOW_BITS, PADDING_1, PADDING_2, DISTANCE, and this library's own TRUNCATED (the input ends
+ *     inside the stream; the reference waits for more) and OUTPUT_FULL.
+ * Everything of RFC 7932: WBITS 10-24, metadata and uncompressed meta-blocks, up to 256 block types per category,
+ * the four context modes, both context maps, simple and complex prefix codes, the distance ring, NPOSTFIX and
+ * NDIRECT, the static dictionary with its 121 transforms.  Large-window streams (WBITS 0010001) are refused with
+ * WINDOW_BITS, as libbrotli refuses them unless asked to (brotli4j never asks); there are no shared or custom
+ * dictionaries.
+ * Differences from libbrotli.  An over-run of a meta-block is decided from the command's lengths before the command
+ * writes, where libbrotli writes the literals or the copy first: BLOCK_LENGTH_1 if the over-running literals, copy
+ * or dictionary word reach the end of libbrotli's ring buffer (whose size the core computes as
+ * BrotliCalculateRingBufferSize does: the window, halved while the half holds the position plus MLEN, 1024 at
+ * least, never shrinking), BLOCK_LENGTH_2 otherwise, which is where libbrotli finds each.  An
+ * error met after the reader passed the input's end is TRUNCATED, where libbrotli stops at the end of the input and
+ * waits.  A command that produces no byte from no bit (no literals, a dictionary word that transforms to nothing,
+ * codes of one symbol), on which libbrotli spins, is DICTIONARY.  The tests hold one complete invalid stream per
+ * format code against BrotliDecoderGetErrorCode.
+ * One wave per stream: lane 0 runs the format core (csrc/brotli_decode_core.hpp), the wave copies.  One slot of
+ * NX_WS_BROTLI_DEC workspace per stream in flight (802 304 bytes: a meta-block's trees and context maps at their
+ * maxima; at most 4 per CU), larger batches run on those slots in turn.  nx_brotli_decoder_reserve(max_streams)
+ * sizes that workspace at start-up and caps it at max_streams slots until nx_workspaces_trim.  The static
+ * dictionary is uploaded once per device and kept for the life of the process: by nx_brotli_decoder_reserve, or
+ * else by the first batch call, which then blocks for a 120 KB copy and must not run inside a stream capture.
+ */
+int32_t nx_brotli_decode_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                               const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len, uint32_t* consumed,
+                               int32_t* status, uint32_t n, void* stream);
+int32_t nx_brotli_decoder_reserve(uint32_t max_streams, void* stream);
+/* What a stream used (nx_brotli_decode_host): meta-blocks by kind (a metadata meta-block counts as metadata
+ * whatever its skip; metadata_skipped sums the skips), the largest NBLTYPES per category (literal, command,
+ * distance), NTREESL and NTREESD, zero runs and inverse move-to-front uses of the context maps, the context modes
+ * seen (bit m: mode m), the largest NPOSTFIX and NDIRECT, prefix codes by kind (simple_codes[k]: NSYM = k + 1;
+ * simple_four_shapes: bit s for a four-symbol code of tree-select s), uses of the repeat codes 16 and 17, the
+ * distance symbols 0..15 read (bit c; the implicit last distance of a command below 128 is not one), dictionary
+ * references and the transforms they used (bit t of the 128). */
+typedef struct nx_brotli_decode_stats {
+    uint32_t mb_compressed, mb_uncompressed, mb_metadata, mb_empty_last, metadata_skipped;
+    uint32_t max_nbltypes[3], max_ntrees_l, max_ntrees_d;
+    uint32_t cmap_rle_runs, cmap_imtf, context_modes, max_npostfix, max_ndirect;
+    uint32_t simple_codes[4], simple_four_shapes, complex_codes, repeat_16, repeat_17;
+    uint32_t ring_codes, dict_refs, transforms[4];
+} nx_brotli_decode_stats;
+/*
+ * The first stream of in[0..n) decoded on the host, single-threaded, by the same format functions the kernel
+ * runs, with the contract and codes of an item of nx_brotli_decode_batch.  NOT a product path: it is the CPU
+ * check of the format logic and the GPU tests' second opinion.  stats may be NULL; it is zeroed first.
+ * nx_brotli_transform_word: word[0, len) (len 4..24) under transform 0..120 of RFC 7932 Appendix B into out (at
+ * least 37 bytes); returns the result's length, or NX_ERR_INVALID_ARG.
+ * nx_brotli_dictionary: the 122 784 bytes of RFC 7932 Appendix A (CRC-32 0x5136cb04).
+ */
+int32_t nx_brotli_decode_host(const uint8_t* in, size_t n, uint8_t* out, size_t out_cap, size_t* out_len, size_t* consumed,
+                              nx_brotli_decode_stats* stats);
+int32_t nx_brotli_transform_word(uint32_t transform, const uint8_t* word, uint32_t len, uint8_t* out);
+const uint8_t* nx_brotli_dictionary(size_t* size);
 
 /*
  * Replaces Zstd.decompress as ZstdDecoder.java calls it through zstd-jni (ZSTD_decompress on one frame),

@@ -161,6 +161,29 @@
 #define NX_ERR_BROTLI_MODE                (-152)
 /* This library's own: the stream does not fit the output slot. */
 #define NX_ERR_BROTLI_ENCODE_FULL         (-153)
+/* Brotli stream decoding (nx_brotli_decode_batch, nx_brotli_decode_host; what brotli4j's DecoderJNI reports to
+ * BrotliDecoder.java as ERROR): one code per format error of libbrotli's decoder (decode.h,
+ * BROTLI_DECODER_ERROR_FORMAT_*), with the same meanings. */
+#define NX_ERR_BROTLI_EXUBERANT_NIBBLE        (-154)  /* MLEN's last nibble is zero though MNIBBLES > 4 */
+#define NX_ERR_BROTLI_RESERVED                (-155)  /* the reserved bit of a metadata meta-block is set */
+#define NX_ERR_BROTLI_EXUBERANT_META_NIBBLE   (-156)  /* MSKIPLEN's last byte is zero though MSKIPBYTES > 1 */
+#define NX_ERR_BROTLI_SIMPLE_HUFFMAN_ALPHABET (-157)  /* a simple code's symbol is outside the alphabet */
+#define NX_ERR_BROTLI_SIMPLE_HUFFMAN_SAME     (-158)  /* a simple code names a symbol twice */
+#define NX_ERR_BROTLI_CL_SPACE                (-159)  /* the code-length code is over- or under-subscribed */
+#define NX_ERR_BROTLI_HUFFMAN_SPACE           (-160)  /* a prefix code is over- or under-subscribed */
+#define NX_ERR_BROTLI_CONTEXT_MAP_REPEAT      (-161)  /* a zero run of a context map passes its end */
+#define NX_ERR_BROTLI_BLOCK_LENGTH_1          (-162)  /* a command passes the end of the meta-block and reaches the end of libbrotli's ring buffer */
+#define NX_ERR_BROTLI_BLOCK_LENGTH_2          (-163)  /* a command passes the end of the meta-block, short of the ring buffer's end */
+#define NX_ERR_BROTLI_TRANSFORM               (-164)  /* a dictionary reference's transform index is 121 or more */
+#define NX_ERR_BROTLI_DICTIONARY              (-165)  /* a dictionary reference with a copy length outside 4..24 */
+#define NX_ERR_BROTLI_WINDOW_BITS             (-166)  /* WBITS 0010001, the large-window escape */
+#define NX_ERR_BROTLI_PADDING_1               (-167)  /* non-zero padding before uncompressed or metadata bytes */
+#define NX_ERR_BROTLI_PADDING_2               (-168)  /* non-zero padding after the last meta-block */
+#define NX_ERR_BROTLI_DISTANCE                (-169)  /* a distance of zero or less from the ring, or above 0x7FFFFFFC */
+/* This library's own: the input ends inside the stream (the reference waits for more input). */
+#define NX_ERR_BROTLI_TRUNCATED               (-170)
+/* This library's own: the decoded bytes do not fit out_cap. */
+#define NX_ERR_BROTLI_OUTPUT_FULL             (-171)
 
 /* Device frame scan (nx_snappy_frame_scan_batch), one code per SnappyFrameDecoder throw site: */
 /* :116-118  "Unexpected length of stream identifier: %d" */

@@ -33,6 +33,14 @@ class BrotliEncodeStats(C.Structure):  # nx_brotli_encode_stats
                 ("complex_codes", C.c_uint64), ("limited_codes", C.c_uint64), ("max_depth_unlimited", C.c_uint64)]
 
 
+class BrotliDecodeStats(C.Structure):  # nx_brotli_decode_stats
+    _fields_ = [("mb_compressed", u32), ("mb_uncompressed", u32), ("mb_metadata", u32), ("mb_empty_last", u32), ("metadata_skipped", u32),
+                ("max_nbltypes", u32 * 3), ("max_ntrees_l", u32), ("max_ntrees_d", u32), ("cmap_rle_runs", u32), ("cmap_imtf", u32),
+                ("context_modes", u32), ("max_npostfix", u32), ("max_ndirect", u32), ("simple_codes", u32 * 4), ("simple_four_shapes", u32),
+                ("complex_codes", u32), ("repeat_16", u32), ("repeat_17", u32), ("ring_codes", u32), ("dict_refs", u32),
+                ("transforms", u32 * 4)]
+
+
 class NxMsg(C.Structure):
     _fields_ = [("data", C.POINTER(C.c_uint8)), ("len", C.c_size_t)]
 
@@ -119,6 +127,11 @@ _SIGS = {
     "nx_brotli_max_compressed_length": (sz, [sz]),
     "nx_brotli_encode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, i32, vp]),
     "nx_brotli_encode_host": (i64, [C.c_char_p, sz, i32, vp, sz, vp]),
+    "nx_brotli_decode_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]),
+    "nx_brotli_decoder_reserve": (i32, [u32, vp]),
+    "nx_brotli_decode_host": (i32, [C.c_char_p, sz, vp, sz, C.POINTER(sz), C.POINTER(sz), vp]),
+    "nx_brotli_transform_word": (i32, [u32, C.c_char_p, u32, vp]),
+    "nx_brotli_dictionary": (vp, [C.POINTER(sz)]),
     "nx_brotli_encoder_check": (i32, [i32, i32, i32]),
     "nx_brotli_encoder_new": (vp, [i32, i32, i32]),
     "nx_brotli_encoder_free": (None, [vp]),

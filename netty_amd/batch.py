@@ -25,7 +25,7 @@ def _chk(rc, what):
 
 
 # Shared device workspaces (include/netty_amd.h NX_WS_*; csrc/workspace.hpp)
-WS_SNAPPY_ENC, WS_LZ4_ENC, WS_FASTLZ_ENC, WS_LZF_ENC, WS_DEC_RECORDS, WS_LZ4HC_ENC, WS_DEFLATE_ENC, WS_ZSTD_ENC, WS_ZSTD_DEC, WS_BZIP2_DEC, WS_BZIP2_ENC, WS_LZMA_ENC, WS_BROTLI_ENC = range(13)
+WS_SNAPPY_ENC, WS_LZ4_ENC, WS_FASTLZ_ENC, WS_LZF_ENC, WS_DEC_RECORDS, WS_LZ4HC_ENC, WS_DEFLATE_ENC, WS_ZSTD_ENC, WS_ZSTD_DEC, WS_BZIP2_DEC, WS_BZIP2_ENC, WS_LZMA_ENC, WS_BROTLI_ENC, WS_BROTLI_DEC = range(14)
 
 
 def workspace_info(kind: int) -> tuple[int, int]:
@@ -410,6 +410,66 @@ def bzip2_decode_host(data: bytes, out_cap: int):
     ol, cs = C.c_size_t(0), C.c_size_t(0)
     st = _lib.load().nx_bzip2_decode_host(data, len(data), C.cast(buf, C.c_void_p), int(out_cap), C.byref(ol), C.byref(cs))
     return st, buf.raw[:ol.value], cs.value
+
+
+def brotli_decode(inp, in_off, in_len, out, out_off, out_cap):
+    """One complete Brotli stream (RFC 7932) per item (nx_brotli_decode_batch): item i starts at inp[in_off[i]],
+    bytes after its end inside in_len[i] are left alone; it decodes into out[out_off[i] : + out_cap[i]].  Returns
+    (out_len, consumed, status): the decoded size (on an error, what was written before it), the stream's size
+    through the byte that holds its last bit (0 on an error) and 0 or one NX_ERR_BROTLI_* code (-154 .. -171) per
+    item, libbrotli's format errors one for one plus TRUNCATED (-170) and OUTPUT_FULL (-171)."""
+    n = in_len.numel()
+    dev = inp.device
+    out_len = torch.empty(n, dtype=torch.int32, device=dev)
+    consumed = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    _chk(_lib.load().nx_brotli_decode_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off), _ptr(out_cap),
+                                            _ptr(out_len), _ptr(consumed), _ptr(status), n, _stream()), "nx_brotli_decode_batch")
+    return out_len, consumed, status
+
+
+def brotli_decoder_reserve(max_streams: int):
+    """nx_brotli_decoder_reserve: size the decoder's tree workspace for max_streams streams in flight now and
+    cap it there until workspaces_trim()."""
+    _chk(_lib.load().nx_brotli_decoder_reserve(int(max_streams), _stream()), "nx_brotli_decoder_reserve")
+
+
+def brotli_decode_host(data: bytes, out_cap: int, stats: bool = False):
+    """nx_brotli_decode_host on host bytes: (status, decoded bytes, consumed) of the first stream of `data`, by
+    the kernel's format functions on the CPU (the tests' second opinion, not a product path); with stats=True a
+    fourth element, the nx_brotli_decode_stats census as a dict (arrays as lists)."""
+    import ctypes as C
+    data = bytes(data)
+    buf = C.create_string_buffer(max(int(out_cap), 1))
+    ol, cs = C.c_size_t(0), C.c_size_t(0)
+    census = _lib.BrotliDecodeStats()
+    st = _lib.load().nx_brotli_decode_host(data, len(data), C.cast(buf, C.c_void_p), int(out_cap), C.byref(ol), C.byref(cs),
+                                           C.byref(census) if stats else None)
+    if not stats:
+        return st, buf.raw[:ol.value], cs.value
+    d = {}
+    for name, _ in census._fields_:
+        v = getattr(census, name)
+        d[name] = v if isinstance(v, int) else list(v)
+    return st, buf.raw[:ol.value], cs.value, d
+
+
+def brotli_transform_word(transform: int, word: bytes):
+    """nx_brotli_transform_word: `word` (4..24 bytes) under transform 0..120 of RFC 7932 Appendix B."""
+    import ctypes as C
+    out = C.create_string_buffer(40)
+    n = _lib.load().nx_brotli_transform_word(int(transform), bytes(word), len(word), C.cast(out, C.c_void_p))
+    if n < 0:
+        raise ValueError(f"nx_brotli_transform_word: {_lib.status_string(n)}")
+    return out.raw[:n]
+
+
+def brotli_dictionary() -> bytes:
+    """nx_brotli_dictionary: the static dictionary of RFC 7932 Appendix A."""
+    import ctypes as C
+    size = C.c_size_t(0)
+    p = _lib.load().nx_brotli_dictionary(C.byref(size))
+    return C.string_at(p, size.value)
 
 
 def bzip2_stream_info(data: bytes):

@@ -51,6 +51,24 @@ extern "C" const char* nx_status_string(int32_t s) {
         case NX_ERR_BROTLI_LGWIN: return "lgwin should be in range [10, 24], or -1";
         case NX_ERR_BROTLI_MODE: return "mode should be GENERIC, TEXT or FONT";
         case NX_ERR_BROTLI_ENCODE_FULL: return "the Brotli stream does not fit the output slot";
+        case NX_ERR_BROTLI_EXUBERANT_NIBBLE: return "EXUBERANT_NIBBLE";
+        case NX_ERR_BROTLI_RESERVED: return "RESERVED";
+        case NX_ERR_BROTLI_EXUBERANT_META_NIBBLE: return "EXUBERANT_META_NIBBLE";
+        case NX_ERR_BROTLI_SIMPLE_HUFFMAN_ALPHABET: return "SIMPLE_HUFFMAN_ALPHABET";
+        case NX_ERR_BROTLI_SIMPLE_HUFFMAN_SAME: return "SIMPLE_HUFFMAN_SAME";
+        case NX_ERR_BROTLI_CL_SPACE: return "CL_SPACE";
+        case NX_ERR_BROTLI_HUFFMAN_SPACE: return "HUFFMAN_SPACE";
+        case NX_ERR_BROTLI_CONTEXT_MAP_REPEAT: return "CONTEXT_MAP_REPEAT";
+        case NX_ERR_BROTLI_BLOCK_LENGTH_1: return "BLOCK_LENGTH_1";
+        case NX_ERR_BROTLI_BLOCK_LENGTH_2: return "BLOCK_LENGTH_2";
+        case NX_ERR_BROTLI_TRANSFORM: return "TRANSFORM";
+        case NX_ERR_BROTLI_DICTIONARY: return "DICTIONARY";
+        case NX_ERR_BROTLI_WINDOW_BITS: return "WINDOW_BITS";
+        case NX_ERR_BROTLI_PADDING_1: return "PADDING_1";
+        case NX_ERR_BROTLI_PADDING_2: return "PADDING_2";
+        case NX_ERR_BROTLI_DISTANCE: return "DISTANCE";
+        case NX_ERR_BROTLI_TRUNCATED: return "the input ends inside the Brotli stream";
+        case NX_ERR_BROTLI_OUTPUT_FULL: return "the decoded bytes do not fit the output";
         case NX_ERR_LZ4_ENCODE_FINISHED: return "encode finished and not enough space to write remaining data";
         case NX_ERR_SNAPPY_PREAMBLE_TOO_LONG: return "Preamble is greater than 4 bytes";
         case NX_ERR_SNAPPY_OFFSET_ZERO: return "Offset is less than minimum permissible value";

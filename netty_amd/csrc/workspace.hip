@@ -90,6 +90,7 @@ size_t ws_want(WsKind k, uint32_t n, int cus) {
     if (k == WsKind::Lz4HcEnc) return hc_slots(n, cus);
     if (k == WsKind::ZstdDec) return std::min<size_t>(n, (size_t)cus * kZstdDecWavesPerCu);
     if (k == WsKind::Bzip2Dec) return std::min<size_t>(n, (size_t)cus * kBzip2DecWavesPerCu);
+    if (k == WsKind::BrotliDec) return std::min<size_t>(n, (size_t)cus * kBrotliDecWavesPerCu);
     if (k == WsKind::Bzip2Enc) return n;  // units: the callers count streams x level (bzip2_encode.hip)
     return lane_grid(n, cus, kWsSpec[(int)k].waves_per_cu).slots;
 }

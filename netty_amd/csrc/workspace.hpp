@@ -20,7 +20,7 @@
 
 namespace nx {
 
-enum class WsKind : int { SnappyEnc = 0, Lz4Enc, FastLzEnc, LzfEnc, DecRecords, Lz4HcEnc, DeflateEnc, ZstdEnc, ZstdDec, Bzip2Dec, Bzip2Enc, LzmaEnc, BrotliEnc, Count };
+enum class WsKind : int { SnappyEnc = 0, Lz4Enc, FastLzEnc, LzfEnc, DecRecords, Lz4HcEnc, DeflateEnc, ZstdEnc, ZstdDec, Bzip2Dec, Bzip2Enc, LzmaEnc, BrotliEnc, BrotliDec, Count };
 
 // Table geometry per encoder kind (entry bytes, log2 entries per table, waves per CU of its launch);
 // each codec static_asserts its own constants against this.
@@ -49,6 +49,9 @@ struct WsSpec {
 // launch pair as ZstdEnc; the items' sequence words live in the workspace's side allocation (SharedWs::side), sized
 // per call from the lengths (WsAreaCut).
 // BrotliEnc: the same geometry for the Brotli matcher (brotli.hip), with the same use of its own side allocation.
+// BrotliDec: no tables: one slot per stream in flight holds a meta-block's trees and context maps at the format's
+// maxima (802 304 bytes; brotli_decode.hip derives it), leased by part, one slot per wave of the launch on at most
+// kBrotliDecWavesPerCu waves per CU.
 #ifndef NX_LZ4_WPCU  // build options for A/B runs of the alt encoders' occupancy (scripts/build_lib_variant.sh; LZ4 at 20: level)
 #define NX_LZ4_WPCU 16
 #endif
@@ -58,7 +61,7 @@ struct WsSpec {
 #ifndef NX_LZF_WPCU  // LZF: 16 waves per CU measured level with 8 (profiles/r06/s4), so the smaller workspace stays
 #define NX_LZF_WPCU 8
 #endif
-constexpr WsSpec kWsSpec[] = {{8, 14, 20}, {8, 13, NX_LZ4_WPCU}, {8, 13, NX_FLZ_WPCU}, {8, 14, NX_LZF_WPCU}, {0, 0, 0}, {8, 15, 2}, {8, 14, 16}, {8, 16, 16}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {8, 16, 16}, {8, 16, 16}};
+constexpr WsSpec kWsSpec[] = {{8, 14, 20}, {8, 13, NX_LZ4_WPCU}, {8, 13, NX_FLZ_WPCU}, {8, 14, NX_LZF_WPCU}, {0, 0, 0}, {8, 15, 2}, {8, 14, 16}, {8, 16, 16}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {8, 16, 16}, {8, 16, 16}, {0, 0, 0}};
 static_assert(sizeof(kWsSpec) / sizeof(kWsSpec[0]) == (size_t)WsKind::Count, "one spec per kind");
 constexpr size_t kDecSlotBytes = 16384u * 4u + 8u;  // records of one frame + its count and length
 #ifndef NX_DEC_MAX_FRAMES  // build option for A/B runs (scripts/build_lib_variant.sh)
@@ -76,9 +79,14 @@ constexpr size_t kBzip2EncUnitBytes = 24u * 100000u + 4096u;
 // k_bzip2_encode is one workgroup of 1 024 lanes with about 69 KiB of LDS: one per CU, 256 slots, 5.5 GB at level 9
 // (615 MB at level 1) on 256 CUs
 constexpr unsigned kBzip2EncGroupsPerCu = 1;
+// 256 literal, command and distance trees at 544, 1 440 and 1 072 bytes, the block trees, the context maps and their
+// code: 802 216 bytes (brotli_decode.hip's header has the sum), rounded up to a multiple of 256
+constexpr size_t kBrotliDecSlotBytes = 802304;
+// k_brotli_decode keeps about 3 KiB of LDS per wave; four waves per CU leave one per SIMD and 822 MB of slots on 256 CUs
+constexpr unsigned kBrotliDecWavesPerCu = 4;
 // bytes per slot of a kind without tables (0 for the table kinds)
 constexpr size_t ws_plain_slot_bytes(WsKind k) {
-    return k == WsKind::DecRecords ? kDecSlotBytes : k == WsKind::ZstdDec ? kZstdDecSlotBytes : k == WsKind::Bzip2Dec ? kBzip2DecSlotBytes : k == WsKind::Bzip2Enc ? kBzip2EncUnitBytes : 0;
+    return k == WsKind::DecRecords ? kDecSlotBytes : k == WsKind::ZstdDec ? kZstdDecSlotBytes : k == WsKind::Bzip2Dec ? kBzip2DecSlotBytes : k == WsKind::Bzip2Enc ? kBzip2EncUnitBytes : k == WsKind::BrotliDec ? kBrotliDecSlotBytes : 0;
 }
 
 struct WsUse {  // an in-flight part lease: slots [a, b), done when ev completes

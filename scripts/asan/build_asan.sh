@@ -9,7 +9,7 @@ set -eu
 cd "$(dirname "$0")/../.."
 H=/opt/rocm/bin/hipcc
 SAN=${SAN:-address}  # SAN=address,undefined adds UBSan (host side too)
-F="-O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -munsafe-fp-atomics -Xarch_host -fsanitize=$SAN -Xarch_host -fno-omit-frame-pointer"
+F="-O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -munsafe-fp-atomics -Xarch_host -fsanitize=$SAN -Xarch_host -fno-omit-frame-pointer -DNX_BROTLI_DICT_PATH=\"netty_amd/csrc/brotli_dictionary.bin\""
 O=netty_amd/build_asan
 mkdir -p $O
 objs=""
